@@ -28,7 +28,7 @@ def _bench(*args, timeout=240):
 
 
 def test_devices_mode_one_gpu_2_20():
-    r = _bench("--gpus", "1", "--mode", "devices", "--steps", "6", "--warmup", "2", "--no-extras",
+    r = _bench("--gpus", "1", "--mode", "devices", "--steps", "6", "--warmup", "2", "--full", "--no-extras",
                "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -42,11 +42,35 @@ def test_devices_mode_one_gpu_2_20():
 def test_devices_mode_with_extras_2_18():
     # the lone-MSM latency over the resident shards and the multi-device host-array pass, checked
     r = _bench("--gpus", "1", "--mode", "devices", "--n", str(1 << 18), "--steps", "4", "--warmup", "1",
-               "--no-cpu-baseline")
+               "--full", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["correct"] is True and out["latency_ms"] > 0
     assert out["multi_device"]["correct"] is True
+
+
+def test_plain_run_dumps_last_step_2_16(tmp_path):
+    # a plain run (no --full): the headline fields only, every timed result checked, and
+    # --dump-outputs writes the last timed step's 16 wire words (step 1 + 3 - 1 = 3 -> scalar set 3)
+    import numpy as np
+
+    n = 1 << 16
+    r = _bench("--gpus", "1", "--n", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["results_checked"] == 3 and out["correct"] is True
+    assert out["ms_per_step"] == out["value"] > 0 and out["unit"] == "ms/MSM" and out["higher_is_better"] is False
+    assert out["roofline"] is None and "cpu_baseline" not in out and "latency_ms" not in out
+    assert [p.name for p in (tmp_path / "out").iterdir()] == ["msm_result.npy"]
+    got = np.load(tmp_path / "out" / "msm_result.npy")
+    assert got.dtype == np.float64 and got.shape == (16,)
+    with open(os.path.join(ROOT, "tests", "golden", "bench_expected.json")) as f:
+        x, y = json.load(f)["rows"][f"{n}:3"]
+    words = [int(w) for w in got]
+    assert sum(w << (32 * (7 - i)) for i, w in enumerate(words[:8])) == int(x)
+    assert sum(w << (32 * (7 - i)) for i, w in enumerate(words[8:])) == int(y)
 
 
 def test_more_gpus_than_visible_fails():

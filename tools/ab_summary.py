@@ -33,7 +33,7 @@ def main():
                       "accumulate_ms_median", "run_length", "correct"):
                 row[k] = d.get(k)
         else:
-            r = d.get("roofline", {})
+            r = d.get("roofline") or {}  # null in a line of a run without --full
             c = r.get("compute_roofline") or d.get("compute_roofline") or {}
             row.update(value=d.get("value"), kernel_ms=r.get("kernel_ms"), latency_ms=d.get("latency_ms"),
                        frac_isa_measured=c.get("frac_isa_measured"),

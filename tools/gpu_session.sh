@@ -9,7 +9,7 @@
 #   tests        the -m gpu parity suites (libmsm.so)
 #   tests_alt    the same with eager launches, then with one slot and one MSM per launch
 #   testslib:LIBS  the parity suites (random sweep aside) against in-tree library variants
-#   bench        python bench.py (the driver's command)
+#   bench        python bench.py --full (the headline and every other figure)
 #   bench50      50 timed steps, no extras
 #   sizes        pipelined ms per MSM at 2^16..2^19 (20 and 50 steps)
 #   size:LG:LIBS pipelined ms per MSM at 2^LG points for each listed library variant
@@ -59,7 +59,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 LIBDIR=$PWD/webgpu-msm_amd/msm_amd/_lib
-BENCH_Q=(--no-cpu-baseline)
+BENCH_Q=(--full --no-cpu-baseline)  # --full: the records keep kernel_ms and the rooflines (tools/ab_summary.py)
 
 run() {  # name timeout cmd...
   local name=$1 to=$2; shift 2
@@ -90,7 +90,7 @@ for step in "$@"; do
       for lib in ${libs//,/ }; do
         MSM_AMD_LIB=$LIBDIR/$lib run "tests_${lib%.so}" 900 "${PYTEST[@]}" -k "not random_sweep"
       done ;;
-    bench) run bench 300 python bench.py ;;
+    bench) run bench 300 python bench.py --full ;;
     bench50) run bench50 300 python bench.py --steps 50 --warmup 20 --no-extras "${BENCH_Q[@]}" ;;
     steps:*)  # steps:K1,K2[:R] -- 2^20 bench over timed step counts (pipeline fill / drain share)
       IFS=: read -r _ ks rounds <<< "$step"
@@ -119,8 +119,8 @@ for step in "$@"; do
         run size$lg 120 python bench.py --steps 50 --warmup 20 --no-extras "${BENCH_Q[@]}" --n $((1 << lg))
         run size${lg}_k20 120 python bench.py --no-extras "${BENCH_Q[@]}" --n $((1 << lg))
       done ;;
-    batch64) run "batch64${KS:-}" 300 python bench.py --batch 64 --n 262144 ;;
-    batch64d) run "batch64d${KS:-}" 300 python bench.py --batch 64 --n 262144 --distinct ;;  # distinct base vectors
+    batch64) run "batch64${KS:-}" 300 python bench.py --full --batch 64 --n 262144 ;;
+    batch64d) run "batch64d${KS:-}" 300 python bench.py --full --batch 64 --n 262144 --distinct ;;  # distinct base vectors
     gloo8)
       MSM_DIST_BACKEND=gloo OMP_NUM_THREADS=2 run gloo8 400 python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 10 --warmup 2 \
@@ -129,7 +129,7 @@ for step in "$@"; do
     sharded) run sharded 300 python tools/sharded_probe.py ;;  # the device-list host path, D repeated shards
     rocprof20)  # the driver-shape bench (20 steps, 5 warm-up) under a kernel trace: must exit 0
       run rocprof20 300 rocprofv3 --kernel-trace --stats --output-format csv -d "gpurun_out/${TAG}_rocprof20_d" -o run \
-        -- python3 bench.py --steps 20 --warmup 5 ;;
+        -- python3 bench.py --full --steps 20 --warmup 5 ;;
     split) run split 600 python tools/split_probe.py --gpus 8 ;;
     splitrl:*)  # splitrl:K1,K2[:R] -- the 4 x 2 (c = 15) shares of an 8-GPU split over accumulation run lengths
       IFS=: read -r _ ks rounds <<< "$step"
@@ -153,7 +153,7 @@ for step in "$@"; do
         -d "gpurun_out/${TAG}_splitk${KS:-}_d" -o run -- python3 tools/split_probe.py --gpus 8 --splits 4x2 --window 15 ;;
     kstats)
       run kstats 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_kstats_d -o run \
-        -- python3 bench.py ;;
+        -- python3 bench.py --full ;;
     ktrace:*)  # ktrace:VAR=A,B -- rocprofv3 kernel trace of the pipelined bench for each value of one knob
       IFS=: read -r _ spec <<< "$step"
       var=${spec%%=*}; vals=${spec#*=}
