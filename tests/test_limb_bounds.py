@@ -16,13 +16,11 @@ arithmetic on the limb maxima) and asserts:
 It mirrors the kernels by hand; test_mirrored_sources_unchanged pins a digest of every mirrored
 function body, so an edit to fp29.cuh / ec.cuh fails until the model here is re-reviewed.
 """
-P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
-NL, LB = 9, 29
-MASK = (1 << LB) - 1
-R = 1 << 261
-P29 = [(P >> (LB * i)) & MASK for i in range(NL)]
-K8P29 = [536870920, 610271231, 536871443, 661646591, 939568340, 880373981, 718018184, 1050291364, 9788201]
-K5P29 = [536870917, 851181567, 536871243, 681964575, 654339076, 550233738, 717196821, 991976422, 6117625]
+# the constants and the bit-exact models (fe_mul_exact, fe_mul_sd_exact, fe_mul_2d_exact, fe_mul_d_exact)
+# live in tests/_fp29_model.py, shared with the limb-for-limb device comparison (tests/test_gpu_limbs.py)
+from _fp29_model import (DELTA_SD_LOG, K2D_INT, K5P29, K8P29, KD_INT, LB, MASK, NL, P, P29, R,  # noqa: F401
+                         SD_OFF58, WIDE_ALL, WIDE_EF, WIDE_EH, WIDE_GH, fe_mul_2d_exact, fe_mul_d_exact,
+                         fe_mul_exact, fe_mul_sd_exact, sd_seed, seed, value_of)
 
 
 class B:
@@ -39,19 +37,6 @@ class B:
 
 
 N_MUL = B.normalised(2 * P)  # fe_mul output: normalised, value < 2p
-
-
-def value_of(limbs):
-    return sum(x << (LB * i) for i, x in enumerate(limbs))
-
-
-WIDE_ALL, WIDE_GH, WIDE_EH, WIDE_EF = 0xFF, 0xE7, 0xBF, 0xEF  # fp29.cuh: steps with a 32-bit digit
-
-
-def seed(wide: int, k: int) -> int:
-    """fp29.cuh fe_mul_seed: register offset of column k (2^32 - 1 on the reduction columns, -7
-    after a narrow step)."""
-    return ((1 << 32) - 1 if k <= NL - 1 else 0) - (7 if k >= 1 and not (wide >> (k - 1)) & 1 else 0)
 
 
 def digit_max(wide: int, i: int) -> int:
@@ -75,89 +60,6 @@ def fe_mul(a: B, b: B, wide: int = WIDE_ALL) -> B:
         # carry out: (column + digit) / 2^29 on the reduction columns, column >> 29 above
         carry = (col + digit_max(wide, k)) >> LB if k < NL else col >> LB
     return N_MUL
-
-
-def fe_mul_exact(a, b, wide: int = WIDE_ALL):
-    """Bit-exact model of fp29.cuh fe_mul_w<wide> on limb lists (64-bit register wrap checked):
-    returns the 9 output limbs."""
-    M64 = (1 << 64) - 1
-    c = [0] * (2 * NL)
-    for k in range(NL + 1):
-        c[k] = seed(wide, k) & M64
-    for i in range(NL):
-        for j in range(NL):
-            c[i + j] = (c[i + j] + a[i] * b[j]) & M64
-    for i in range(NL):
-        lo = c[i] & 0xFFFFFFFF
-        if i < NL - 1 and (wide >> i) & 1:
-            m = ~lo & 0xFFFFFFFF
-            c[i + 1] = (c[i + 1] + 8 * (c[i] >> 32)) & M64
-        else:
-            m = ~lo & MASK
-            c[i + 1] = (c[i + 1] + (c[i] >> LB)) & M64
-        for j in range(1, NL):
-            c[i + j] = (c[i + j] + m * P29[j]) & M64
-    r = [0] * NL
-    for k in range(NL, 2 * NL - 1):
-        c[k + 1] = (c[k + 1] + (c[k] >> LB)) & M64
-        r[k - NL] = c[k] & MASK
-    r[NL - 1] = c[2 * NL - 1] & 0xFFFFFFFF
-    return r
-
-
-K2D_INT, MU2D = 6042, (1 << 284) // P
-
-
-def fe_mul_2d_exact(v: int):
-    """Bit-exact model of fp29.cuh fe_mul_2d on the normalised representation of v (< 2^254):
-    returns (limbs, value)."""
-    a = [(v >> (LB * i)) & MASK for i in range(NL - 1)] + [v >> (LB * (NL - 1))]
-    r, c = [0] * NL, 0
-    for i in range(NL - 1):
-        c = a[i] * K2D_INT + c
-        assert c < 1 << 64
-        r[i] = c & MASK
-        c >>= LB
-    c = a[NL - 1] * K2D_INT + c
-    assert c >> 20 < 1 << 32
-    q = ((c >> 20) * MU2D) >> 32
-    d = 0
-    for i in range(NL - 1):
-        d += r[i] - q * P29[i]
-        assert -(1 << 63) <= d < 1 << 63
-        r[i] = d & MASK
-        d >>= LB  # Python's >> is arithmetic, like the int64 shift
-    r[NL - 1] = d + c - q * P29[NL - 1]
-    assert 0 <= r[NL - 1] < 1 << 32
-    return r, value_of(r)
-
-
-KD_INT, MU272 = 3021, (1 << 272) // P
-
-
-def fe_mul_d_exact(v: int):
-    """Bit-exact model of fp29.cuh fe_mul_d on the normalised representation of v (< 2^254):
-    returns (limbs, value)."""
-    a = [(v >> (LB * i)) & MASK for i in range(NL - 1)] + [v >> (LB * (NL - 1))]
-    r, c = [0] * NL, 0
-    for i in range(NL - 1):
-        c = a[i] * KD_INT + c
-        assert c < 1 << 64
-        r[i] = c & MASK
-        c >>= LB
-    c = a[NL - 1] * KD_INT + c
-    assert c < 1 << 34
-    q = ((c >> 8) * MU272) >> 32
-    assert q < 1 << 32
-    d = 0
-    for i in range(NL - 1):
-        d += r[i] - q * P29[i]
-        assert -(1 << 63) <= d < 1 << 63
-        r[i] = d & MASK
-        d >>= LB
-    r[NL - 1] = d + c - q * P29[NL - 1]
-    assert 0 <= r[NL - 1] < 1 << 32
-    return r, value_of(r)
 
 
 def fe_mul_2d(a: B) -> B:
@@ -207,16 +109,6 @@ ONE29 = 536870474 + (276299775 << 29)  # value of Montgomery one is < p; covered
 
 
 # ---- signed differences (fp29.cuh fe_sub_s / fe_mul_sd, pt_madd) ----------------------------------
-DELTA_SD_LOG = 26  # fp29.cuh: the bias DELTA_SD p 2^232 added through the seeds of columns 8..16
-SD_OFF58 = [-1, -3, -3, -5, -9, -9, -12, -14, -14, -12, -11, -9, -6, -5, -2, -1, -1, 0]  # fp29.cuh: O_k / 2^58
-
-
-def sd_seed(wide: int, k: int) -> int:
-    """fp29.cuh fe_mul_sd_seed as a signed integer: register offset + bias + O_k - O_(k-1) / 2^29."""
-    bias = (P29[k - (NL - 1)] << DELTA_SD_LOG) if NL - 1 <= k < 2 * NL - 1 else 0
-    return (seed(wide, k) if k <= NL else 0) + bias + (SD_OFF58[k] << 58) - ((SD_OFF58[k - 1] << 29) if k >= 1 else 0)
-
-
 class SB:
     """Interval bounds of a field element with signed limbs: per-limb [lo, hi] and value [vlo, vhi]
     (all inclusive)."""
@@ -300,44 +192,6 @@ def test_madd_bounds():
         fe_mul(G, H)
         fe_mul_sd(E, SB.of(H))
         fe_mul_sd(F, SB.of(G))
-
-
-def fe_mul_sd_exact(a, b, wide: int = WIDE_ALL):
-    """Bit-exact model of fp29.cuh fe_mul_sd on limb lists (signed limbs; 64-bit two's-complement
-    registers, wrap checked against the true integers): returns the 9 output limbs."""
-    M64 = (1 << 64) - 1
-
-    def s64(x):
-        x &= M64
-        return x - (1 << 64) if x >> 63 else x
-
-    def s32(x):
-        x &= 0xFFFFFFFF
-        return x - (1 << 32) if x >> 31 else x
-
-    c = [sd_seed(wide, k) for k in range(2 * NL)]  # the registers, as signed integers
-    for i in range(NL):
-        for j in range(NL):
-            c[i + j] += s32(a[i]) * s32(b[j])
-    for i in range(NL):
-        assert -(1 << 63) <= c[i] < 1 << 63
-        lo = c[i] & 0xFFFFFFFF
-        if i < NL - 1 and (wide >> i) & 1:
-            m = ~lo & 0xFFFFFFFF
-            c[i + 1] += 8 * s32(c[i] >> 32)
-        else:
-            m = ~lo & MASK
-            c[i + 1] += c[i] >> LB
-        for j in range(1, NL):
-            c[i + j] += m * P29[j]
-    r = [0] * NL
-    for k in range(NL, 2 * NL - 1):
-        assert -(1 << 63) <= c[k] < 1 << 63
-        c[k + 1] += c[k] >> LB
-        r[k - NL] = c[k] & MASK
-    assert 0 <= c[2 * NL - 1] < 1 << 32
-    r[NL - 1] = c[2 * NL - 1]
-    return [x & 0xFFFFFFFF for x in r]
 
 
 def test_sd_offsets_match_header():
@@ -598,6 +452,26 @@ REVIEWED = {
     ("ec.cuh", "pt_dbl"): "784353f9934ef437",
     ("ec.cuh", "kt_neg_if"): "19c79f3cf45dee09",
     ("ec.cuh", "pt_add_quad"): "875eba21c1f11e82",
+    # mirrored by the limb-exact model only (tests/_fp29_model.py, compared with the device by
+    # tests/test_gpu_limbs.py)
+    ("fp29.cuh", "opaque_s"): "46cf266b295cbf08",
+    ("fp29.cuh", "fe_sqr"): "f8e70a3f2dd0089a",
+    ("fp29.cuh", "fe_geq_p"): "4eb5d532c3233462",
+    ("fp29.cuh", "fe_sub_p"): "d1a009c0411c837b",
+    ("fp29.cuh", "fe_to_std"): "b8ce08d971edfe7f",
+    ("fp29.cuh", "fe_to_host_mont"): "307abc9eeb63e40d",
+    ("fp29.cuh", "fe_to_mont"): "1504f8a92b704f1a",
+    ("fp29.cuh", "fe_from_words_le"): "452047bc0d4e746b",
+    ("fp29.cuh", "fe_to_words_le"): "75b7e2c51d7e06c8",
+    ("fp29.cuh", "words_lt_p"): "7561894852928329",
+    ("fp29.cuh", "fe_inv"): "7178747f7853f144",
+    ("fp29.cuh", "ONE29"): "e27181d893aa29eb",
+    ("fp29.cuh", "R2_29"): "a66b69c23bcae68b",
+    ("fp29.cuh", "R2H_29"): "67d729fb41ed6ee0",
+    ("fp29.cuh", "HALF29"): "fb513a1a00dd9fdd",
+    ("fp29.cuh", "R256_29"): "d4cab8ce33c9709c",
+    ("msm_kernels.hip", "k_prepare_points"): "931ef0feb027c2bc",
+    ("msm_kernels.hip", "load_pre_signed"): "05db1a9e570b7dcc",
 }
 
 

@@ -2813,6 +2813,36 @@ int multi_many_entry(const ManyInputs& in, size_t n, size_t count, const msm_opt
   });
 }
 
+// ---- helpers of the device test hooks (msm_test_field_op .. msm_test_records) -------------------
+// A device buffer of one hook call: freed when the call returns, on its HIPCHECK exits too.
+struct TestBuf {
+  uint32_t* p = nullptr;
+  TestBuf() = default;
+  TestBuf(const TestBuf&) = delete;
+  TestBuf& operator=(const TestBuf&) = delete;
+  ~TestBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+
+// One k_test_limbs* instantiation per LimbOp (msm_kernels.hip), picked by the runtime op.
+template <int OP>
+void launch_limb_op(const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  const dim3 g(grid_for(n, 256)), t(256);
+  if constexpr (OP == LOP_PT_QUAD)
+    hipLaunchKernelGGL(k_test_limbs_quad, dim3(grid_for(4 * (size_t)n, 256)), t, 0, 0, a, b, out, n);
+  else if constexpr (OP >= LOP_PT_ADD)
+    hipLaunchKernelGGL(k_test_limbs_point<OP>, g, t, 0, 0, a, b, neg, out, n);
+  else
+    hipLaunchKernelGGL(k_test_limbs<OP>, g, t, 0, 0, a, b, out, n);
+}
+template <int... OPS>
+void dispatch_limb_op(int op, std::integer_sequence<int, OPS...>, const uint32_t* a, const uint32_t* b,
+                      const uint32_t* neg, uint32_t* out, uint32_t n) {
+  ((op == OPS ? launch_limb_op<OPS>(a, b, neg, out, n) : (void)0), ...);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3387,18 +3417,15 @@ int msm_test_field_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_
   int rc = get_ctx(-1, &c);
   if (rc != MSM_OK) return rc;
   std::lock_guard<std::mutex> lk(c->mu);
-  uint32_t *da, *db, *dout;
-  HIPCHECK(hipMalloc(&da, n * 32 + 32));
-  HIPCHECK(hipMalloc(&db, n * 32 + 32));
-  HIPCHECK(hipMalloc(&dout, n * 32 + 32));
-  HIPCHECK(hipMemcpy(da, a, n * 32, hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(db, b, n * 32, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_test_field, dim3(grid_for(n, 256)), dim3(256), 0, 0, da, db, dout, (uint32_t)n, op);
+  TestBuf da, db, dout;  // freed on every return path
+  HIPCHECK(da.alloc(n * 32 + 32));
+  HIPCHECK(db.alloc(n * 32 + 32));
+  HIPCHECK(dout.alloc(n * 32 + 32));
+  HIPCHECK(hipMemcpy(da.p, a, n * 32, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(db.p, b, n * 32, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_field, dim3(grid_for(n, 256)), dim3(256), 0, 0, da.p, db.p, dout.p, (uint32_t)n, op);
   HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpy(out, dout, n * 32, hipMemcpyDeviceToHost));
-  hipFree(da);
-  hipFree(db);
-  hipFree(dout);
+  HIPCHECK(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
   return MSM_OK;
 }
 
@@ -3407,25 +3434,98 @@ int msm_test_point_op(uint32_t op, const uint32_t* p, const uint32_t* q, uint32_
   int rc = get_ctx(-1, &c);
   if (rc != MSM_OK) return rc;
   std::lock_guard<std::mutex> lk(c->mu);
-  uint32_t *dp, *dq, *dout;
-  HIPCHECK(hipMalloc(&dp, n * 64 + 64));
-  HIPCHECK(hipMalloc(&dq, n * 64 + 64));
-  HIPCHECK(hipMalloc(&dout, n * 128 + 128));
-  HIPCHECK(hipMemcpy(dp, p, n * 64, hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(dq, q, n * 64, hipMemcpyHostToDevice));
+  TestBuf dp, dq, dout;
+  HIPCHECK(dp.alloc(n * 64 + 64));
+  HIPCHECK(dq.alloc(n * 64 + 64));
+  HIPCHECK(dout.alloc(n * 128 + 128));
+  HIPCHECK(hipMemcpy(dp.p, p, n * 64, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(dq.p, q, n * 64, hipMemcpyHostToDevice));
   if (op == 3)
-    hipLaunchKernelGGL(k_test_quad, dim3(grid_for(4 * n, 256)), dim3(256), 0, 0, dp, dq, dout, (uint32_t)n);
+    hipLaunchKernelGGL(k_test_quad, dim3(grid_for(4 * n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
   else if (op == 0)
-    hipLaunchKernelGGL(k_test_point<0>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp, dq, dout, (uint32_t)n);
+    hipLaunchKernelGGL(k_test_point<0>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
   else if (op == 1)
-    hipLaunchKernelGGL(k_test_point<1>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp, dq, dout, (uint32_t)n);
+    hipLaunchKernelGGL(k_test_point<1>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
   else
-    hipLaunchKernelGGL(k_test_point<2>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp, dq, dout, (uint32_t)n);
+    hipLaunchKernelGGL(k_test_point<2>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
   HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpy(out, dout, n * 128, hipMemcpyDeviceToHost));
-  hipFree(dp);
-  hipFree(dq);
-  hipFree(dout);
+  HIPCHECK(hipMemcpy(out, dout.p, n * 128, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// ---- raw-limb hooks (msm_kernels.hip k_test_limbs*, tests/test_gpu_limbs.py) --------------------
+// The four WIDE_* masks this library was built with (fp29.cuh; all 0 under MSM_NARROW_DIGITS).
+int msm_test_wide_masks(uint32_t out[4]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  out[0] = WIDE_ALL;
+  out[1] = WIDE_GH;
+  out[2] = WIDE_EH;
+  out[3] = WIDE_EF;
+  return MSM_OK;
+}
+
+// out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
+// msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
+int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {
+  if (op >= (uint32_t)LOP_COUNT || n == 0 || n > (1u << 24) || !a || !out) return MSM_ERR_INVALID_ARG;
+  const size_t wa = limb_op_in_words((int)op), wb = limb_op_b_words((int)op), wo = limb_op_out_words((int)op);
+  if ((wb && !b) || (op == (uint32_t)LOP_PT_MADD && !neg)) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf da, db, dn, dout;
+  HIPCHECK(da.alloc(n * wa * 4));
+  HIPCHECK(db.alloc(n * (wb ? wb : 1) * 4));
+  HIPCHECK(dn.alloc(n * 4));
+  HIPCHECK(dout.alloc(n * wo * 4));
+  HIPCHECK(hipMemcpy(da.p, a, n * wa * 4, hipMemcpyHostToDevice));
+  if (wb) HIPCHECK(hipMemcpy(db.p, b, n * wb * 4, hipMemcpyHostToDevice));
+  if (op == (uint32_t)LOP_PT_MADD) HIPCHECK(hipMemcpy(dn.p, neg, n * 4, hipMemcpyHostToDevice));
+  dispatch_limb_op((int)op, std::make_integer_sequence<int, LOP_COUNT>{}, da.p, db.p, dn.p, dout.p, (uint32_t)n);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, n * wo * 4, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// k_prepare_points on n input points (fmt: PT_FMT_WIRE 32, PT_FMT_XY 16 or PT_FMT_XYZ 24 BE words
+// each) -> the n 32-word records and the device error word; then, for m > 0, the accumulation's
+// gather and add on them: out[j] = acc[j] + record(ents[j]), ents[j] = index << 1 | sign.
+int msm_test_records(uint32_t fmt, const uint32_t* in, size_t n, uint32_t* records, uint32_t* err,
+                     const uint32_t* ents, const uint32_t* acc, uint32_t* out, size_t m) {
+  if (fmt > PT_FMT_XYZ || !in || !records || !err || n == 0 || n > (1u << 24) || m > (1u << 24))
+    return MSM_ERR_INVALID_ARG;
+  if (m && (!ents || !acc || !out)) return MSM_ERR_INVALID_ARG;
+  for (size_t j = 0; j < m; j++)
+    if ((ents[j] >> 1) >= n) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t in_bytes = n * pt_fmt_slots(fmt) * 16;
+  TestBuf din, dpts, derr, dents, dacc, dout;
+  HIPCHECK(din.alloc(in_bytes));
+  HIPCHECK(dpts.alloc(n * PRE_WORDS * 4));
+  HIPCHECK(derr.alloc(4));
+  HIPCHECK(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemset(derr.p, 0, 4));
+  BatchPtrs bp{};
+  bp.p[0] = din.p;
+  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(n, PP_THREADS), 1), dim3(PP_THREADS), 0, 0, bp, dpts.p, (uint32_t)n,
+                     derr.p, 0u, fmt);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(records, dpts.p, n * PRE_WORDS * 4, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(err, derr.p, 4, hipMemcpyDeviceToHost));
+  if (!m) return MSM_OK;
+  HIPCHECK(dents.alloc(m * 4));
+  HIPCHECK(dacc.alloc(m * PT_WORDS * 4));
+  HIPCHECK(dout.alloc(m * PT_WORDS * 4));
+  HIPCHECK(hipMemcpy(dents.p, ents, m * 4, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(dacc.p, acc, m * PT_WORDS * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_limbs_gather, dim3(grid_for(m, 256)), dim3(256), 0, 0, dpts.p, dents.p, dacc.p, dout.p,
+                     (uint32_t)m);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, m * PT_WORDS * 4, hipMemcpyDeviceToHost));
   return MSM_OK;
 }
 

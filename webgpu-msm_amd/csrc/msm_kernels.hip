@@ -2137,4 +2137,120 @@ extern "C" __global__ void k_test_quad(const uint32_t* __restrict__ p, const uin
   }
 }
 
+// ---- raw-limb hooks (tests/test_gpu_limbs.py) ---------------------------------------------------
+// The kernels above convert canonical words on the way in and reduce on the way out, so they see
+// fresh fe_mul outputs only and compare mod p.  These take the 9 u32 limbs of each operand as they
+// are and return every output limb as it is, for a limb-for-limb comparison with the bit-exact
+// model (tests/_fp29_model.py) at operands no conversion produces: the unnormalised forms at
+// their limb maxima, signed differences, values in [p, 2p).  One instantiation per op.
+enum LimbOp : int {
+  LOP_MUL_ALL = 0, LOP_MUL_GH, LOP_MUL_EH, LOP_MUL_EF, LOP_MUL_GHEH,  // fe_mul_w<mask>
+  LOP_MUL_SD_U, LOP_MUL_SD_S,                                         // fe_mul_sd<WIDE_ALL, false | true>
+  LOP_MUL_2D, LOP_MUL_D, LOP_SUB, LOP_NEG, LOP_ADD_N, LOP_DBL_N, LOP_TO_STD, LOP_TO_HOST_MONT, LOP_INV,
+  LOP_FROM_WORDS, LOP_TO_WORDS, LOP_WORDS_LT_P,                       // [n][8] LE words on one side
+  LOP_PT_ADD, LOP_PT_DBL, LOP_PT_MADD, LOP_PT_QUAD,                   // [n][36] X|Y|T|Z limbs
+  LOP_COUNT
+};
+__host__ __device__ constexpr uint32_t limb_op_in_words(int op) {
+  return op >= LOP_PT_ADD ? PT_WORDS : (op == LOP_FROM_WORDS || op == LOP_WORDS_LT_P) ? 8u : (uint32_t)NL;
+}
+__host__ __device__ constexpr uint32_t limb_op_b_words(int op) {  // 0: no second operand
+  return op == LOP_PT_MADD ? 3u * NL : (op == LOP_PT_ADD || op == LOP_PT_QUAD) ? PT_WORDS
+         : (op <= LOP_MUL_SD_S || op == LOP_SUB || op == LOP_ADD_N) ? (uint32_t)NL : 0u;
+}
+__host__ __device__ constexpr uint32_t limb_op_out_words(int op) {
+  return op >= LOP_PT_ADD ? PT_WORDS : op == LOP_TO_WORDS ? 8u : op == LOP_WORDS_LT_P ? 1u : (uint32_t)NL;
+}
+
+template <int OP>
+__global__ void k_test_limbs(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                             uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (OP == LOP_FROM_WORDS || OP == LOP_WORDS_LT_P) {
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = a[(size_t)i * 8 + k];
+    if constexpr (OP == LOP_FROM_WORDS)
+      store_fe(out + (size_t)i * NL, fe_from_words_le(w));
+    else
+      out[i] = words_lt_p(w) ? 1u : 0u;
+  } else if constexpr (OP == LOP_TO_WORDS) {
+    uint32_t w[8];
+    fe_to_words_le(load_fe(a + (size_t)i * NL), w);
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[(size_t)i * 8 + k] = w[k];
+  } else {
+    const fe x = load_fe(a + (size_t)i * NL);
+    fe y = fe_zero();
+    if constexpr (limb_op_b_words(OP) != 0) y = load_fe(b + (size_t)i * NL);
+    fe r;
+    if constexpr (OP == LOP_MUL_ALL) r = fe_mul_w<WIDE_ALL>(x, y);
+    else if constexpr (OP == LOP_MUL_GH) r = fe_mul_w<WIDE_GH>(x, y);
+    else if constexpr (OP == LOP_MUL_EH) r = fe_mul_w<WIDE_EH>(x, y);
+    else if constexpr (OP == LOP_MUL_EF) r = fe_mul_w<WIDE_EF>(x, y);
+    else if constexpr (OP == LOP_MUL_GHEH) r = fe_mul_w<WIDE_GH & WIDE_EH>(x, y);
+    else if constexpr (OP == LOP_MUL_SD_U) r = fe_mul_sd<WIDE_ALL, false>(x, y);
+    else if constexpr (OP == LOP_MUL_SD_S) r = fe_mul_sd<WIDE_ALL, true>(x, y);
+    else if constexpr (OP == LOP_MUL_2D) r = fe_mul_2d(x);
+    else if constexpr (OP == LOP_MUL_D) r = fe_mul_d(x);
+    else if constexpr (OP == LOP_SUB) r = fe_sub(x, y);
+    else if constexpr (OP == LOP_NEG) r = fe_neg(x);
+    else if constexpr (OP == LOP_ADD_N) r = fe_add_n(x, y);
+    else if constexpr (OP == LOP_DBL_N) r = fe_dbl_n(x);
+    else if constexpr (OP == LOP_TO_STD) r = fe_to_std(x);
+    else if constexpr (OP == LOP_TO_HOST_MONT) r = fe_to_host_mont(x);
+    else r = fe_inv(x);
+    store_fe(out + (size_t)i * NL, r);
+  }
+}
+
+// pt_add / pt_dbl / pt_madd on raw extended coordinates.  pt_madd's q is a raw record
+// (ymx | ypx | kt, 27 limbs) and neg[i] != 0 negates it as k_accumulate's gather does: the halves
+// swapped, then kt_neg_if.
+template <int OP>
+__global__ void k_test_limbs_point(const uint32_t* __restrict__ p, const uint32_t* __restrict__ q,
+                                   const uint32_t* __restrict__ neg, uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const xyzt P = load_pt(p + (size_t)i * PT_WORDS);
+  xyzt R;
+  if constexpr (OP == LOP_PT_ADD) {
+    R = pt_add(P, load_pt(q + (size_t)i * PT_WORDS));
+  } else if constexpr (OP == LOP_PT_DBL) {
+    R = pt_dbl(P);
+  } else {
+    const uint32_t* qs = q + (size_t)i * 3 * NL;
+    const bool ng = neg[i] != 0;
+    pre qq;
+    qq.ymx = load_fe(qs + (ng ? NL : 0));
+    qq.ypx = load_fe(qs + (ng ? 0 : NL));
+    qq.kt = kt_neg_if(load_fe(qs + 2 * NL), ng);
+    R = pt_madd(P, qq);
+  }
+  store_pt(out + (size_t)i * PT_WORDS, R);
+}
+
+// pt_add_quad on raw coordinates: pair i on lanes 4i..4i+3, lane c holding coordinate c, as
+// k_test_quad deals them (dead quads of the last wave run on pair 0 and store nothing).
+__global__ void k_test_limbs_quad(const uint32_t* __restrict__ p, const uint32_t* __restrict__ q,
+                                  uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 2, c = threadIdx.x & 3;
+  const bool live = i < n;
+  const uint32_t ii = live ? i : 0;
+  const fe a = load_fe(p + (size_t)ii * PT_WORDS + c * NL), b = load_fe(q + (size_t)ii * PT_WORDS + c * NL);
+  const fe r = pt_add_quad(a, b);
+  if (live) store_fe(out + (size_t)i * PT_WORDS + c * NL, r);
+}
+
+// The gather and add of k_accumulate on prepared records: out[j] = acc[j] + record(ents[j]),
+// ents[j] = point index << 1 | sign (load_pre_signed).  The host checks every index < n.
+__global__ void k_test_limbs_gather(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ents,
+                                    const uint32_t* __restrict__ acc, uint32_t* __restrict__ out, uint32_t m) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const pre q = load_pre_signed(pts, ents[j]);
+  store_pt(out + (size_t)j * PT_WORDS, pt_madd(load_pt(acc + (size_t)j * PT_WORDS), q));
+}
+
 }  // namespace msm

@@ -130,6 +130,9 @@ def load() -> ctypes.CDLL:
         "msm_last_profile": ([ctypes.POINTER(MsmProfile)], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
         "msm_test_point_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
+        "msm_test_wide_masks": ([u32p], ctypes.c_int),
+        "msm_test_limb_op": ([ctypes.c_uint32, vp, vp, vp, u32p, sz], ctypes.c_int),
+        "msm_test_records": ([ctypes.c_uint32, vp, sz, u32p, u32p, vp, vp, u32p, sz], ctypes.c_int),
         "msm_test_shard_range": ([sz, sz, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)], ctypes.c_int),
         "msm_test_sharded": ([ctypes.c_int, vp, vp, sz, optp, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, vp,
                               u32p], ctypes.c_int),
@@ -628,6 +631,55 @@ def _test_point_op(op: int, p: np.ndarray, q: np.ndarray) -> np.ndarray:
     o, op_ = _out(p.shape[0] * 32)
     _check(L.msm_test_point_op(op, _ptr(p), _ptr(q), op_, p.shape[0]), "msm_test_point_op")
     return o.reshape(-1, 32)
+
+
+# Raw-limb test hooks (csrc/msm_kernels.hip LimbOp): name -> (op, words of a, of b, of the output)
+# per element.  Limbs go in and come out as they are, neither converted nor reduced.
+_LIMB_OPS = {name: (i, wa, wb, wo) for i, (name, wa, wb, wo) in enumerate((
+    ("mul_all", 9, 9, 9), ("mul_gh", 9, 9, 9), ("mul_eh", 9, 9, 9), ("mul_ef", 9, 9, 9), ("mul_gheh", 9, 9, 9),
+    ("mul_sd_u", 9, 9, 9), ("mul_sd_s", 9, 9, 9), ("mul_2d", 9, 0, 9), ("mul_d", 9, 0, 9), ("sub", 9, 9, 9),
+    ("neg", 9, 0, 9), ("add_n", 9, 9, 9), ("dbl_n", 9, 0, 9), ("to_std", 9, 0, 9), ("to_host_mont", 9, 0, 9),
+    ("inv", 9, 0, 9), ("from_words", 8, 0, 9), ("to_words", 9, 0, 8), ("words_lt_p", 8, 0, 1),
+    ("pt_add", 36, 36, 36), ("pt_dbl", 36, 0, 36), ("pt_madd", 36, 27, 36), ("pt_add_quad", 36, 36, 36)))}
+
+
+def _test_wide_masks() -> Tuple[int, int, int, int]:
+    """The (WIDE_ALL, WIDE_GH, WIDE_EH, WIDE_EF) reduction masks the loaded library was built with
+    (fp29.cuh; all zero in an MSM_NARROW_DIGITS build).  No GPU needed."""
+    o, op_ = _out(4)
+    _check(load().msm_test_wide_masks(op_), "msm_test_wide_masks")
+    return tuple(int(x) for x in o)
+
+
+def _test_limb_op(name: str, a, b=None, neg=None) -> np.ndarray:
+    """Device op `name` (_LIMB_OPS) on raw u32 limb arrays: a [n, wa], b [n, wb] for the two-operand
+    ops, neg [n] negate flags for pt_madd -> [n, wo] (test hook)."""
+    op, wa, wb, wo = _LIMB_OPS[name]
+    a = _u32(a).reshape(-1, wa)
+    n = a.shape[0]
+    b = _u32(b).reshape(n, wb) if wb else None
+    neg = _u32(neg).reshape(n) if name == "pt_madd" else None
+    o, op_ = _out(n * wo)
+    _check(load().msm_test_limb_op(op, _ptr(a), _ptr(b) if wb else None, _ptr(neg) if neg is not None else None,
+                                   op_, n), "msm_test_limb_op")
+    return o.reshape(n, wo)
+
+
+def _test_records(fmt: int, points, entries=(), acc=None) -> Tuple[np.ndarray, int, np.ndarray]:
+    """k_prepare_points on `points` (BE words; fmt 0: 32-word wire records x|y|t|z, 1: x|y, 2: x|y|z)
+    -> (records [n, 32], device error word, sums [m, 36]): the sums are acc[j] + the record of
+    entries[j] (index << 1 | sign) through load_pre_signed and pt_madd on raw limbs (test hook)."""
+    w = {0: 32, 1: 16, 2: 24}[fmt]
+    pts = _u32(points).reshape(-1, w)
+    n = pts.shape[0]
+    ents = _u32(entries).reshape(-1)
+    m = ents.shape[0]
+    accs = _u32(acc if m else []).reshape(m, 36)
+    rec, rec_ = _out(n * 32)
+    err, err_ = _out(1)
+    o, op_ = _out(max(m, 1) * 36)
+    _check(load().msm_test_records(fmt, _ptr(pts), n, rec_, err_, _ptr(ents), _ptr(accs), op_, m), "msm_test_records")
+    return rec.reshape(n, 32), int(err[0]), o.reshape(-1, 36)[:m]
 
 
 def _test_sharded(mode: int, points, scalars, n: int, devices: Sequence[int], window_size: Optional[int] = None,
