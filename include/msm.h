@@ -218,6 +218,61 @@ int msm_compute_many(const uint32_t* const* points_be, const uint32_t* const* sc
 int msm_compute_shared(const uint32_t* points_be, const uint32_t* const* scalars_be, size_t n, size_t count,
                        const msm_opts* opts, uint32_t* out_xy_be);
 
+/* Resident prepared bases: a prover's base vector stays fixed while every call brings new scalars,
+ * so the vector is prepared once into a handle and each MSM then uploads (host entries) or reads
+ * (device entries) scalars only -- no point upload, no k_prepare_points.
+ *
+ * A handle lives on ONE device (opts->device at creation, -1 = the calling thread's current one)
+ * and holds `levels` copies of the n 128-B prepared records there: level j is 2^(j S) P_i.  With
+ * levels = k > 1 every MSM runs folded: scalar i is cut into k chunks of S bits (all 256 bits, the
+ * wire scalar is not reduced), and the MSM of the k n (level, point) pairs runs over the lowest Wc
+ * of the width's windows only -- 1/k of the bucket reduction, k times the entries per bucket
+ * (DESIGN.md §9 gives S and Wc).  levels = 1 is the plain MSM on resident records.
+ *
+ * Creation runs the preparation once: MSM_ERR_COORD_RANGE and MSM_ERR_BAD_POINT are reported
+ * there and nowhere later.  levels: 0 = auto (1 unless a measured size says otherwise), else 1..8;
+ * levels * n must stay below 2^30 and inside the launch plan's entry limit (MSM_ERR_INVALID_ARG);
+ * MSM_ERR_OOM when the records do not fit; a failed creation leaves nothing allocated and *out
+ * null.  opts->window_bits at creation fixes the window width of a levels > 1 handle (0 = the
+ * library's choice for the folded problem).  Results of a levels > 1 handle are specified for points
+ * on the curve only (the shifted levels are multiples computed with the curve's doubling law).
+ * MSM_FLAG_DEVICES and MSM_FLAG_WINDOWS give MSM_ERR_INVALID_ARG at creation and at compute.
+ *
+ * Compute: opts may set run_length, MSM_FLAG_SERIAL and device (-1 or the handle's own); with
+ * levels > 1 window_bits must be 0 or the handle's width, with levels = 1 any width is accepted
+ * (the records do not depend on it).  The scalar vectors hold the handle's n scalars each; n = 0
+ * gives the identity and count = 0 returns at once, as in the entries above.  The `many` entries
+ * are pipelined as msm_compute_shared_device is.  Calls on one handle may run concurrently from
+ * several threads (they serialise on the device, as every entry does).
+ *
+ * Lifetime: msm_bases_destroy frees the records; msm_shutdown frees those of every live handle.
+ * A handle used after either returns MSM_ERR_INVALID_ARG (handles are registry tokens, never
+ * dereferenced). */
+typedef struct msm_bases msm_bases;
+typedef struct msm_bases_info_t {
+  uint64_t n;           /* points of the base vector                                   */
+  uint32_t levels;      /* copies held (1 = unfolded)                                  */
+  uint32_t window_bits; /* levels > 1: the window width the levels were shifted for    */
+  uint32_t chunk_bits;  /* levels > 1: S, bits per scalar chunk; else 0                */
+  uint32_t windows;     /* levels > 1: Wc, windows a folded MSM runs; else 0           */
+  int32_t device;       /* HIP ordinal the records live on                             */
+  uint32_t reserved;    /* 0 */
+  uint64_t bytes;       /* device memory of the records: levels * n * 128              */
+} msm_bases_info_t;
+int msm_bases_create(const uint32_t* points_be, size_t n, const msm_opts* opts, uint32_t levels, msm_bases** out);
+int msm_bases_create_device(const uint32_t* d_points_be, size_t n, const msm_opts* opts, uint32_t levels,
+                            void* hip_stream, msm_bases** out);
+int msm_bases_destroy(msm_bases* bases);
+int msm_bases_info(const msm_bases* bases, msm_bases_info_t* out);
+int msm_bases_compute(const msm_bases* bases, const uint32_t* scalars_be, const msm_opts* opts,
+                      uint32_t out_xy_be[16]);
+int msm_bases_compute_device(const msm_bases* bases, const uint32_t* d_scalars_be, const msm_opts* opts,
+                             void* hip_stream, uint32_t out_xy_be[16]);
+int msm_bases_compute_many(const msm_bases* bases, const uint32_t* const* scalars_be, size_t count,
+                           const msm_opts* opts, uint32_t* out_xy_be);
+int msm_bases_compute_many_device(const msm_bases* bases, const uint32_t* const* d_scalars_be, size_t count,
+                                  const msm_opts* opts, void* hip_stream, uint32_t* out_xy_be);
+
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,
  * 7M mixed adds into per-thread bucket tables.  window_bits 0 = auto, n_threads <= 0 = all

@@ -1,0 +1,142 @@
+"""Resident prepared bases (msm_amd.Bases) against the entries that take the points on every call:
+the sweep behind the auto table in msm_host.hip (BASES_AUTO) and DESIGN.md §9.
+
+    python tools/bases_probe.py [--sizes 16,18,20] [--levels 1,2,4] [--count 20] [--out FILE]
+
+Without --n the sizes run one after the other, each as a child process under its own `timeout`;
+the sweep stops at the first child that fails (nothing more is started on the GPU after a fault
+or a time limit).  With --n one size runs in this process and prints / appends JSON lines:
+
+  {"entry": "msm_compute_shared_device", ...}  pipelined ms per MSM, base vector prepared per call
+  {"entry": "msm_compute", ...}                one awaited MSM from host arrays (points + scalars)
+  {"entry": "bases", "levels", "c", ...}       handle creation (ms), pipelined ms per MSM over
+                                               `count` MSMs (compute_many_device), one awaited MSM
+                                               from device scalars and from host scalars
+
+c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
+digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
+checked against the closed form.  Times are host wall clock around calls that return with the
+result on the host; medians over --runs repeats after one warm-up call.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "webgpu-msm_amd"), os.path.join(ROOT, "tests")]
+
+
+def timed(fn, runs):
+    fn()  # warm-up: graph capture, allocations
+    ts = []
+    res = None
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        res = fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), [round(t, 4) for t in ts], res
+
+
+def one_size(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import as_xy, closed_form
+
+    n, count = a.n, a.count
+    lines = []
+
+    def emit(d):
+        d = {"n": n, **d}
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    pts = M.gen_points(n, k0=3, step=5)
+    distinct = min(count, 4)  # a few scalar vectors, cycled: the device holds 4, not `count`, of them
+    scs = [M.gen_scalars(n, seed=500 + i) for i in range(distinct)]
+    exp = [closed_form(3, 5, s) for s in scs]
+    d_pts, d_scs = dev(pts), [dev(s) for s in scs]
+    many = [d_scs[i % distinct] for i in range(count)]
+    many_exp = [exp[i % distinct] for i in range(count)]
+    torch.cuda.synchronize()
+
+    def check(rows):
+        return [as_xy(r) for r in rows] == many_exp
+
+    # the comparison entries, same run, same box
+    ms, runs, res = timed(lambda: M.compute_msm_shared_device(d_pts, many, n), a.runs)
+    emit({"entry": "msm_compute_shared_device", "count": count, "ms_per_msm": round(ms / count, 4),
+          "runs_ms": runs, "correct": check(res)})
+    ms, runs, res = timed(lambda: M.compute_msm_device(d_pts, d_scs[0], n), a.runs)
+    emit({"entry": "msm_compute_device", "ms": round(ms, 4), "runs_ms": runs, "correct": res == exp[0]})
+    ms, runs, res = timed(lambda: M.compute_msm_wire(pts, scs[0]), a.runs)
+    emit({"entry": "msm_compute", "ms": round(ms, 4), "runs_ms": runs, "correct": res == exp[0]})
+
+    c0 = M.launch_plan(n, pipelined=True)["c"]
+    widths = [c for c in range(c0, c0 + 3) if c <= 16] + ([17] if a.wide else [])
+    for levels in a.levels:
+        for c in widths:
+            t0 = time.perf_counter()
+            b = M.Bases.from_device(d_pts, n, levels=levels, window_size=c)
+            create_ms = (time.perf_counter() - t0) * 1e3
+            with b:
+                inf = b.info
+                row = {"entry": "bases", "levels": levels, "c": c, "windows": inf["windows"] or M.window_count(c),
+                       "chunk_bits": inf["chunk_bits"], "bytes": inf["bytes"], "create_ms": round(create_ms, 3)}
+                ms, runs, res = timed(lambda: b.compute_many_device(many, window_size=c), a.runs)
+                row.update(count=count, pipelined_ms_per_msm=round(ms / count, 4), pipelined_runs_ms=runs)
+                ok = check(res)
+                ms, runs, res = timed(lambda: b.compute_device(d_scs[0], window_size=c), a.runs)
+                row.update(single_device_ms=round(ms, 4), single_device_runs_ms=runs)
+                ok = ok and res == exp[0]
+                ms, runs, res = timed(lambda: b.compute(scs[0], window_size=c), a.runs)
+                row.update(single_host_ms=round(ms, 4), single_host_runs_ms=runs)
+                ok = ok and res == exp[0]
+                row["correct"] = ok
+                emit(row)
+            if levels == 1 and c == widths[0]:
+                # creation from host arrays (upload + preparation), once per size
+                t0 = time.perf_counter()
+                with M.Bases.from_wire(pts, levels=1):
+                    emit({"entry": "bases_create_host", "levels": 1, "create_ms": round((time.perf_counter() - t0) * 1e3, 3)})
+    return 0 if all(d.get("correct", True) for d in lines) else 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=0, help="run this one size in-process")
+    ap.add_argument("--sizes", default="16,18,20", help="log2 sizes of the sweep")
+    ap.add_argument("--levels", default="1,2,4")
+    ap.add_argument("--count", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--wide", action="store_true", help="also time c = 17 (32-bit digit codes)")
+    ap.add_argument("--out", default="")
+    ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
+    a = ap.parse_args()
+    a.levels = [int(x) for x in str(a.levels).split(",")]
+    if a.n:
+        return one_size(a)
+    for lg in (int(x) for x in a.sizes.split(",")):
+        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n", str(1 << lg),
+               "--levels", ",".join(map(str, a.levels)), "--count", str(a.count), "--runs", str(a.runs)]
+        cmd += (["--wide"] if a.wide else []) + (["--out", a.out] if a.out else [])
+        rc = subprocess.run(cmd).returncode
+        if rc != 0:
+            print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -155,13 +156,14 @@ struct Workspace {
   Buf lead_val, lead_open, cross_key, lead_flag, skew_list, g_head, g_hkey, g_tkey, red_U, red_T;
   Buf wire_pts, wire_sc;  // device copies of host-resident inputs (msm_compute*, host entries)
   Buf red_G;               // k_red2_groups' points per (window, group of RG_CH chunks)
+  Buf split_sc;            // k_split_scalars' virtual scalars of a folded launch (msm_bases_*, levels > 1)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
   void release() {
     Buf* bufs[] = {&pts, &err, &digits, &colsum, &bin_base, &bin_cur, &part_entry, &part_fine,
                    &sorted_entry, &bucket_start, &run_key, &buckets, &lead_val, &lead_open, &cross_key,
-                   &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G};
+                   &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G, &split_sc};
     for (Buf* b : bufs) b->release();
   }
 };
@@ -578,7 +580,8 @@ bool red2_tree(const Plan& pl) {
   return on && red2_groups(pl) <= RG_MAXG;
 }
 
-int ensure_workspace(DevCtx* c, const Plan& pl, int si) {
+// (`own_pts` false: the launch reads a handle's resident records, the slot needs no record buffer.)
+int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
   Slot& sl0 = c->slot[si];
   Workspace& w = sl0.ws;
   const MsmDims& d = pl.d;
@@ -587,7 +590,7 @@ int ensure_workspace(DevCtx* c, const Plan& pl, int si) {
   const uint64_t gen0 = g_alloc_gen.load();
 #define ENS(buf, bytes) \
   if ((rc = w.buf.ensure(bytes)) != MSM_OK) return rc
-  ENS(pts, (size_t)(d.shared ? 1 : d.nm) * d.n * PRE_WORDS * 4);
+  ENS(pts, own_pts ? (size_t)(d.shared ? 1 : d.nm) * d.n * PRE_WORDS * 4 : 0);
   ENS(err, 16);
   ENS(digits, (size_t)d.W * d.n * 4);
   ENS(colsum, ((size_t)d.nbins + d.W) * 4);  // bin totals, then window totals
@@ -2017,6 +2020,14 @@ struct ManyInputs {
                         // k_prepare_points reads that format
   const uint32_t* const* dev_scalars = nullptr;  // host inputs whose scalars are already on the
                                                  // device (n + padding words per MSM): no scalar upload
+  // Records already prepared (a msm_bases handle's, device memory): they stand where the shared
+  // base vector's records stand, and nothing is prepared.  With levels > 1 they are `levels`
+  // copies of n records (level j = 2^(j chunk_bits) P_i) and every MSM runs folded: its scalars
+  // are cut into levels * n virtual scalars of chunk_bits bits (k_split_scalars, into the slot's
+  // split_sc) and the plan is the one of levels * n points (the caller's opts carry the window
+  // width and the window range [0, Wc)).
+  const uint32_t* prepared = nullptr;
+  uint32_t levels = 1, chunk_bits = 0;
 };
 
 // `count` MSMs of n points each, pipelined over pipeline_slots slots, each with its own stream and
@@ -2042,8 +2053,11 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     for (size_t b = 0; b < count; b++) emit(pt_identity(), b);
     return MSM_OK;
   }
-  const bool shared = in.shared_points != nullptr;
+  const bool prepared = in.prepared != nullptr;
+  const bool shared = in.shared_points != nullptr || prepared;
   const bool host = in.kind == ManyInputs::HOST;
+  const uint32_t kf = prepared ? std::max(1u, in.levels) : 1u;  // levels of a folded launch
+  const size_t np = n * kf;                                      // points the plan sees per MSM
   for (size_t b = 0; b < count; b++)
     if ((!shared && !in.points[b]) || !in.scalars[b]) return MSM_ERR_INVALID_ARG;
   // the batch's BatchPtrs hold MSM_MAX_BATCH entries: never more MSMs per launch than that
@@ -2051,7 +2065,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
       in.batch ? std::min<size_t>(in.batch, count) : pipeline_batch(n, count), MSM_MAX_BATCH);
   const size_t nbatch = (count + nm - 1) / nm;
   Plan pl;
-  int rc = make_plan(n, o, c->shape, &pl, count > 1, nm, shared);
+  int rc = make_plan(np, o, c->shape, &pl, count > 1, nm, shared);
   if (rc != MSM_OK) return rc;
   // host inputs: one more launch in flight, so its upload queues behind the running ones
   // (2^20 msm_compute 4.21 -> 4.05 ms with three, profiles/r2t_*; device inputs are best with two)
@@ -2059,7 +2073,8 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
   const int nslot = nbatch > 1 ? (int)std::min<size_t>(nbatch, (size_t)std::min(want, NSLOT)) : 1;
   for (int si = 0; si < nslot; si++) {
     c->slot[si].pipelined = nslot > 1;
-    if ((rc = ensure_workspace(c, pl, si)) != MSM_OK) return rc;
+    if ((rc = ensure_workspace(c, pl, si, !prepared)) != MSM_OK) return rc;
+    if (kf > 1 && (rc = c->slot[si].ws.split_sc.ensure((size_t)nm * np * 32)) != MSM_OK) return rc;
     if (host) {
       Workspace& w = c->slot[si].ws;
       if ((!shared && (rc = w.wire_pts.ensure((size_t)nm * n * 128)) != MSM_OK) ||
@@ -2073,8 +2088,8 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     for (int k = 0; k < nslot; k++) hipStreamSynchronize(c->slot[k].stream);
     return code;
   };
-  uint32_t* pts_shared = nullptr;
-  if (shared) {
+  uint32_t* pts_shared = prepared ? const_cast<uint32_t*>(in.prepared) : nullptr;
+  if (shared && !prepared) {
     // the base vector's records, prepared once on slot 0's stream; the other slots wait for them
     if ((rc = c->shared_pts.ensure(n * PRE_WORDS * 4)) != MSM_OK) return rc;
     pts_shared = c->shared_pts.as<uint32_t>();
@@ -2326,6 +2341,14 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
         }
         if (uploader && !wait_for(up_ready, j + 1)) return fail(up_rc.load());
         if (hipStreamWaitEvent(sl.stream, c->up_ev[2 * j + 1], 0) != hipSuccess) return fail(MSM_ERR_HIP);
+      }
+      if (kf > 1) {
+        // the launch's scalars cut into its virtual scalars, on the slot's stream ahead of the sort
+        uint32_t* vs = sl.ws.split_sc.as<uint32_t>();
+        hipLaunchKernelGGL(k_split_scalars, dim3(grid_for(n, 256), kf, nm), dim3(256), 0, sl.stream, bs, vs,
+                           (uint32_t)n, kf, in.chunk_bits);
+        if (hipGetLastError() != hipSuccess) return fail(MSM_ERR_HIP);
+        for (uint32_t m = 0; m < MSM_MAX_BATCH; m++) bs.p[m] = vs + (size_t)std::min(m, nm - 1) * np * 8;
       }
       Plan plj = pl;
       plj.pfmt = packed ? launch_fmt[j] : PT_FMT_WIRE;  // set by the uploader before up_ready
@@ -2591,7 +2614,8 @@ int device_entry(const uint32_t* d_points_be, const uint32_t* d_scalars_be, size
 
 int many_entry(const ManyInputs& in, size_t n, size_t count, const msm_opts* opts, void* hip_stream, uint32_t* out,
                bool projective) {
-  if (!out || (!in.scalars && count) || (!in.points && !in.shared_points && count)) return MSM_ERR_INVALID_ARG;
+  if (!out || (!in.scalars && count) || (!in.points && !in.shared_points && !in.prepared && count))
+    return MSM_ERR_INVALID_ARG;
   if (count == 0) return MSM_OK;
   return on_device(opts, [&](DevCtx* c) {
     return run_many(c, in, n, count, opts, (hipStream_t)hip_stream, out, projective);
@@ -2813,6 +2837,212 @@ int multi_many_entry(const ManyInputs& in, size_t n, size_t count, const msm_opt
   });
 }
 
+// ---- resident prepared bases (msm_bases_*, include/msm.h) ----------------------------------------
+// The fold geometry of `levels` = k shifted levels at window width c: with the
+// library's balanced windows (make_plan), Wc is the smallest window count whose offset, less one
+// bit, times k covers the 256 scalar bits, and the chunk is S = off(Wc) - 1 bits: one bit less than
+// windows [0, Wc) hold, so the top window's value plus its carry is at most 2^(b-1) and nothing
+// carries out of the range.  k = 1 is the plain MSM: every window, no cut (S reported as 256).
+struct BasesGeo {
+  uint32_t c, Wc, S;
+};
+bool bases_geometry(uint32_t c, uint32_t k, BasesGeo* g) {
+  if (c < 4 || c > 20 || k < 1 || k > 8) return false;
+  const uint32_t wm = (MAIN_BITS + c - 1) / c, q = MAIN_BITS / wm, nhi = MAIN_BITS - q * wm;
+  g->c = c;
+  if (k == 1) {
+    g->Wc = wm + 1;
+    g->S = 256;
+    return true;
+  }
+  for (uint32_t w = 1; w <= wm; w++) {
+    const uint32_t off = w * q + std::min(w, nhi);
+    if (k * (off - 1) >= 256) {  // off(wm) = 254: always met for k >= 2
+      g->Wc = w;
+      g->S = off - 1;
+      return true;
+    }
+  }
+  return false;
+}
+
+// What levels = 0 and window_bits = 0 resolve to at creation.  Every row is a measurement of
+// tools/bases_probe.py committed as profiles/bases_sweep.jsonl; a size that file does not hold
+// gets levels = 1, and no row picks records past the 256 MiB Infinity Cache unless they won there.
+struct BasesAutoRow {
+  size_t n_lo, n_hi;  // sizes [n_lo, n_hi) the row was measured for
+  uint32_t levels, window_bits;
+};
+constexpr BasesAutoRow BASES_AUTO[] = {
+    // profiles/bases_sweep.jsonl, n = 2^16: levels 2 at c = 15 does not beat levels 1 pipelined (0.125
+    // against 0.123 ms per MSM at c = 14); levels 4 loses
+    {1u << 16, (1u << 16) + 1, 1, 0},
+    // profiles/bases_sweep.jsonl, n = 2^18: levels 2 at c = 15 wins pipelined (0.272 against 0.292 ms per
+    // MSM at levels 1, c = 15) and awaited (0.438 against 0.479 ms at levels 1, c = 16); 64 MiB of records
+    {1u << 18, (1u << 18) + 1, 2, 15},
+    // profiles/bases_sweep.jsonl, n = 2^20: levels 2 loses (1.121 against 0.921 ms per MSM), levels 4 more
+    {1u << 20, (1u << 20) + 1, 1, 0},
+};
+uint32_t bases_auto_levels(size_t n) {
+  for (const BasesAutoRow& r : BASES_AUTO)
+    if (n >= r.n_lo && n < r.n_hi) return r.levels;
+  return 1;
+}
+// The width of a folded handle created with window_bits = 0: the table's where the size was
+// measured, else the pipelined width of the folded problem's k n points, at most 16 (wider windows
+// take the 32-bit digit codes).
+uint32_t bases_auto_window(size_t n, uint32_t levels) {
+  for (const BasesAutoRow& r : BASES_AUTO)
+    if (n >= r.n_lo && n < r.n_hi && r.levels == levels && r.window_bits) return r.window_bits;
+  return std::min(16u, pipelined_window(n * levels));
+}
+
+// A handle's state.  The caller's msm_bases* is a token (the registry key, never an address), so a
+// stale or foreign handle is a failed lookup, not a dereference.  `rec` is freed, and `alive`
+// cleared, under the owning device context's lock (msm_bases_destroy, msm_shutdown); a compute
+// call holds a reference and checks `alive` under that lock before it reads the records.
+struct Bases {
+  int device = -1;
+  size_t n = 0;
+  uint32_t levels = 1;
+  uint32_t window_bits = 0;  // levels > 1: the width the levels were shifted for
+  BasesGeo geo{};            // levels > 1
+  Buf rec;                   // levels * n records, level j at [j n, (j + 1) n)
+  bool alive = false;
+};
+std::map<uintptr_t, std::shared_ptr<Bases>> g_bases;  // under g_mu
+uintptr_t g_bases_next = 1;
+
+std::shared_ptr<Bases> find_bases(const msm_bases* h) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_bases.find(reinterpret_cast<uintptr_t>(h));
+  return it == g_bases.end() ? nullptr : it->second;
+}
+
+bool bases_flags_ok(const msm_opts* o) {  // a handle lives on one device and runs whole MSMs
+  return !o || !(o->flags & (MSM_FLAG_DEVICES | MSM_FLAG_WINDOWS | MSM_FLAG_HALF_WINDOWS));
+}
+
+int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* opts, uint32_t levels,
+                 hipStream_t user_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  *out = nullptr;
+  if ((!points && n) || levels > 8 || !bases_flags_ok(opts)) return MSM_ERR_INVALID_ARG;
+  const uint32_t wb = opts ? opts->window_bits : 0;
+  if (wb && (wb < 4 || wb > 20)) return MSM_ERR_UNSUPPORTED_WINDOW;
+  if (!levels) levels = bases_auto_levels(n);
+  auto b = std::make_shared<Bases>();
+  b->n = n;
+  b->levels = levels;
+  if (levels > 1) {
+    b->window_bits = wb ? wb : bases_auto_window(n, levels);
+    if (!bases_geometry(b->window_bits, levels, &b->geo)) return MSM_ERR_INVALID_ARG;
+  }
+  if ((uint64_t)levels * n >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  msm_opts od{};
+  od.device = opts ? opts->device : -1;
+  int rc = on_device(&od, [&](DevCtx* c) -> int {
+    b->device = c->device;
+    if (!n) return MSM_OK;
+    {  // the launch plan of one MSM on these records must exist (finish_plan's Mmax limit)
+      msm_opts op{};
+      op.window_bits = levels > 1 ? b->window_bits : wb;
+      if (levels > 1) {
+        op.flags = MSM_FLAG_WINDOWS;
+        op.window_hi = b->geo.Wc;
+      }
+      Plan pl;
+      if (int prc = make_plan(n * levels, &op, c->shape, &pl, false, 1, true)) return prc;
+    }
+    Slot& s0 = c->slot[0];
+    Buf errb;  // the preparation's error word
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if ((r = b->rec.ensure((size_t)levels * n * PRE_WORDS * 4)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    auto done = [&](int code) {  // every exit past the allocations: a failure leaves nothing allocated
+      hipStreamSynchronize(c->copy_stream);
+      hipStreamSynchronize(s0.stream);
+      errb.release();
+      if (code != MSM_OK) b->rec.release();
+      return code;
+    };
+    uint32_t* rec = b->rec.as<uint32_t>();
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    const uint32_t nt = prep_nt((size_t)levels * n);
+    if (host) {
+      if ((r = s0.ws.wire_pts.ensure(n * 128)) != MSM_OK) return done(r);
+      if ((r = upload_points(c, points, n, s0.ws.wire_pts.as<uint32_t>(), rec, errp, s0.stream)) != MSM_OK)
+        return done(r);
+    } else {
+      launch_prepare(points, rec, (uint32_t)n, errp, nt, s0.stream);
+    }
+    for (uint32_t j = 1; j < levels; j++)
+      hipLaunchKernelGGL(k_shift_bases, dim3(grid_for(n, PP_THREADS)), dim3(PP_THREADS), 0, s0.stream,
+                         rec + (size_t)(j - 1) * n * PRE_WORDS, rec + (size_t)j * n * PRE_WORDS, (uint32_t)n,
+                         b->geo.S, nt);
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+  if (rc != MSM_OK) return rc;
+  b->alive = true;  // n = 0: nothing allocated
+  std::lock_guard<std::mutex> lk(g_mu);
+  // msm_shutdown may have run since the records were made (it frees only registered handles)
+  if (n && ((int)g_ctx.size() <= b->device || !g_ctx[b->device])) {
+    b->rec.release();
+    return MSM_ERR_INVALID_ARG;
+  }
+  const uintptr_t id = g_bases_next++;
+  g_bases[id] = b;
+  *out = reinterpret_cast<msm_bases*>(id);
+  return MSM_OK;
+}
+
+// `count` MSMs over a handle's records: run_many's pipelined path with the records in the place
+// of a shared base vector's (count = 1: the single entries, which then have no preparation to fork).
+int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host, size_t count, const msm_opts* opts,
+                  void* hip_stream, uint32_t* out) {
+  if (!h || !out || (!scalars && count) || !bases_flags_ok(opts)) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b) return MSM_ERR_INVALID_ARG;
+  if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
+  msm_opts o{};
+  o.run_length = opts ? opts->run_length : 0;
+  o.flags = opts ? (opts->flags & MSM_FLAG_SERIAL) : 0;
+  o.device = b->device;
+  o.window_bits = opts ? opts->window_bits : 0;
+  if (b->levels > 1) {
+    if (o.window_bits && o.window_bits != b->window_bits) return MSM_ERR_INVALID_ARG;
+    o.window_bits = b->window_bits;
+    o.flags |= MSM_FLAG_WINDOWS;
+    o.window_lo = 0;
+    o.window_hi = b->geo.Wc;
+  }
+  if (count == 0) return MSM_OK;
+  for (size_t k = 0; k < count; k++)
+    if (!scalars[k] && b->n) return MSM_ERR_INVALID_ARG;
+  return on_device(&o, [&](DevCtx* c) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    ManyInputs in;
+    in.kind = host ? ManyInputs::HOST : ManyInputs::DEVICE;
+    in.scalars = scalars;
+    in.prepared = b->rec.as<uint32_t>();
+    in.levels = b->levels;
+    in.chunk_bits = b->geo.S;
+    return run_many(c, in, b->n, count, &o, (hipStream_t)hip_stream, out, false);
+  });
+}
+
 // ---- helpers of the device test hooks (msm_test_field_op .. msm_test_records) -------------------
 // A device buffer of one hook call: freed when the call returns, on its HIPCHECK exits too.
 struct TestBuf {
@@ -2865,6 +3095,11 @@ void msm_shutdown(void) {
     c->shared_pts.release();
     c->host_sc.release();
     c->host_pts.release();
+    for (auto& kv : g_bases)  // every live handle's records; its next use fails the registry lookup
+      if (kv.second->device == c->device) {
+        kv.second->alive = false;
+        kv.second->rec.release();
+      }
     for (Slot& sl : c->slot) {
       sl.ws.release();
       for (Segment& sg : sl.seg) sg.drop();
@@ -2904,6 +3139,7 @@ void msm_shutdown(void) {
     delete c;
     c = nullptr;
   }
+  g_bases.clear();  // every handle was freed with its device context above
   std::lock_guard<std::mutex> lk3(g_test_mu);
   g_test_pools.stop();
 }
@@ -3072,6 +3308,68 @@ int msm_compute_shared(const uint32_t* points_be, const uint32_t* const* scalars
   in.scalars = scalars_be;
   if (!n) in.points = scalars_be;
   return multi_many_entry(in, n, count, opts, nullptr, out_xy_be, false);
+}
+
+int msm_bases_create(const uint32_t* points_be, size_t n, const msm_opts* opts, uint32_t levels, msm_bases** out) {
+  return create_bases(points_be, true, n, opts, levels, nullptr, out);
+}
+
+int msm_bases_create_device(const uint32_t* d_points_be, size_t n, const msm_opts* opts, uint32_t levels,
+                            void* hip_stream, msm_bases** out) {
+  return create_bases(d_points_be, false, n, opts, levels, (hipStream_t)hip_stream, out);
+}
+
+int msm_bases_destroy(msm_bases* h) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_bases.find(reinterpret_cast<uintptr_t>(h));
+  if (!h || it == g_bases.end()) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = it->second;
+  g_bases.erase(it);
+  // under the device context's lock: a compute call on this handle has returned, or will find it dead
+  DevCtx* c = b->device >= 0 && b->device < (int)g_ctx.size() ? g_ctx[b->device] : nullptr;
+  if (c) {
+    std::lock_guard<std::mutex> lk2(c->mu);
+    DeviceGuard g(c->device);
+    b->alive = false;
+    b->rec.release();
+  } else {
+    b->alive = false;
+  }
+  return MSM_OK;
+}
+
+int msm_bases_info(const msm_bases* h, msm_bases_info_t* out) {
+  if (!h || !out) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b) return MSM_ERR_INVALID_ARG;
+  *out = msm_bases_info_t{};
+  out->n = b->n;
+  out->levels = b->levels;
+  out->window_bits = b->window_bits;
+  out->chunk_bits = b->levels > 1 ? b->geo.S : 0;
+  out->windows = b->levels > 1 ? b->geo.Wc : 0;
+  out->device = b->device;
+  out->bytes = (uint64_t)b->levels * b->n * PRE_WORDS * 4;
+  return MSM_OK;
+}
+
+int msm_bases_compute(const msm_bases* h, const uint32_t* scalars_be, const msm_opts* opts, uint32_t out_xy_be[16]) {
+  return bases_compute(h, &scalars_be, true, 1, opts, nullptr, out_xy_be);
+}
+
+int msm_bases_compute_device(const msm_bases* h, const uint32_t* d_scalars_be, const msm_opts* opts,
+                             void* hip_stream, uint32_t out_xy_be[16]) {
+  return bases_compute(h, &d_scalars_be, false, 1, opts, hip_stream, out_xy_be);
+}
+
+int msm_bases_compute_many(const msm_bases* h, const uint32_t* const* scalars_be, size_t count, const msm_opts* opts,
+                           uint32_t* out_xy_be) {
+  return bases_compute(h, scalars_be, true, count, opts, nullptr, out_xy_be);
+}
+
+int msm_bases_compute_many_device(const msm_bases* h, const uint32_t* const* d_scalars_be, size_t count,
+                                  const msm_opts* opts, void* hip_stream, uint32_t* out_xy_be) {
+  return bases_compute(h, d_scalars_be, false, count, opts, hip_stream, out_xy_be);
 }
 
 int msm_combine_partials(const uint32_t* partials_xyzt_be, size_t count, uint32_t out_xy_be[16]) {
@@ -3526,6 +3824,57 @@ int msm_test_records(uint32_t fmt, const uint32_t* in, size_t n, uint32_t* recor
                      (uint32_t)m);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpy(out, dout.p, m * PT_WORDS * 4, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// The fold geometry a handle of `levels` levels gets at width window_bits (0: the auto width for n
+// points): out = {window_bits c, windows per folded MSM Wc, chunk bits S, points of the folded
+// problem levels * n}.  Host code only (no device needed).
+int msm_test_bases_plan(size_t n, uint32_t levels, uint32_t window_bits, uint32_t out[4]) {
+  if (!out || levels < 1 || levels > 8) return MSM_ERR_INVALID_ARG;
+  const uint32_t c = window_bits ? window_bits : levels > 1 ? bases_auto_window(n, levels) : msm_best_window(n);
+  BasesGeo g;
+  if (!bases_geometry(c, levels, &g)) return MSM_ERR_UNSUPPORTED_WINDOW;
+  out[0] = g.c;
+  out[1] = g.Wc;
+  out[2] = g.S;
+  out[3] = (uint32_t)(n * levels);
+  return MSM_OK;
+}
+
+// The records of one level of a handle, copied to the host (n * 32 words).
+int msm_test_bases_records(const msm_bases* h, uint32_t level, uint32_t* records) {
+  if (!h || !records) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b || level >= b->levels) return MSM_ERR_INVALID_ARG;
+  msm_opts o{};
+  o.device = b->device;
+  return on_device(&o, [&](DevCtx*) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;
+    if (!b->n) return MSM_OK;
+    HIPCHECK(hipMemcpy(records, b->rec.as<uint32_t>() + (size_t)level * b->n * PRE_WORDS, b->n * PRE_WORDS * 4,
+                       hipMemcpyDeviceToHost));
+    return MSM_OK;
+  });
+}
+
+// k_split_scalars on n wire scalars: out = the k * n virtual scalars of S bits (8 words each,
+// element j n + i).
+int msm_test_split_scalars(const uint32_t* scalars, size_t n, uint32_t k, uint32_t S, uint32_t* out) {
+  if (!scalars || !out || n == 0 || n > (1u << 24) || k < 2 || k > 8 || S < 1 || S > 255)
+    return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf din, dout;
+  HIPCHECK(din.alloc(n * 32));
+  HIPCHECK(dout.alloc((size_t)k * n * 32));
+  HIPCHECK(hipMemcpy(din.p, scalars, n * 32, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_split_scalars, dim3(grid_for(n, 256), k, 1), dim3(256), 0, 0, splat(din.p), dout.p, (uint32_t)n, k,
+                     S);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, (size_t)k * n * 32, hipMemcpyDeviceToHost));
   return MSM_OK;
 }
 

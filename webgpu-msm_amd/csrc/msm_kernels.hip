@@ -235,6 +235,134 @@ extern "C" __global__ void __launch_bounds__(256) k_pad_identity(uint32_t* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// resident prepared bases (msm_bases_*): shifted levels and the scalar cut
+// ---------------------------------------------------------------------------------------------
+// Level j + 1 of a handle's records from level j: record i of `src` (the halved affine form of
+// Q_i = 2^(jS) P_i) -> record i of `dst` for 2^S Q_i.  One workgroup = PP_THREADS records, moved
+// between HBM and LDS exactly as k_prepare_points moves them (coalesced 16-B accesses, slots
+// XOR-swizzled by the record index); each lane rebuilds its extended point, doubles it S times
+// (pt_dbl, complete: the identity, the order-2 point (0, -1) and the order-4 points with y = 0
+// need no branch), and normalises with one fe_inv (~260 of the lane's 8 S + ~270 multiplies).
+// Results are specified for on-curve points (Z of a multiple is then never 0).
+// Limb forms written -- the ones k_prepare_points writes, which tests/test_limb_bounds.py
+// test_madd_bounds proves for pt_madd's record operand: x and y below are fe_mul outputs (N_MUL),
+// so (y-x)/2 = fe_sub(N_MUL, N_MUL) (normalised, < 10p), (y+x)/2 = fe_norm(fe_add(N_MUL, N_MUL))
+// (normalised, < 4p) and d t = fe_mul_d of an fe_mul output (normalised, < 2p: N_MUL).
+extern "C" __global__ void __launch_bounds__(PP_THREADS) k_shift_bases(const uint32_t* __restrict__ src,
+                                                                       uint32_t* __restrict__ dst, uint32_t n,
+                                                                       uint32_t S, uint32_t nt) {
+  __shared__ uint4 st[PP_THREADS * 8];
+  const uint32_t p0 = blockIdx.x * PP_THREADS;
+  const uint32_t np = min(PP_THREADS, n - p0);
+  const uint4* in = reinterpret_cast<const uint4*>(src) + (size_t)p0 * 8;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * PP_THREADS + threadIdx.x;
+    if (g < np * 8) st[pp_slot(g >> 3, g & 7)] = in[g];
+  }
+  __syncthreads();
+  const uint32_t i = threadIdx.x;
+  uint32_t rec[32];
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) {
+    // lanes past the block's last record work on zeros (x = y = 0: every doubling and the
+    // inversion stay 0) and nothing of theirs is written back
+    const uint4 v = i < np ? st[pp_slot(i, q)] : make_uint4(0u, 0u, 0u, 0u);
+    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+  }
+  __syncthreads();
+  fe ymx, ypx;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    ymx.v[k] = rec[k];
+    ypx.v[k] = rec[PRE_HALF + k];
+  }
+  // The extended point (X : Y : T : Z) = (x : y : x y : 1), every coordinate an fe_mul output as
+  // pt_dbl's bound proof takes them.  (y-x)/2 may reach 10p with a top limb above K8P's, so it
+  // goes through one multiply by R (value kept, < 2p) before it is subtracted.
+  const fe one = fe_one();
+  const fe a = fe_mul(ymx, one);        // (y-x)/2, N_MUL
+  const fe xs = fe_sub(ypx, a);         // x + 8p: normalised, < 12p
+  const fe ys = fe_add_n(ypx, a);       // y: normalised, < 6p
+  xyzt p;
+  p.X = fe_mul(xs, one);
+  p.Y = fe_mul(ys, one);
+  p.T = fe_mul(xs, ys);                 // 72 p^2 < p R
+  p.Z = one;
+#pragma unroll 1
+  for (uint32_t s = 0; s < S; s++) p = pt_dbl(p);
+  // halved affine record, as k_prepare_points' projective branch writes it
+  const fe zh = fe_mul(fe_inv(p.Z), fe_const(HALF29));
+  const fe x = fe_mul(p.X, zh);
+  const fe y = fe_mul(p.Y, zh);
+  const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
+  const fe o_ymx = fe_sub(y, x);
+  const fe o_ypx = fe_add_n(y, x);
+#pragma unroll
+  for (int k = 0; k < 32; k++) rec[k] = 0;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    rec[k] = o_ymx.v[k];
+    rec[PRE_HALF + k] = o_ypx.v[k];
+  }
+#pragma unroll
+  for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
+  // the duplicated top limbs (msm_dev.h PRE_WORDS)
+  rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
+  rec[NL + 1] = o_ypx.v[NL - 1];
+  rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1];
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++)
+    st[pp_slot(i, q)] = make_uint4(rec[4 * q], rec[4 * q + 1], rec[4 * q + 2], rec[4 * q + 3]);
+  __syncthreads();
+  uint4* out = reinterpret_cast<uint4*>(dst) + (size_t)p0 * 8;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * PP_THREADS + threadIdx.x;
+    if (g < np * 8) {
+      const uint4 v = st[pp_slot(g >> 3, g & 7)];
+      if (nt) {
+        const pp_v4 w = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(w, reinterpret_cast<pp_v4*>(out + g));
+      } else {
+        out[g] = v;
+      }
+    }
+  }
+}
+
+// The virtual scalars of a folded launch (levels = k > 1): out[m][j n + i] = bits [j S, (j+1) S)
+// of scalar i of MSM m, wire layout (32 B, big-endian words, upper bits zero).  blockIdx.y = level
+// j, blockIdx.z = MSM of the batch (its wire scalars from scalar_sets.p[z], its k n virtual
+// scalars at out + z k n 8 words).  Two 16-B loads and two 16-B stores per lane; the shift
+// amounts are wave-uniform, so the scalar moves down by whole words in a uniform loop and by the
+// rest with v_alignbit (no dynamically indexed register array).
+extern "C" __global__ void __launch_bounds__(256) k_split_scalars(BatchPtrs scalar_sets, uint32_t* __restrict__ out,
+                                                                    uint32_t n, uint32_t k, uint32_t S) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = blockIdx.y;
+  uint32_t s[8];
+  load_be_words(scalar_sets.p[blockIdx.z] + (size_t)i * 8, s);
+  const uint32_t lo = j * S;  // may pass 256 (k = 8 at wide windows): such a level's chunks are zero
+  for (uint32_t w = 0; w < (lo >> 5); w++) {
+#pragma unroll
+    for (int q = 0; q < 7; q++) s[q] = s[q + 1];
+    s[7] = 0;
+  }
+  const uint32_t sh = lo & 31u;  // v_alignbit by 0 returns the low word
+#pragma unroll
+  for (int q = 0; q < 7; q++) s[q] = __builtin_amdgcn_alignbit(s[q + 1], s[q], sh);
+  s[7] >>= sh;
+  const uint32_t sw = S >> 5, sb = S & 31u;
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) s[q] = q < sw ? s[q] : q == sw ? s[q] & ((1u << sb) - 1u) : 0u;
+  uint4* dst = reinterpret_cast<uint4*>(out + ((size_t)blockIdx.z * k * n + (size_t)j * n + i) * 8);
+  dst[0] = make_uint4(s[7], s[6], s[5], s[4]);
+  dst[1] = make_uint4(s[3], s[2], s[1], s[0]);
+}
+
 // Gathers the record of sorted entry `ent` (point index << 1 | sign) as the point it adds:
 // a negated point's (y-x)/2 and (y+x)/2 swap by reading the record's halves in the other order
 // (msm_dev.h PRE_WORDS), and its d*t is negated (kt_neg_if).

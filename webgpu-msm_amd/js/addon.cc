@@ -24,6 +24,12 @@
 //   bestWindowSize(n) -> number                                                     (submission.ts:18-23)
 //   init() -> number (0 ok), deviceCount() -> number, deviceOrdinals() -> number[],
 //   strerror(code) -> string
+// Resident prepared bases (msm_bases_*; these three are not enumerable, the list above is the
+// addon's enumerable surface):
+//   prepareBases(points: Uint32Array(32n), levels?, windowSize?) -> { id, n, levels, windowSize, bytes }
+//   computeMsmPrepared(id, scalars: Uint32Array(8n)) -> Promise<Uint32Array(16)>
+//   releaseBases(id) -> number (0 ok, -1 for a handle already released)
+//   Handles left open are freed by the cleanup hook's msm_shutdown.
 #include <node_api.h>
 
 #include <algorithm>
@@ -109,6 +115,7 @@ struct Job {
   uint32_t window = 0;
   std::vector<int32_t> devices;  // empty: the current device
   double cpu_work_ratio = 0;     // > 0: CPU/GPU co-compute (msm_compute_cocompute)
+  const msm_bases* bases = nullptr;  // computeMsmPrepared: the handle whose records the MSM reads
   uint32_t out[16] = {0};
   int rc = 0;
 };
@@ -126,6 +133,10 @@ void execute(napi_env, void* data) {
   }
   const uint32_t* pts = j->p_points ? j->p_points : j->stage ? j->stage->points.data() : j->points.data();
   const uint32_t* sc = j->p_scalars ? j->p_scalars : j->stage ? j->stage->scalars.data() : j->scalars.data();
+  if (j->bases) {
+    j->rc = msm_bases_compute(j->bases, sc, nullptr, j->out);
+    return;
+  }
   j->rc = j->cpu_work_ratio != 0 ? msm_compute_cocompute(pts, sc, j->n, &o, j->cpu_work_ratio, 0, j->out)
                                   : msm_compute(pts, sc, j->n, &o, j->out);
 }
@@ -470,6 +481,96 @@ napi_value FlattenU32(napi_env env, napi_callback_info info) {
   return r;
 }
 
+// ---- resident prepared bases ---------------------------------------------------------------------
+const msm_bases* get_handle(napi_env env, napi_value v) {
+  double id = 0;
+  if (napi_get_value_double(env, v, &id) != napi_ok || !(id >= 1) || id > 9007199254740992.0) return nullptr;
+  return reinterpret_cast<const msm_bases*>((uintptr_t)id);
+}
+
+napi_value PrepareBases(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint32_t* pts;
+  size_t plen;
+  if (argc < 1 || !get_u32_array(env, argv[0], &pts, &plen)) {
+    napi_throw_type_error(env, nullptr, "prepareBases(points: Uint32Array, levels?, windowSize?)");
+    return nullptr;
+  }
+  msm_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = -1;
+  o.window_bits = argc > 2 ? get_window(env, argv[2]) : 0;
+  const uint32_t levels = argc > 1 ? get_window(env, argv[1]) : 0;
+  msm_bases* h = nullptr;
+  // synchronous: the points are read before this returns (upload and preparation, ~3 ms at 2^20)
+  int rc = msm_bases_create(pts, plen / 32, &o, levels, &h);
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  msm_bases_info_t inf;
+  rc = msm_bases_info(h, &inf);
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  napi_value obj, v;
+  NAPI_OK(napi_create_object(env, &obj));
+  const struct {
+    const char* name;
+    double val;
+  } fields[] = {{"id", (double)reinterpret_cast<uintptr_t>(h)}, {"n", (double)inf.n},
+                {"levels", (double)inf.levels}, {"windowSize", (double)inf.window_bits},
+                {"bytes", (double)inf.bytes}};
+  for (const auto& f : fields) {
+    NAPI_OK(napi_create_double(env, f.val, &v));
+    NAPI_OK(napi_set_named_property(env, obj, f.name, v));
+  }
+  return obj;
+}
+
+napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint32_t* sc;
+  size_t slen;
+  bool sshared = false;
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  if (argc < 2 || !h || !get_u32_array(env, argv[1], &sc, &slen, &sshared)) {
+    napi_throw_type_error(env, nullptr, "computeMsmPrepared(id: number, scalars: Uint32Array)");
+    return nullptr;
+  }
+  msm_bases_info_t inf;
+  int rc = msm_bases_info(h, &inf);
+  if (rc != MSM_OK) return throw_rc(env, rc);  // released, or never a handle
+  if (slen / 8 < inf.n) {
+    napi_throw_range_error(env, nullptr, "fewer scalars than the handle has points");
+    return nullptr;
+  }
+  Job* j = new Job();
+  j->bases = h;
+  j->n = (size_t)inf.n;
+  if (sshared) {
+    j->p_scalars = sc;
+    if (napi_create_reference(env, argv[1], 1, &j->ref_scalars) != napi_ok) {
+      delete j;
+      napi_throw_error(env, nullptr, "cannot reference the input array");
+      return nullptr;
+    }
+  } else {  // detachable memory: the worker reads a copy
+    j->scalars.resize(j->n * 8);
+    copy_words(j->scalars.data(), sc, j->n * 8);
+  }
+  return start_job(env, j);
+}
+
+napi_value ReleaseBases(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  napi_value r;
+  NAPI_OK(napi_create_int32(env, h ? msm_bases_destroy(const_cast<msm_bases*>(h)) : MSM_ERR_INVALID_ARG, &r));
+  return r;
+}
+
 napi_value BestWindowSize(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1];
@@ -539,6 +640,9 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceOrdinals", nullptr, DeviceOrdinals, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"strerror", nullptr, StrError, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"prepareBases", nullptr, PrepareBases, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"computeMsmPrepared", nullptr, ComputeMsmPrepared, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"releaseBases", nullptr, ReleaseBases, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -13,6 +13,19 @@ export declare const compute_msm: (
 ) => Promise<{ x: bigint; y: bigint }>;
 export declare function flattenU32(points: U32ArrayPoint[], scalars: Uint32Array[]): [Uint32Array, Uint32Array];
 
+// Resident prepared bases: the base vector prepared once and kept on the GPU, then scalars only.
+// levels > 1 keeps shifted copies too (folded MSMs); absent or 0 = the library's choice.
+export type BasesHandle = { id: number; n: number; levels: number; windowSize: number; bytes: number };
+export declare function prepare_bases(
+  baseAffinePoints: BigIntPoint[] | U32ArrayPoint[] | Uint32Array,
+  options?: { levels?: number; windowSize?: number }
+): BasesHandle;
+export declare const compute_msm_prepared: (
+  handle: BasesHandle,
+  scalars: bigint[] | Uint32Array[] | Uint32Array
+) => Promise<{ x: bigint; y: bigint }>;
+export declare function release_bases(handle: BasesHandle): number;
+
 export declare function getBestWindowSize(n: number): number;
 export declare function u32ArrayToBigInts(u32Array: Uint32Array): bigint[];
 export declare const split_dynamic: (windowSize: number, scalars: Uint32Array) => Uint32Array;

@@ -151,6 +151,65 @@ export const compute_msm = async (baseAffinePoints, scalars, options) => {
   return { x, y };
 };
 
+// ---- resident prepared bases (msm_bases_*, include/msm.h) -----------------------------------------
+// A prover's base vector is prepared once and kept on the GPU; every MSM then brings scalars only:
+//
+//   const bases = prepare_bases(baseAffinePoints, { levels });   // -> handle
+//   const { x, y } = await compute_msm_prepared(bases, scalars); // any number of times
+//   release_bases(bases);
+//
+// The inputs take the forms compute_msm takes (BigIntPoint[] / U32ArrayPoint[] / a flat Uint32Array of
+// n x 32 words; bigint[] / Uint32Array[] / a flat Uint32Array of n x 8 words).  levels > 1 also keeps
+// shifted copies of the base (folded MSMs, 0 or absent = the library's choice); a coordinate >= p
+// or a z = 0 point throws here, never from compute_msm_prepared.  A handle that is never released
+// is freed when the addon's environment is torn down.
+function wordsOf(v, out, at) {
+  let b = BigInt(v);
+  if (b < 0n || b >> 256n) throw new RangeError("value must be a bigint in [0, 2^256)");
+  for (let i = 7; i >= 0; i--) {
+    out[at + i] = Number(b & 0xffffffffn);
+    b >>= 32n;
+  }
+}
+
+function pointWords(points) {
+  if (points instanceof Uint32Array) return points.subarray(0, Math.floor(points.length / nUint32PerPoint) * nUint32PerPoint);
+  const pb = new Uint32Array(points.length * nUint32PerPoint);
+  points.forEach((p, i) =>
+    ["x", "y", "t", "z"].forEach((k, j) => {
+      if (typeof p[k] === "bigint") wordsOf(p[k], pb, 32 * i + 8 * j);
+      else pb.set(p[k].subarray(0, 8), 32 * i + 8 * j);
+    }));
+  return pb;
+}
+
+function scalarWords(scalars) {
+  if (scalars instanceof Uint32Array) return scalars;
+  const sb = new Uint32Array(scalars.length * nUint32PerScalar);
+  scalars.forEach((s, i) => {
+    if (typeof s === "bigint") wordsOf(s, sb, 8 * i);
+    else sb.set(s.subarray(0, 8), 8 * i);
+  });
+  return sb;
+}
+
+export function prepare_bases(baseAffinePoints, options) {
+  const levels = options && options.levels ? options.levels | 0 : 0;
+  return addon.prepareBases(pointWords(baseAffinePoints), levels, windowFrom(options));
+}
+
+export const compute_msm_prepared = async (handle, scalars) => {
+  if (!handle || typeof handle.id !== "number") throw new TypeError("compute_msm_prepared(handle, scalars): not a handle");
+  const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars));
+  const [x, y] = u32ArrayToBigInts(result);
+  return { x, y };
+};
+
+export function release_bases(handle) {
+  if (!handle || typeof handle.id !== "number") throw new TypeError("release_bases(handle): not a handle");
+  return addon.releaseBases(handle.id);
+}
+
 function toBigIntPoint(p) {
   return {
     x: u32ArrayToBigInts(p.x)[0],

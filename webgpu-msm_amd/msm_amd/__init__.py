@@ -26,7 +26,7 @@ __all__ = [
     "combine_partials", "combine_partials_many", "point_add_affine",
     "split_dynamic", "get_best_window_size", "set_profiling", "last_profile", "device_count", "device_ordinals",
     "MSM_FLAG_DEVICES", "MSM_FLAG_WINDOWS", "MSM_FLAG_HALF_WINDOWS", "MSM_MAX_DEVICES", "window_count",
-    "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P",
+    "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P", "Bases", "BasesInfo",
 ]
 
 P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
@@ -60,6 +60,13 @@ class MsmProfile(ctypes.Structure):
         ("run_length", ctypes.c_uint32), ("chunk_len", ctypes.c_uint32),
         ("accumulate_sum", ctypes.c_double), ("device_total_sum", ctypes.c_double), ("profiled", ctypes.c_uint32),
         ("msms_per_launch", ctypes.c_uint32), ("accumulate_union_sum", ctypes.c_double)]
+
+class BasesInfo(ctypes.Structure):
+    """include/msm.h msm_bases_info_t."""
+    _fields_ = [("n", ctypes.c_uint64), ("levels", ctypes.c_uint32), ("window_bits", ctypes.c_uint32),
+                ("chunk_bits", ctypes.c_uint32), ("windows", ctypes.c_uint32), ("device", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
+
 
 MSM_FLAG_SERIAL = 1  # pipelined entries: one launch in flight at a time
 MSM_FLAG_DEVICES = 2  # msm_opts carries a device list (include/msm.h)
@@ -128,6 +135,17 @@ def load() -> ctypes.CDLL:
         "msm_gen_points": ([u32p, ctypes.c_uint64, ctypes.c_uint64, sz, u32p], ctypes.c_int),
         "msm_gen_scalars": ([ctypes.c_uint64, sz, u32p], ctypes.c_int),
         "msm_last_profile": ([ctypes.POINTER(MsmProfile)], ctypes.c_int),
+        "msm_bases_create": ([vp, sz, optp, ctypes.c_uint32, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_bases_create_device": ([vp, sz, optp, ctypes.c_uint32, vp, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_bases_destroy": ([vp], ctypes.c_int),
+        "msm_bases_info": ([vp, ctypes.POINTER(BasesInfo)], ctypes.c_int),
+        "msm_bases_compute": ([vp, vp, optp, u32p], ctypes.c_int),
+        "msm_bases_compute_device": ([vp, vp, optp, vp, u32p], ctypes.c_int),
+        "msm_bases_compute_many": ([vp, vp, sz, optp, u32p], ctypes.c_int),
+        "msm_bases_compute_many_device": ([vp, vp, sz, optp, vp, u32p], ctypes.c_int),
+        "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
         "msm_test_point_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
         "msm_test_wide_masks": ([u32p], ctypes.c_int),
@@ -147,8 +165,8 @@ def load() -> ctypes.CDLL:
         "msm_test_pools": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
-        if name.startswith("msm_test_") and not hasattr(L, name):
-            continue  # a test hook an older library variant (MSM_AMD_LIB A/B builds) predates
+        if name.startswith(("msm_test_", "msm_bases_")) and not hasattr(L, name):
+            continue  # a test hook or the handle API an older library variant (MSM_AMD_LIB A/B builds) predates
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res
@@ -458,6 +476,106 @@ def _host_list(arrs, words: int):
     return keep, ptrs
 
 
+class Bases:
+    """A base vector prepared once and kept on one device (include/msm.h msm_bases_*): every
+    compute call then brings scalars only.  `levels` > 1 also keeps the shifted copies
+    2^(j S) P_i, and every MSM runs folded over 1/levels of the windows (0 = the library's choice).
+
+        with Bases.from_wire(points) as bases:
+            x, y = bases.compute(scalars)
+
+    A coordinate >= p or a z = 0 point fails the constructor (MsmError -3 / -4), never a compute
+    call.  Use after close() -- or after the library shut down -- raises MsmError(-1)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @classmethod
+    def from_wire(cls, points, levels: int = 0, window_size: Optional[int] = None, device: int = -1) -> "Bases":
+        """Host points (wire [n, 32] words, or anything points_to_wire takes)."""
+        pts = np.ascontiguousarray(points_to_wire(points))
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_create(_ptr(pts), pts.shape[0], _opts(window_size, None, device), int(levels),
+                                       ctypes.byref(h)), "msm_bases_create")
+        return cls(h.value or 0)
+
+    @classmethod
+    def from_device(cls, d_points, n: int, levels: int = 0, window_size: Optional[int] = None, device: int = -1,
+                    stream: int = 0) -> "Bases":
+        """Points already in HBM (a torch tensor or a raw device pointer, wire layout)."""
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_create_device(_dev_ptr(d_points), n, _opts(window_size, None, device), int(levels),
+                                              _stream(stream, d_points), ctypes.byref(h)), "msm_bases_create_device")
+        return cls(h.value or 0)
+
+    @property
+    def info(self) -> dict:
+        inf = BasesInfo()
+        _check(load().msm_bases_info(self._h or None, ctypes.byref(inf)), "msm_bases_info")
+        return {name: int(getattr(inf, name)) for name, _ in BasesInfo._fields_ if name != "reserved"}
+
+    def compute(self, scalars, window_size: Optional[int] = None, run_length: Optional[int] = None) -> Tuple[int, int]:
+        """One MSM of host scalars ([n, 8] wire words, or anything scalars_to_wire takes)."""
+        n = self.info["n"]
+        sc = np.ascontiguousarray(scalars_to_wire(scalars))
+        if sc.shape[0] < n:
+            raise ValueError("fewer scalars than the handle has points")
+        o, op = _out(16)
+        _check(load().msm_bases_compute(self._h, _ptr(sc), _opts(window_size, run_length), op), "msm_bases_compute")
+        return _xy(o)
+
+    def compute_device(self, d_scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
+                       stream: int = 0) -> Tuple[int, int]:
+        """One MSM of device-resident scalars (a torch tensor or a raw device pointer, n x 8 words)."""
+        o, op = _out(16)
+        _check(load().msm_bases_compute_device(self._h or None, _dev_ptr(d_scalars), _opts(window_size, run_length),
+                                               _stream(stream, d_scalars), op), "msm_bases_compute_device")
+        return _xy(o)
+
+    def compute_many(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
+                     flags: int = 0) -> np.ndarray:
+        """len(scalars_list) pipelined MSMs of host scalar vectors.  [count][16] BE words."""
+        n = self.info["n"]
+        ks, ss = _host_list(scalars_list, 8)
+        if any(b.shape[0] < n for b in ks):
+            raise ValueError("fewer scalars than the handle has points")
+        count = len(ks)
+        o, op = _out(16 * max(count, 1))
+        _check(load().msm_bases_compute_many(self._h, ctypes.cast(ss, ctypes.c_void_p), count,
+                                             _opts(window_size, run_length, -1, flags), op), "msm_bases_compute_many")
+        return o[:16 * count].reshape(count, 16)
+
+    def compute_many_device(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
+                            flags: int = 0, stream: int = 0) -> np.ndarray:
+        """The same with device-resident scalar vectors."""
+        count = len(scalars_list)
+        ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
+        o, op = _out(16 * max(count, 1))
+        _check(load().msm_bases_compute_many_device(self._h or None, ctypes.cast(ss, ctypes.c_void_p), count,
+                                                    _opts(window_size, run_length, -1, flags),
+                                                    _stream(stream, _first(scalars_list)), op),
+               "msm_bases_compute_many_device")
+        return o[:16 * count].reshape(count, 16)
+
+    def close(self) -> None:
+        """Free the records.  Closing twice is harmless."""
+        h, self._h = self._h, 0
+        if h and _lib is not None:
+            _lib.msm_bases_destroy(h)  # -1 when msm_shutdown already freed it
+
+    def __enter__(self) -> "Bases":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter teardown: the module's globals may be gone
+            pass
+
+
 def compute_msm_many(points_list, scalars_list, n: int, window_size: Optional[int] = None,
                      run_length: Optional[int] = None, device: int = -1, flags: int = 0,
                      devices: Optional[Sequence[int]] = None) -> np.ndarray:
@@ -680,6 +798,30 @@ def _test_records(fmt: int, points, entries=(), acc=None) -> Tuple[np.ndarray, i
     o, op_ = _out(max(m, 1) * 36)
     _check(load().msm_test_records(fmt, _ptr(pts), n, rec_, err_, _ptr(ents), _ptr(accs), op_, m), "msm_test_records")
     return rec.reshape(n, 32), int(err[0]), o.reshape(-1, 36)[:m]
+
+
+def _test_bases_plan(n: int, levels: int, window_size: int = 0) -> dict:
+    """The fold geometry of a `levels`-level handle (msm_test_bases_plan): window width c, windows
+    per folded MSM, chunk bits S, points of the folded problem.  No GPU needed."""
+    o, op_ = _out(4)
+    _check(load().msm_test_bases_plan(n, levels, window_size, op_), "msm_test_bases_plan")
+    return dict(zip(("c", "windows", "chunk_bits", "points"), (int(v) for v in o)))
+
+
+def _test_bases_records(bases: "Bases", level: int) -> np.ndarray:
+    """The records of one level of a handle, [n, 32] words (test hook)."""
+    n = bases.info["n"]
+    o, op_ = _out(max(n, 1) * 32)
+    _check(load().msm_test_bases_records(bases._h or None, level, op_), "msm_test_bases_records")
+    return o[: n * 32].reshape(n, 32)
+
+
+def _test_split_scalars(scalars, levels: int, chunk_bits: int) -> np.ndarray:
+    """k_split_scalars on wire scalars [n, 8] -> [levels * n, 8] virtual scalars (test hook)."""
+    sc = np.ascontiguousarray(_u32(scalars).reshape(-1, 8))
+    o, op_ = _out(levels * sc.shape[0] * 8)
+    _check(load().msm_test_split_scalars(_ptr(sc), sc.shape[0], levels, chunk_bits, op_), "msm_test_split_scalars")
+    return o.reshape(-1, 8)
 
 
 def _test_sharded(mode: int, points, scalars, n: int, devices: Sequence[int], window_size: Optional[int] = None,
