@@ -240,7 +240,8 @@ int msm_compute_shared(const uint32_t* points_be, const uint32_t* const* scalars
  *
  * Compute: opts may set run_length, MSM_FLAG_SERIAL and device (-1 or the handle's own); with
  * levels > 1 window_bits must be 0 or the handle's width, with levels = 1 any width is accepted
- * (the records do not depend on it).  The scalar vectors hold the handle's n scalars each; n = 0
+ * (the records do not depend on it).  The scalar vectors hold the handle's n scalars each (the
+ * msm_bases_compute_subset* entries below take shorter and indexed ones); n = 0
  * gives the identity and count = 0 returns at once, as in the entries above.  The `many` entries
  * are pipelined as msm_compute_shared_device is.  Calls on one handle may run concurrently from
  * several threads (they serialise on the device, as every entry does).
@@ -272,6 +273,47 @@ int msm_bases_compute_many(const msm_bases* bases, const uint32_t* const* scalar
                            const msm_opts* opts, uint32_t* out_xy_be);
 int msm_bases_compute_many_device(const msm_bases* bases, const uint32_t* const* d_scalars_be, size_t count,
                                   const msm_opts* opts, void* hip_stream, uint32_t* out_xy_be);
+
+/* MSMs over a SUBSET of a handle's bases: one handle sized for a prover's largest polynomial serves
+ * its shorter ones (a prefix, a slice) and its sparse ones (an index list) without zero-padded
+ * scalar vectors.  Everything is sized by m -- the upload, the recode, the sort, the workspace and
+ * the launch plan; only the record gather reaches into the handle's n records.
+ *
+ *   range form   (indices == NULL): result b = sum_i scalars[b][i] * P_(first + i),  i < m
+ *   indexed form (indices != NULL): result b = sum_i scalars[b][i] * P_(indices[b][i])
+ *
+ * Each scalar vector holds m scalars (the full 256-bit wire integers, as everywhere).  The single
+ * entries use indices[0]; in the `many` entries every MSM shares m (and `first`), and in indexed
+ * form MSM b has its own index vector indices[b] (the pointers may repeat).  Indices may repeat
+ * inside a vector, so m may exceed n.  m = 0 gives the identity, count = 0 returns at once.
+ *
+ * Limits as at creation: levels * m < 2^30 and inside the launch plan's entry limit; the range
+ * form needs first + m <= n and the indexed form first == 0 (MSM_ERR_INVALID_ARG).  The opts rules
+ * are msm_bases_compute's, and so are the results for a stale handle or null arguments.
+ *
+ * An index >= n gives MSM_ERR_INVALID_ARG.  The host entries check every index of every vector
+ * before anything is uploaded or enqueued.  The device entries check on the device: the kernel that
+ * reads the caller's indices replaces such an index by 0, so it never becomes an out-of-range read,
+ * the launch runs to its end, and the entry then returns the error (its results are unspecified).
+ *
+ * The range [0, m) of a levels = 1 handle runs exactly as a handle of those m points does. */
+typedef struct msm_subset_t {
+  uint64_t first;                 /* range form: bases [first, first + m)                        */
+  uint64_t m;                     /* terms per MSM                                               */
+  const uint32_t* const* indices; /* NULL: range form.  Else indices[b] = the m base indices of
+                                     MSM b (each < n; host arrays for the host entries, device
+                                     pointers for the *_device entries); `first` must be 0       */
+} msm_subset_t;
+int msm_bases_compute_subset(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* scalars_be,
+                             const msm_opts* opts, uint32_t out_xy_be[16]);
+int msm_bases_compute_subset_device(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* d_scalars_be,
+                                    const msm_opts* opts, void* hip_stream, uint32_t out_xy_be[16]);
+int msm_bases_compute_subset_many(const msm_bases* bases, const msm_subset_t* subset,
+                                  const uint32_t* const* scalars_be, size_t count, const msm_opts* opts,
+                                  uint32_t* out_xy_be);
+int msm_bases_compute_subset_many_device(const msm_bases* bases, const msm_subset_t* subset,
+                                         const uint32_t* const* d_scalars_be, size_t count, const msm_opts* opts,
+                                         void* hip_stream, uint32_t* out_xy_be);
 
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,

@@ -13,6 +13,20 @@ or a time limit).  With --n one size runs in this process and prints / appends J
                                                `count` MSMs (compute_many_device), one awaited MSM
                                                from device scalars and from host scalars
 
+With --subset the pass is the subset sweep of DESIGN.md §9 instead (msm_bases_compute_subset*): on
+one handle of n points (--sizes, default 2^20), at levels 1 and at the handle's auto levels where
+they differ, for m in --subset-sizes (log2; default 12,16,18,20) one line per way of computing an
+m-term MSM:
+
+  {"entry": "subset", "form": "padded", ...}        msm_bases_compute*, the scalar vector zero-padded to n
+  {"entry": "subset", "form": "own_handle", ...}    a handle built from exactly those m points (the floor)
+  {"entry": "subset", "form": "range", "first"}     the range form at first = 0 and at first = n - m
+  {"entry": "subset", "form": "indexed", "order"}   the indexed form, sorted-unique and random indices
+
+each with the awaited call from host arrays and from device-resident ones and the pipelined call
+over `count` MSMs, both ways, plus the per-phase device times of one profiled awaited call
+(msm_set_profiling(1)).
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -113,6 +127,111 @@ def one_size(a):
     return 0 if all(d.get("correct", True) for d in lines) else 1
 
 
+def subset_pass(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import as_xy, scalar_dot
+    from oracle import oracle as O
+
+    n, count, k0, step = a.n, a.count, 3, 5
+    bad = []
+
+    def emit(d):
+        d = {"n": n, **d}
+        if not d.get("correct", True):
+            bad.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def closed(idx, sc):
+        return O.scalar_mul(O.G, scalar_dot(k0 + step * np.asarray(idx, dtype=np.uint64), sc) % O.R_ORDER)
+
+    phases = ("recode_count", "coarse_scatter", "fine_sort", "accumulate", "bucket_reduce_1", "bucket_reduce_2",
+              "device_total")
+
+    def profile(fn):
+        M.set_profiling(1)
+        try:
+            fn()
+            p = M.last_profile()
+        finally:
+            M.set_profiling(0)
+        return {k: round(float(p[k]), 4) for k in phases}
+
+    def measure(row, exp, host1, dev1, host_many, dev_many):
+        """The four timings of one way of computing the MSM, each checked against the closed form."""
+        ok = True
+        for key, fn, many in (("single_host", host1, False), ("single_device", dev1, False),
+                              ("pipelined_host", host_many, True), ("pipelined_device", dev_many, True)):
+            ms, runs, res = timed(fn, a.runs)
+            if many:
+                row[key + "_ms_per_msm"] = round(ms / count, 4)
+                ok = ok and [as_xy(r) for r in res] == [exp] * count
+            else:
+                row[key + "_ms"] = round(ms, 4)
+                ok = ok and res == exp
+            row[key + "_runs_ms"] = runs
+        row["phases_ms"] = profile(dev1)
+        row["correct"] = ok
+        emit(row)
+
+    pts = M.gen_points(n, k0=k0, step=step)
+    d_pts = dev(pts)
+    auto = M.Bases.from_device(d_pts, n)
+    auto_levels = auto.info["levels"]
+    auto.close()
+    rnd = np.random.RandomState(17)
+    for levels in sorted({1, auto_levels}):
+        with M.Bases.from_device(d_pts, n, levels=levels) as b:
+            for lg in a.subset_sizes:
+                m = 1 << lg
+                if m > n:
+                    continue
+                sc = M.gen_scalars(m, seed=900 + lg)
+                d_sc = dev(sc)
+                base = {"entry": "subset", "levels": levels, "m": m, "count": count}
+                # (a) today's workaround: the full entry on a scalar vector zero-padded to n
+                pad = np.zeros((n, 8), np.uint32)
+                pad[:m] = sc
+                d_pad = dev(pad)
+                measure({**base, "form": "padded"}, closed(np.arange(m), sc),
+                        lambda: b.compute(pad), lambda: b.compute_device(d_pad),
+                        lambda: b.compute_many([pad] * count), lambda: b.compute_many_device([d_pad] * count))
+                del pad, d_pad
+                # (b) a handle of exactly those m points: the floor
+                with M.Bases.from_device(d_pts, m, levels=levels) as own:
+                    measure({**base, "form": "own_handle"}, closed(np.arange(m), sc),
+                            lambda: own.compute(sc), lambda: own.compute_device(d_sc),
+                            lambda: own.compute_many([sc] * count), lambda: own.compute_many_device([d_sc] * count))
+                # (c) the range form
+                for first in sorted({0, n - m}):
+                    measure({**base, "form": "range", "first": first}, closed(first + np.arange(m), sc),
+                            lambda: b.compute_subset(sc, first=first),
+                            lambda: b.compute_subset_device(d_sc, first=first),
+                            lambda: b.compute_subset_many([sc] * count, first=first),
+                            lambda: b.compute_subset_many_device([d_sc] * count, first=first))
+                # (d) the indexed form
+                for order in ("sorted_unique", "random"):
+                    if order == "random":
+                        idx = rnd.randint(0, n, size=m).astype(np.uint32)
+                    else:
+                        idx = np.sort(rnd.permutation(n)[:m]).astype(np.uint32)
+                    d_idx = dev(idx)
+                    measure({**base, "form": "indexed", "order": order}, closed(idx, sc),
+                            lambda: b.compute_subset(sc, indices=idx),
+                            lambda: b.compute_subset_device(d_sc, indices=d_idx),
+                            lambda: b.compute_subset_many([sc] * count, indices=idx),
+                            lambda: b.compute_subset_many_device([d_sc] * count, indices=d_idx))
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=0, help="run this one size in-process")
@@ -122,9 +241,20 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--wide", action="store_true", help="also time c = 17 (32-bit digit codes)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--subset", action="store_true", help="the subset sweep (msm_bases_compute_subset*) instead")
+    ap.add_argument("--subset-sizes", default="12,16,18,20", help="log2 term counts m of the subset sweep")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
+    if a.subset:
+        a.subset_sizes = [int(x) for x in str(a.subset_sizes).split(",")]
+        if a.n:
+            return subset_pass(a)
+        lg = int(a.sizes.split(",")[-1])  # one handle: the largest size given (default 2^20)
+        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n", str(1 << lg),
+               "--subset", "--subset-sizes", ",".join(map(str, a.subset_sizes)), "--count", str(a.count),
+               "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
+        return subprocess.run(cmd).returncode
     if a.n:
         return one_size(a)
     for lg in (int(x) for x in a.sizes.split(",")):

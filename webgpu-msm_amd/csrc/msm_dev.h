@@ -41,7 +41,16 @@ struct MsmDims {
                    // (when nm n <= 2^(31 - fb)); else a separate u16 array holds the fine keys
   uint32_t shared; // every MSM of the batch uses ONE base vector (prover batch): entries index
                    // point records [0, n) instead of [m n, (m+1) n)
+  // Subset launches on a handle's records (msm_bases_compute_subset*): the launch's n positions are
+  // `levels` levels of sm terms each, and position p = j sm + i (level j, term i) takes record
+  // j rstride + first + i (MSM_SUB_RANGE) or j rstride + idx[i] (MSM_SUB_INDEXED: the slot's staged
+  // index vector of the window's MSM).  All zero for every other launch (k_part_scatter reads none).
+  uint32_t sub;      // MSM_SUB_*
+  uint32_t rstride;  // records per level of the handle: its n
+  uint32_t first;    // range form: the first base of the range
+  uint32_t sm;       // terms per level: n / levels
 };
+constexpr uint32_t MSM_SUB_NONE = 0, MSM_SUB_RANGE = 1, MSM_SUB_INDEXED = 2;
 
 
 constexpr uint32_t MAIN_BITS = 254;  // bits covered by the main windows (scalars < 2^253, + carry)
@@ -72,5 +81,6 @@ constexpr uint32_t KEY_PASS = 0x80000000u;
 
 constexpr uint32_t MSM_DEV_ERR_COORD_RANGE = 1u;  // a coordinate >= p (bytes.rs:19 panics)
 constexpr uint32_t MSM_DEV_ERR_BAD_POINT = 2u;    // z == 0
+constexpr uint32_t MSM_DEV_ERR_BAD_INDEX = 4u;    // a subset's base index >= the handle's n (k_stage_indices)
 
 }  // namespace msm

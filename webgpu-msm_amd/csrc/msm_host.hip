@@ -144,7 +144,8 @@ bool plan_eq(const Plan& a, const Plan& b) {
          x.half_lo == y.half_lo && x.half_hi == y.half_hi &&
          x.nm == y.nm && x.q == y.q &&
          x.nhi == y.nhi && x.fb == y.fb && x.nbc == y.nbc && x.nbins == y.nbins && x.ch == y.ch && x.nch == y.nch &&
-         x.packed == y.packed && x.shared == y.shared && a.K == b.K && a.L == b.L &&
+         x.packed == y.packed && x.shared == y.shared && x.sub == y.sub && x.rstride == y.rstride &&
+         x.first == y.first && x.sm == y.sm && a.K == b.K && a.L == b.L &&
          a.nchunks == b.nchunks && a.nv == b.nv && a.nterms == b.nterms && a.Mmax == b.Mmax &&
          a.runs_max == b.runs_max && a.pfmt == b.pfmt;
 }
@@ -157,13 +158,15 @@ struct Workspace {
   Buf wire_pts, wire_sc;  // device copies of host-resident inputs (msm_compute*, host entries)
   Buf red_G;               // k_red2_groups' points per (window, group of RG_CH chunks)
   Buf split_sc;            // k_split_scalars' virtual scalars of a folded launch (msm_bases_*, levels > 1)
+  Buf sub_idx;             // base indices [nm][m] of an indexed subset launch (msm_bases_compute_subset*)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
   void release() {
     Buf* bufs[] = {&pts, &err, &digits, &colsum, &bin_base, &bin_cur, &part_entry, &part_fine,
                    &sorted_entry, &bucket_start, &run_key, &buckets, &lead_val, &lead_open, &cross_key,
-                   &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G, &split_sc};
+                   &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G, &split_sc,
+                   &sub_idx};
     for (Buf* b : bufs) b->release();
   }
 };
@@ -485,8 +488,17 @@ uint32_t run_length_for(const MsmDims& d, const DevShape& sh, bool pipelined) {
 
 int finish_plan(const MsmDims& d, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined = false);
 
+// A subset launch on a handle's records (msm_bases_compute_subset*): the plan's n is levels * m
+// terms, but its entries index the handle's whole record space, levels * rec_n records.
+struct SubsetGeo {
+  uint32_t kind = MSM_SUB_NONE;  // MSM_SUB_RANGE / MSM_SUB_INDEXED
+  uint32_t levels = 1;
+  size_t rec_n = 0;  // the handle's n: records per level
+  size_t first = 0;  // range form
+};
+
 int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined = false, uint32_t nm = 1,
-              bool shared = false) {
+              bool shared = false, const SubsetGeo* sub = nullptr) {
   *pl = Plan{};
   uint32_t c = (o && o->window_bits) ? o->window_bits : pipelined ? pipelined_window(n) : msm_best_window(n);
   if (c < 4 || c > 20) return MSM_ERR_UNSUPPORTED_WINDOW;
@@ -525,7 +537,16 @@ int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pi
   d.nbc = nbc;
   d.fb = ilog2(d.B / nbc);
   d.shared = shared ? 1u : 0u;
-  const uint64_t npts = shared ? n : (uint64_t)nm * n;  // point records the entries index
+  uint64_t npts = shared ? n : (uint64_t)nm * n;  // point records the entries index
+  if (sub && sub->kind != MSM_SUB_NONE) {
+    // every count follows the launch's levels * m terms; the entry width alone follows the records
+    npts = (uint64_t)sub->levels * sub->rec_n;
+    if (npts >= (1ull << 30) || sub->first >= (1ull << 30) || n % sub->levels) return MSM_ERR_INVALID_ARG;
+    d.sub = sub->kind;
+    d.rstride = (uint32_t)sub->rec_n;
+    d.first = (uint32_t)sub->first;
+    d.sm = (uint32_t)(n / sub->levels);
+  }
   d.packed = npts <= (1ull << (31 - d.fb)) ? 1u : 0u;
   d.nbins = d.W * d.nbc;
   d.ch = PT_THREADS * PS_R;  // 16384 digits per partition chunk (>= 64 per bin slice while nbc <= 256)
@@ -772,7 +793,26 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
     launch_recode(d, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), s);
     mark(PH_RECODE);
     mark(PH_SCAN);
-    if (d.c <= 16) {
+    if (d.sub != MSM_SUB_NONE) {
+      // a subset launch on a handle's records: the scatter's record-mapping variants, reading the
+      // slot's own index buffer (a fixed address: the captured node never holds a caller's pointer)
+      auto scatter = [&](auto kern, auto* dig) {
+        hipLaunchKernelGGL(kern, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s, dig, d,
+                           w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(), w.bin_base.as<uint32_t>(),
+                           w.part_entry.as<uint32_t>(), w.part_fine.as<uint16_t>(),
+                           static_cast<const uint32_t*>(w.sub_idx.as<uint32_t>()));
+      };
+      const bool ix = d.sub == MSM_SUB_INDEXED;
+      if (d.c <= 16) {
+        const uint16_t* dig = w.digits.as<uint16_t>();
+        if (ix) scatter(k_part_scatter<uint16_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
+        else scatter(k_part_scatter<uint16_t, MSM_SUB_RANGE, const uint32_t*>, dig);
+      } else {
+        const uint32_t* dig = w.digits.as<uint32_t>();
+        if (ix) scatter(k_part_scatter<uint32_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
+        else scatter(k_part_scatter<uint32_t, MSM_SUB_RANGE, const uint32_t*>, dig);
+      }
+    } else if (d.c <= 16) {
       hipLaunchKernelGGL(k_part_scatter<uint16_t>, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s,
                          w.digits.as<uint16_t>(), d, w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(),
                          w.bin_base.as<uint32_t>(), w.part_entry.as<uint32_t>(),
@@ -1688,6 +1728,7 @@ int wait_slot(DevCtx* c, int si, uint32_t* total_out = nullptr) {
   }
   if (err & MSM_DEV_ERR_COORD_RANGE) return MSM_ERR_COORD_RANGE;
   if (err & MSM_DEV_ERR_BAD_POINT) return MSM_ERR_BAD_POINT;
+  if (err & MSM_DEV_ERR_BAD_INDEX) return MSM_ERR_INVALID_ARG;  // a device-entry subset's index >= n
   return MSM_OK;
 }
 
@@ -2028,6 +2069,15 @@ struct ManyInputs {
   // width and the window range [0, Wc)).
   const uint32_t* prepared = nullptr;
   uint32_t levels = 1, chunk_bits = 0;
+  // A subset of the handle's bases (msm_bases_compute_subset*; `prepared` set): run_many's n is then
+  // the subset's m terms and everything is planned for levels * m, while the entries index the
+  // handle's levels * rec_n records -- bases [first, first + m) of every level (MSM_SUB_RANGE) or
+  // bases indices[b][0..m) for MSM b (MSM_SUB_INDEXED: host arrays, validated by the caller, or
+  // device pointers, by `kind`).  The range [0, m) of a levels = 1 handle is not a subset launch
+  // but the plain one on the first m records (sub = MSM_SUB_NONE).
+  uint32_t sub = MSM_SUB_NONE;
+  size_t sub_first = 0, rec_n = 0;
+  const uint32_t* const* indices = nullptr;
 };
 
 // `count` MSMs of n points each, pipelined over pipeline_slots slots, each with its own stream and
@@ -2064,8 +2114,17 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
   const uint32_t nm = (uint32_t)std::min<size_t>(
       in.batch ? std::min<size_t>(in.batch, count) : pipeline_batch(n, count), MSM_MAX_BATCH);
   const size_t nbatch = (count + nm - 1) / nm;
+  SubsetGeo sg;
+  sg.kind = prepared ? in.sub : MSM_SUB_NONE;
+  sg.levels = kf;
+  sg.rec_n = in.rec_n;
+  sg.first = in.sub_first;
+  const bool indexed = sg.kind == MSM_SUB_INDEXED;
+  if (indexed)
+    for (size_t b = 0; b < count; b++)
+      if (!in.indices || !in.indices[b]) return MSM_ERR_INVALID_ARG;
   Plan pl;
-  int rc = make_plan(np, o, c->shape, &pl, count > 1, nm, shared);
+  int rc = make_plan(np, o, c->shape, &pl, count > 1, nm, shared, &sg);
   if (rc != MSM_OK) return rc;
   // host inputs: one more launch in flight, so its upload queues behind the running ones
   // (2^20 msm_compute 4.21 -> 4.05 ms with three, profiles/r2t_*; device inputs are best with two)
@@ -2075,6 +2134,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     c->slot[si].pipelined = nslot > 1;
     if ((rc = ensure_workspace(c, pl, si, !prepared)) != MSM_OK) return rc;
     if (kf > 1 && (rc = c->slot[si].ws.split_sc.ensure((size_t)nm * np * 32)) != MSM_OK) return rc;
+    if (indexed && (rc = c->slot[si].ws.sub_idx.ensure((size_t)nm * n * 4)) != MSM_OK) return rc;
     if (host) {
       Workspace& w = c->slot[si].ws;
       if ((!shared && (rc = w.wire_pts.ensure((size_t)nm * n * 128)) != MSM_OK) ||
@@ -2222,6 +2282,15 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
       return true;
     };
     if (!in.dev_scalars && !up(in.scalars, bs, 8)) return MSM_ERR_HIP;
+    if (indexed) {
+      // the launch's index vectors into the slot's own buffer (validated by the entry: no kernel);
+      // the padding MSMs of a short last launch repeat the last real MSM's, as they do its scalars
+      uint32_t* ib = c->slot[j % nslot].ws.sub_idx.as<uint32_t>();
+      for (uint32_t m = 0; m < nm; m++)
+        if (hipMemcpyAsync(ib + (size_t)m * n, in.indices[j * nm + std::min(m, nreal - 1)], n * 4,
+                           hipMemcpyHostToDevice, c->copy_stream) != hipSuccess)
+          return MSM_ERR_HIP;
+    }
     for (uint32_t m = 0; m < nreal && !shared; m++) {
       const size_t len = len_of(std::min(j * nm + m, count - 1));
       if (len < n) {
@@ -2277,6 +2346,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
   // and the pool the earlier launches' tails (their terms copied out per launch)
   HornerPool* pool = ctx_pool(c);
   std::vector<std::vector<uint32_t>> launch_terms(pool ? nbatch : 0);
+  size_t finished = 0;  // launches waited for (finish_msm returned, with or without an error)
   auto fail = [&](int code) {
     if (crew_armed) crew->disarm();  // no terms will come
     crew_armed = false;
@@ -2284,6 +2354,11 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     stop_uploader();
     hipStreamSynchronize(c->copy_stream);
     for (int k = 0; k < nslot; k++) hipStreamSynchronize(c->slot[k].stream);
+    // An indexed subset fails at run time (MSM_DEV_ERR_BAD_INDEX) with other launches in flight:
+    // each of those is waited for as usual, so that a skewed one still gets its second reduction,
+    // which is what clears its slot's skew flags for the next call.
+    if (indexed && !host)
+      for (size_t j = finished; j < enqueued.load(); j++) (void)wait_slot(c, (int)(j % nslot));
     return code;
   };
   if (uploader) {
@@ -2320,7 +2395,10 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     // the last launch's terms stay in `terms` (its tails run here, over the crew); the pool's jobs
     // read their launch's own copy
     std::vector<uint32_t>* tdst = pool && have && f + 1 < nbatch ? &launch_terms[f] : &terms;
-    if (have && (rc = finish_msm(c, (int)(f % nslot), nullptr, tdst)) != MSM_OK) return fail(rc);
+    if (have) {
+      finished = f + 1;
+      if ((rc = finish_msm(c, (int)(f % nslot), nullptr, tdst)) != MSM_OK) return fail(rc);
+    }
     if (j < nbatch) {
       const int si = (int)(j % nslot);
       Slot& sl = c->slot[si];
@@ -2349,6 +2427,16 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
                            (uint32_t)n, kf, in.chunk_bits);
         if (hipGetLastError() != hipSuccess) return fail(MSM_ERR_HIP);
         for (uint32_t m = 0; m < MSM_MAX_BATCH; m++) bs.p[m] = vs + (size_t)std::min(m, nm - 1) * np * 8;
+      }
+      if (indexed && !host) {
+        // the caller's index vectors checked into the slot's buffer, on the slot's stream ahead of
+        // the (captured) sort; padding MSMs repeat the last real MSM's (launch_inputs' rule)
+        BatchPtrs bi{};
+        for (uint32_t m = 0; m < MSM_MAX_BATCH; m++)
+          bi.p[m] = in.indices[std::min(j * nm + std::min<uint32_t>(m, nm - 1), count - 1)];
+        hipLaunchKernelGGL(k_stage_indices, dim3(grid_for(n, 256), nm), dim3(256), 0, sl.stream, bi,
+                           sl.ws.sub_idx.as<uint32_t>(), (uint32_t)n, (uint32_t)in.rec_n, sl.ws.err.as<uint32_t>());
+        if (hipGetLastError() != hipSuccess) return fail(MSM_ERR_HIP);
       }
       Plan plj = pl;
       plj.pfmt = packed ? launch_fmt[j] : PT_FMT_WIRE;  // set by the uploader before up_ready
@@ -3008,13 +3096,41 @@ int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* op
   return MSM_OK;
 }
 
+// The argument rules of a subset that need no device: the range inside the handle's n bases, no
+// `first` beside an index list, and levels * m inside the creation limit.
+int subset_check(size_t n_handle, uint32_t levels, uint64_t first, uint64_t m, bool indexed) {
+  if (indexed ? first != 0 || (m && !n_handle) : first > n_handle || m > n_handle - first) return MSM_ERR_INVALID_ARG;
+  if (m >= (1ull << 30) || (uint64_t)levels * m >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  return MSM_OK;
+}
+// The range [0, m) of an unfolded handle is the plain launch on its first m records (the existing
+// kernels with n := m); every other subset is a subset launch (MsmDims::sub).
+uint32_t subset_kind(uint32_t levels, uint64_t first, bool indexed) {
+  return indexed ? MSM_SUB_INDEXED : (first == 0 && levels == 1) ? MSM_SUB_NONE : MSM_SUB_RANGE;
+}
+
 // `count` MSMs over a handle's records: run_many's pipelined path with the records in the place
 // of a shared base vector's (count = 1: the single entries, which then have no preparation to fork).
+// With `sub`, over a subset of the bases (msm_bases_compute_subset*).
 int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host, size_t count, const msm_opts* opts,
-                  void* hip_stream, uint32_t* out) {
-  if (!h || !out || (!scalars && count) || !bases_flags_ok(opts)) return MSM_ERR_INVALID_ARG;
+                  void* hip_stream, uint32_t* out, const msm_subset_t* sub = nullptr, bool is_subset = false) {
+  if (!h || !out || (!scalars && count) || !bases_flags_ok(opts) || (is_subset && !sub)) return MSM_ERR_INVALID_ARG;
   std::shared_ptr<Bases> b = find_bases(h);
   if (!b) return MSM_ERR_INVALID_ARG;
+  const bool indexed = sub && sub->indices;
+  const size_t terms = sub ? (size_t)sub->m : b->n;  // scalars per vector
+  if (sub) {
+    if (int rc = subset_check(b->n, b->levels, sub->first, sub->m, indexed)) return rc;
+    for (size_t k = 0; indexed && terms && k < count; k++) {
+      const uint32_t* ix = sub->indices[k];
+      if (!ix) return MSM_ERR_INVALID_ARG;
+      // host index vectors are checked here, before anything is uploaded or enqueued (the device
+      // entries' are checked by k_stage_indices); a vector given again is checked once
+      if (!host || (k && ix == sub->indices[k - 1])) continue;
+      for (size_t i = 0; i < terms; i++)
+        if (ix[i] >= b->n) return MSM_ERR_INVALID_ARG;
+    }
+  }
   if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
   msm_opts o{};
   o.run_length = opts ? opts->run_length : 0;
@@ -3030,7 +3146,7 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   }
   if (count == 0) return MSM_OK;
   for (size_t k = 0; k < count; k++)
-    if (!scalars[k] && b->n) return MSM_ERR_INVALID_ARG;
+    if (!scalars[k] && terms) return MSM_ERR_INVALID_ARG;
   return on_device(&o, [&](DevCtx* c) -> int {
     if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
     ManyInputs in;
@@ -3039,7 +3155,13 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
     in.prepared = b->rec.as<uint32_t>();
     in.levels = b->levels;
     in.chunk_bits = b->geo.S;
-    return run_many(c, in, b->n, count, &o, (hipStream_t)hip_stream, out, false);
+    if (sub) {
+      in.sub = subset_kind(b->levels, sub->first, indexed);
+      in.sub_first = (size_t)sub->first;
+      in.rec_n = b->n;
+      in.indices = sub->indices;
+    }
+    return run_many(c, in, terms, count, &o, (hipStream_t)hip_stream, out, false);
   });
 }
 
@@ -3365,6 +3487,27 @@ int msm_bases_compute_device(const msm_bases* h, const uint32_t* d_scalars_be, c
 int msm_bases_compute_many(const msm_bases* h, const uint32_t* const* scalars_be, size_t count, const msm_opts* opts,
                            uint32_t* out_xy_be) {
   return bases_compute(h, scalars_be, true, count, opts, nullptr, out_xy_be);
+}
+
+int msm_bases_compute_subset(const msm_bases* h, const msm_subset_t* sub, const uint32_t* scalars_be,
+                             const msm_opts* opts, uint32_t out_xy_be[16]) {
+  return bases_compute(h, &scalars_be, true, 1, opts, nullptr, out_xy_be, sub, true);
+}
+
+int msm_bases_compute_subset_device(const msm_bases* h, const msm_subset_t* sub, const uint32_t* d_scalars_be,
+                                    const msm_opts* opts, void* hip_stream, uint32_t out_xy_be[16]) {
+  return bases_compute(h, &d_scalars_be, false, 1, opts, hip_stream, out_xy_be, sub, true);
+}
+
+int msm_bases_compute_subset_many(const msm_bases* h, const msm_subset_t* sub, const uint32_t* const* scalars_be,
+                                  size_t count, const msm_opts* opts, uint32_t* out_xy_be) {
+  return bases_compute(h, scalars_be, true, count, opts, nullptr, out_xy_be, sub, true);
+}
+
+int msm_bases_compute_subset_many_device(const msm_bases* h, const msm_subset_t* sub,
+                                         const uint32_t* const* d_scalars_be, size_t count, const msm_opts* opts,
+                                         void* hip_stream, uint32_t* out_xy_be) {
+  return bases_compute(h, d_scalars_be, false, count, opts, hip_stream, out_xy_be, sub, true);
 }
 
 int msm_bases_compute_many_device(const msm_bases* h, const uint32_t* const* d_scalars_be, size_t count,
@@ -3839,6 +3982,40 @@ int msm_test_bases_plan(size_t n, uint32_t levels, uint32_t window_bits, uint32_
   out[1] = g.Wc;
   out[2] = g.S;
   out[3] = (uint32_t)(n * levels);
+  return MSM_OK;
+}
+
+// The launch plan of one subset MSM (msm_bases_compute_subset*) of m terms on a handle of n_handle
+// points and `levels` levels at width window_bits (0: the width such a handle or launch gets):
+// out = {d.n, d.packed, the record stride d.rstride, d.fb, d.sub}.  The argument rules that need no
+// device apply (MSM_ERR_INVALID_ARG); the range [0, m) of a levels = 1 handle reports the plain
+// plan of m points (sub 0, stride 0).  Host code only.
+int msm_test_subset_plan(size_t n_handle, uint32_t levels, uint32_t window_bits, uint64_t first, uint64_t m,
+                         int indexed, uint32_t out[5]) {
+  if (!out || levels < 1 || levels > 8) return MSM_ERR_INVALID_ARG;
+  if ((uint64_t)levels * n_handle >= (1ull << 30)) return MSM_ERR_INVALID_ARG;  // no such handle
+  if (int rc = subset_check(n_handle, levels, first, m, indexed != 0)) return rc;
+  msm_opts op{};
+  op.window_bits = window_bits;
+  if (levels > 1) {
+    BasesGeo g;
+    op.window_bits = window_bits ? window_bits : bases_auto_window(n_handle, levels);
+    if (!bases_geometry(op.window_bits, levels, &g)) return MSM_ERR_UNSUPPORTED_WINDOW;
+    op.flags = MSM_FLAG_WINDOWS;
+    op.window_hi = g.Wc;
+  }
+  SubsetGeo sg;
+  sg.kind = subset_kind(levels, first, indexed != 0);
+  sg.levels = levels;
+  sg.rec_n = n_handle;
+  sg.first = (size_t)first;
+  Plan pl;
+  if (int rc = make_plan((size_t)m * levels, &op, DevShape{}, &pl, false, 1, true, &sg)) return rc;
+  out[0] = pl.d.n;
+  out[1] = pl.d.packed;
+  out[2] = pl.d.rstride;
+  out[3] = pl.d.fb;
+  out[4] = pl.d.sub;
   return MSM_OK;
 }
 

@@ -9,7 +9,8 @@
 //                      written window-major (= first sort level: one contiguous array per window),
 //                      with the coarse-bin totals (LDS histogram, flushed with global atomics)
 //   k_part_scatter     digits -> coarse bins (each chunk reserves and writes one contiguous slice
-//                      per bin)
+//                      per bin); its range / indexed variants map a subset launch's positions to
+//                      a handle's records (k_stage_indices checks a device caller's indices first)
 //   k_fine_sort        per coarse bin: LDS counting sort by bucket -> (entry, bucket key) lists
 //   k_accumulate       fixed-length runs per lane over the sorted list (mixed adds), whole buckets
 //                      written directly, buckets cut by run boundaries joined through LDS
@@ -809,13 +810,48 @@ struct PartStage<uint32_t> {
 };
 static_assert(PT_THREADS * PS_R == (1u << PS_POS) && PS_POS <= 16, "PartStage<uint16_t> packs code and position in 32 bits");
 
-template <typename T>
+//
+// Which point record a position of the launch takes is the one thing a subset launch on a handle's
+// records changes (MsmDims::sub): SUB is a compile-time variant, and MSM_SUB_NONE -- every launch
+// but msm_bases_compute_subset*'s -- compiles to the plain `pbase + position`.
+template <uint32_t SUB>
+__device__ __forceinline__ uint32_t part_record(const MsmDims& d, uint32_t pbase, uint32_t p,
+                                                const uint32_t* __restrict__ idx) {
+  if constexpr (SUB == MSM_SUB_NONE) {
+    return pbase + p;
+  } else {
+    // level j = p / sm by at most 7 compares against wave-uniform thresholds (levels <= 8; a
+    // threshold past the launch's positions never fires), term i = p - j sm
+    uint32_t i = p, base = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 8; k++) {
+      const uint64_t t64 = (uint64_t)k * d.sm;
+      const uint32_t t = t64 > 0xffffffffull ? 0xffffffffu : (uint32_t)t64;
+      const bool up = p >= t;
+      i -= up ? d.sm : 0u;
+      base += up ? d.rstride : 0u;
+    }
+    // the indexed form gathers where the entry word is written: the workgroup's positions stay inside
+    // one chunk-long span of the staged vector (L2-resident)
+    return base + (SUB == MSM_SUB_RANGE ? d.first + i : idx[i]);
+  }
+}
+
+__device__ __forceinline__ const uint32_t* part_sub_idx() { return nullptr; }
+__device__ __forceinline__ const uint32_t* part_sub_idx(const uint32_t* p) { return p; }
+
+// The subset variants take one more argument, the slot's staged index buffer [nm][sm]
+// (k_stage_indices, or the host entries' upload; unread by the range form): IDX is that argument's
+// type, and empty for the plain kernel, whose argument list and code are what they were before the
+// variants existed.
+template <typename T, uint32_t SUB = MSM_SUB_NONE, typename... IDX>
 __global__ void __launch_bounds__(PT_THREADS) k_part_scatter(const T* __restrict__ digits, MsmDims d,
                                                              uint32_t* __restrict__ colsum,
                                                              uint32_t* __restrict__ bin_cur,
                                                              uint32_t* __restrict__ bin_base,
                                                              uint32_t* __restrict__ part_entry,
-                                                             uint16_t* __restrict__ part_fine) {
+                                                             uint16_t* __restrict__ part_fine, IDX... sub_idx) {
+  static_assert(sizeof...(IDX) == (SUB == MSM_SUB_NONE ? 0 : 1), "the subset variants take the index buffer");
   using S = PartStage<T>;
   __shared__ typename S::V st[PT_THREADS * PS_R];
   __shared__ uint32_t m_live;
@@ -904,12 +940,15 @@ __global__ void __launch_bounds__(PT_THREADS) k_part_scatter(const T* __restrict
   PROBE(1, pwg, 5);
   const uint32_t m = lcnt[d.nbc - 1] + m_live;  // live digits of the chunk
   const uint32_t fmask = (1u << fbw) - 1u;
+  // the staged index vector of this window's MSM (indexed subsets only)
+  [[maybe_unused]] const uint32_t* idx = nullptr;
+  if constexpr (SUB == MSM_SUB_INDEXED) idx = part_sub_idx(sub_idx...) + (size_t)(w / d.Wr) * d.sm;
   for (uint32_t j = threadIdx.x; j < m; j += PT_THREADS) {
     const typename S::V v = st[j];
     const uint32_t cd = S::code(v);
     const uint32_t b = cd & DigitCode<T>::MAG;
     const uint32_t fine = b & fmask;
-    const uint32_t ent = ((pbase + lo + S::pos(v)) << 1) | (cd >> DigitCode<T>::SHIFT);
+    const uint32_t ent = (part_record<SUB>(d, pbase, lo + S::pos(v), idx) << 1) | (cd >> DigitCode<T>::SHIFT);
     const uint32_t dst = j + gdel[b >> fbw];
     // packed: the fine key in the low d.fb bits (a narrower window's fbw <= d.fb of them used)
     part_entry[dst] = d.packed ? (ent << d.fb) | fine : ent;
@@ -917,6 +956,24 @@ __global__ void __launch_bounds__(PT_THREADS) k_part_scatter(const T* __restrict
   }
   PROBE(1, pwg, 6);
   PROBE(1, pwg, 7);
+}
+
+// The caller's base indices of a device-entry subset launch into the slot's buffer: out[z][i] =
+// idx_sets.p[z][i] for the launch's nm MSMs (blockIdx.y = z) of m indices each.  An index >= n (the
+// handle's points) is replaced by 0 -- it must never reach the record gather -- and raises
+// MSM_DEV_ERR_BAD_INDEX in the slot's err word, which the reduction reports with the terms and
+// clears, as it does the preparation's bits: the launch runs to its end and the entry then fails.
+extern "C" __global__ void __launch_bounds__(256) k_stage_indices(BatchPtrs idx_sets, uint32_t* __restrict__ out,
+                                                                    uint32_t m, uint32_t n,
+                                                                    uint32_t* __restrict__ err) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  uint32_t v = idx_sets.p[blockIdx.y][i];
+  if (v >= n) {
+    v = 0;
+    atomicOr(err, MSM_DEV_ERR_BAD_INDEX);
+  }
+  out[(size_t)blockIdx.y * m + i] = v;
 }
 
 // Pass 3: one workgroup per coarse bin, counting sort by fine bucket (<= FS_MAXF per bin).  A bin

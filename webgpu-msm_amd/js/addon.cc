@@ -28,6 +28,8 @@
 // addon's enumerable surface):
 //   prepareBases(points: Uint32Array(32n), levels?, windowSize?) -> { id, n, levels, windowSize, bytes }
 //   computeMsmPrepared(id, scalars: Uint32Array(8n)) -> Promise<Uint32Array(16)>
+//   computeMsmPrepared(id, scalars: Uint32Array(8m), first?: number, indices?: Uint32Array(m))
+//       over a subset of the bases: the range [first, first + m), or bases indices[0..m)
 //   releaseBases(id) -> number (0 ok, -1 for a handle already released)
 //   Handles left open are freed by the cleanup hook's msm_shutdown.
 #include <node_api.h>
@@ -116,6 +118,11 @@ struct Job {
   std::vector<int32_t> devices;  // empty: the current device
   double cpu_work_ratio = 0;     // > 0: CPU/GPU co-compute (msm_compute_cocompute)
   const msm_bases* bases = nullptr;  // computeMsmPrepared: the handle whose records the MSM reads
+  // computeMsmPrepared over a subset of the handle's bases (msm_bases_compute_subset): n terms over
+  // bases [first, first + n), or over bases indices[0..n) (a copy of the caller's array)
+  bool subset = false, indexed = false;
+  uint64_t first = 0;
+  std::vector<uint32_t> indices;
   uint32_t out[16] = {0};
   int rc = 0;
 };
@@ -133,6 +140,15 @@ void execute(napi_env, void* data) {
   }
   const uint32_t* pts = j->p_points ? j->p_points : j->stage ? j->stage->points.data() : j->points.data();
   const uint32_t* sc = j->p_scalars ? j->p_scalars : j->stage ? j->stage->scalars.data() : j->scalars.data();
+  if (j->bases && j->subset) {
+    const uint32_t* ix = j->indices.data();
+    msm_subset_t sub;
+    sub.first = j->first;
+    sub.m = j->n;
+    sub.indices = j->indexed ? &ix : nullptr;
+    j->rc = msm_bases_compute_subset(j->bases, &sub, sc, nullptr, j->out);
+    return;
+  }
   if (j->bases) {
     j->rc = msm_bases_compute(j->bases, sc, nullptr, j->out);
     return;
@@ -525,28 +541,52 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// computeMsmPrepared(id, scalars[, first, indices]): with `first` (a number) or `indices` (a
+// Uint32Array) the MSM runs over a subset of the handle's bases and the scalar array gives its
+// length (msm_bases_compute_subset); with neither (absent or undefined) over all of them.
 napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
+  size_t argc = 4;
+  napi_value argv[4];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   const uint32_t* sc;
   size_t slen;
   bool sshared = false;
   const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
-  if (argc < 2 || !h || !get_u32_array(env, argv[1], &sc, &slen, &sshared)) {
-    napi_throw_type_error(env, nullptr, "computeMsmPrepared(id: number, scalars: Uint32Array)");
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  const bool has_first = given(2), has_idx = given(3);
+  double first = 0;
+  const uint32_t* ix = nullptr;
+  size_t ilen = 0;
+  if (argc < 2 || !h || !get_u32_array(env, argv[1], &sc, &slen, &sshared) ||
+      (has_first && (napi_get_value_double(env, argv[2], &first) != napi_ok || !(first >= 0) ||
+                     first > 9007199254740992.0 || first != (double)(uint64_t)first)) ||
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen))) {
+    napi_throw_type_error(env, nullptr,
+                          "computeMsmPrepared(id: number, scalars: Uint32Array, first?: number, indices?: Uint32Array)");
     return nullptr;
   }
   msm_bases_info_t inf;
   int rc = msm_bases_info(h, &inf);
   if (rc != MSM_OK) return throw_rc(env, rc);  // released, or never a handle
-  if (slen / 8 < inf.n) {
+  const bool subset = has_first || has_idx;
+  if (!subset && slen / 8 < inf.n) {
     napi_throw_range_error(env, nullptr, "fewer scalars than the handle has points");
+    return nullptr;
+  }
+  if (has_idx && ilen != slen / 8) {
+    napi_throw_range_error(env, nullptr, "one index per scalar");
     return nullptr;
   }
   Job* j = new Job();
   j->bases = h;
-  j->n = (size_t)inf.n;
+  j->n = subset ? slen / 8 : (size_t)inf.n;
+  j->subset = subset;
+  j->indexed = has_idx;
+  j->first = (uint64_t)first;
+  if (has_idx) j->indices.assign(ix, ix + ilen);  // the worker reads a copy, as it does the scalars'
   if (sshared) {
     j->p_scalars = sc;
     if (napi_create_reference(env, argv[1], 1, &j->ref_scalars) != napi_ok) {

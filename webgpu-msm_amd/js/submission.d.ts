@@ -20,9 +20,14 @@ export declare function prepare_bases(
   baseAffinePoints: BigIntPoint[] | U32ArrayPoint[] | Uint32Array,
   options?: { levels?: number; windowSize?: number }
 ): BasesHandle;
+// With `subset` the MSM runs over a subset of the handle's bases and `scalars` gives its length m:
+// the range [first, first + m), or the bases indices[0..m) (each < handle.n, repeats allowed;
+// `first` must then be absent or 0).  An index or a range outside the handle rejects.
+export type BasesSubset = { first?: number; indices?: Uint32Array };
 export declare const compute_msm_prepared: (
   handle: BasesHandle,
-  scalars: bigint[] | Uint32Array[] | Uint32Array
+  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  subset?: BasesSubset
 ) => Promise<{ x: bigint; y: bigint }>;
 export declare function release_bases(handle: BasesHandle): number;
 

@@ -198,8 +198,21 @@ export function prepare_bases(baseAffinePoints, options) {
   return addon.prepareBases(pointWords(baseAffinePoints), levels, windowFrom(options));
 }
 
-export const compute_msm_prepared = async (handle, scalars) => {
+// With a third argument the MSM runs over a subset of the handle's bases, and `scalars` gives its
+// length m (msm_bases_compute_subset): { first } the range [first, first + m), { indices } (a
+// Uint32Array of m base indices, repeats allowed) the bases indices[i].  An index >= handle.n, or a
+// range past the end, rejects.  Without it the call is what it always was: all n bases.
+export const compute_msm_prepared = async (handle, scalars, subset) => {
   if (!handle || typeof handle.id !== "number") throw new TypeError("compute_msm_prepared(handle, scalars): not a handle");
+  if (subset !== undefined && subset !== null) {
+    const { first, indices } = subset;
+    if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("subset.indices: a Uint32Array");
+    if (first !== undefined && !(Number.isSafeInteger(first) && first >= 0)) throw new RangeError("subset.first: a non-negative integer");
+    // an empty options object is still a subset call: the prefix of as many bases as scalars
+    const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars), first === undefined ? 0 : first, indices);
+    const [x, y] = u32ArrayToBigInts(result);
+    return { x, y };
+  }
   const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars));
   const [x, y] = u32ArrayToBigInts(result);
   return { x, y };

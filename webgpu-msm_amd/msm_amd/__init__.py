@@ -68,6 +68,11 @@ class BasesInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
 
 
+class Subset(ctypes.Structure):
+    """include/msm.h msm_subset_t."""
+    _fields_ = [("first", ctypes.c_uint64), ("m", ctypes.c_uint64), ("indices", ctypes.c_void_p)]
+
+
 MSM_FLAG_SERIAL = 1  # pipelined entries: one launch in flight at a time
 MSM_FLAG_DEVICES = 2  # msm_opts carries a device list (include/msm.h)
 MSM_FLAG_WINDOWS = 4  # msm_opts carries a window range
@@ -143,6 +148,12 @@ def load() -> ctypes.CDLL:
         "msm_bases_compute_device": ([vp, vp, optp, vp, u32p], ctypes.c_int),
         "msm_bases_compute_many": ([vp, vp, sz, optp, u32p], ctypes.c_int),
         "msm_bases_compute_many_device": ([vp, vp, sz, optp, vp, u32p], ctypes.c_int),
+        "msm_bases_compute_subset": ([vp, ctypes.POINTER(Subset), vp, optp, u32p], ctypes.c_int),
+        "msm_bases_compute_subset_device": ([vp, ctypes.POINTER(Subset), vp, optp, vp, u32p], ctypes.c_int),
+        "msm_bases_compute_subset_many": ([vp, ctypes.POINTER(Subset), vp, sz, optp, u32p], ctypes.c_int),
+        "msm_bases_compute_subset_many_device": ([vp, ctypes.POINTER(Subset), vp, sz, optp, vp, u32p], ctypes.c_int),
+        "msm_test_subset_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                  u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -557,6 +568,112 @@ class Bases:
                "msm_bases_compute_many_device")
         return o[:16 * count].reshape(count, 16)
 
+    # ---- subsets of the bases (include/msm.h msm_bases_compute_subset*) ----
+    # Range form: bases [first, first + m).  Indexed form: bases indices[i] (uint32, each < n,
+    # repeats allowed; `first` must stay 0).  m is the length of the scalar vector(s).
+
+    @staticmethod
+    def _subset(first: int, m: int, index_ptrs: Optional[Sequence[int]]):
+        """A msm_subset_t by reference; the pointer array is kept alive by the returned object."""
+        sub = Subset(int(first), int(m), None)
+        if index_ptrs is not None:
+            arr = (ctypes.c_void_p * max(len(index_ptrs), 1))(*index_ptrs)
+            sub.indices = ctypes.cast(arr, ctypes.c_void_p)
+            sub._keep = arr
+        return sub
+
+    @staticmethod
+    def _host_indices(indices, m: int, count: int):
+        """Host index vectors of `count` MSMs (one array: shared by all) as uint32 arrays of m."""
+        if indices is None:
+            return None, None
+        vecs = list(indices) if isinstance(indices, (list, tuple)) else [indices] * count
+        if len(vecs) != count:
+            raise ValueError("one index vector per scalar vector")
+        keep, seen = [], {}
+        for v in vecs:  # a vector given again keeps one copy, and so one pointer
+            if id(v) not in seen:
+                seen[id(v)] = np.ascontiguousarray(np.asarray(v).astype(np.uint32, copy=False).reshape(-1))
+            keep.append(seen[id(v)])
+        if any(a.shape[0] != m for a in keep):
+            raise ValueError("an index vector's length differs from the scalar vector's")
+        return keep, [a.ctypes.data for a in keep]
+
+    @staticmethod
+    def _device_indices(indices, count: int):
+        if indices is None:
+            return None
+        vecs = list(indices) if isinstance(indices, (list, tuple)) else [indices] * count
+        if len(vecs) != count:
+            raise ValueError("one index vector per scalar vector")
+        for t in vecs:
+            if hasattr(t, "dtype") and hasattr(t, "element_size") and t.element_size() != 4:
+                raise ValueError("device indices must be a 32-bit integer tensor")
+        return [_dev_ptr(t) for t in vecs]
+
+    def compute_subset(self, scalars, first: int = 0, indices=None, window_size: Optional[int] = None,
+                       run_length: Optional[int] = None) -> Tuple[int, int]:
+        """One MSM of the m = len(scalars) host scalars over bases [first, first + m), or over
+        bases indices[0..m) (a uint32 array)."""
+        sc = np.ascontiguousarray(scalars_to_wire(scalars))
+        m = sc.shape[0]
+        keep, ptrs = self._host_indices(indices, m, 1)
+        sub = self._subset(first, m, ptrs)
+        o, op = _out(16)
+        _check(load().msm_bases_compute_subset(self._h or None, ctypes.byref(sub), _ptr(sc),
+                                               _opts(window_size, run_length), op), "msm_bases_compute_subset")
+        return _xy(o)
+
+    def compute_subset_device(self, d_scalars, first: int = 0, indices=None, m: Optional[int] = None,
+                              window_size: Optional[int] = None, run_length: Optional[int] = None,
+                              stream: int = 0) -> Tuple[int, int]:
+        """The same with device-resident scalars (a torch tensor [m, 8], or a raw device pointer with
+        `m`) and, in indexed form, a device-resident int32/uint32 index tensor (or pointer)."""
+        m = len(d_scalars) if m is None else int(m)
+        sub = self._subset(first, m, self._device_indices(indices, 1))
+        o, op = _out(16)
+        _check(load().msm_bases_compute_subset_device(self._h or None, ctypes.byref(sub), _dev_ptr(d_scalars),
+                                                      _opts(window_size, run_length),
+                                                      _stream(stream, d_scalars, indices), op),
+               "msm_bases_compute_subset_device")
+        return _xy(o)
+
+    def compute_subset_many(self, scalars_list, first: int = 0, indices=None, window_size: Optional[int] = None,
+                            run_length: Optional[int] = None, flags: int = 0) -> np.ndarray:
+        """len(scalars_list) pipelined MSMs of host scalar vectors of one length m, over one range
+        or over each MSM's own index vector (`indices`: a list of arrays, or one array for all).
+        [count][16] BE words."""
+        ks, ss = _host_list(scalars_list, 8)
+        count = len(ks)
+        m = ks[0].shape[0] if count else 0
+        if any(b.shape[0] != m for b in ks):
+            raise ValueError("the scalar vectors of one call share their length")
+        keep, ptrs = self._host_indices(indices, m, count)
+        sub = self._subset(first, m, ptrs)
+        o, op = _out(16 * max(count, 1))
+        _check(load().msm_bases_compute_subset_many(self._h or None, ctypes.byref(sub), ctypes.cast(ss, ctypes.c_void_p),
+                                                    count, _opts(window_size, run_length, -1, flags), op),
+               "msm_bases_compute_subset_many")
+        return o[:16 * count].reshape(count, 16)
+
+    def compute_subset_many_device(self, scalars_list, first: int = 0, indices=None, m: Optional[int] = None,
+                                   window_size: Optional[int] = None, run_length: Optional[int] = None,
+                                   flags: int = 0, stream: int = 0) -> np.ndarray:
+        """The same with device-resident scalar (and index) vectors."""
+        count = len(scalars_list)
+        if m is None:
+            m = len(scalars_list[0]) if count else 0
+        ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
+        sub = self._subset(first, m, self._device_indices(indices, count))
+        tensors = list(scalars_list[:1]) + (list(indices[:1]) if isinstance(indices, (list, tuple)) else [indices])
+        o, op = _out(16 * max(count, 1))
+        _check(load().msm_bases_compute_subset_many_device(self._h or None, ctypes.byref(sub),
+                                                           ctypes.cast(ss, ctypes.c_void_p), count,
+                                                           _opts(window_size, run_length, -1, flags),
+                                                           _stream(stream, *tensors), op),
+               "msm_bases_compute_subset_many_device")
+        return o[:16 * count].reshape(count, 16)
+
     def close(self) -> None:
         """Free the records.  Closing twice is harmless."""
         h, self._h = self._h, 0
@@ -806,6 +923,17 @@ def _test_bases_plan(n: int, levels: int, window_size: int = 0) -> dict:
     o, op_ = _out(4)
     _check(load().msm_test_bases_plan(n, levels, window_size, op_), "msm_test_bases_plan")
     return dict(zip(("c", "windows", "chunk_bits", "points"), (int(v) for v in o)))
+
+
+def _test_subset_plan(n_handle: int, levels: int, window_size: int, first: int, m: int, indexed: bool) -> dict:
+    """The launch plan of one subset MSM of m terms on a handle of n_handle points (msm_test_subset_plan):
+    the terms the plan counts (d.n), whether its entries carry their fine key (packed), the record
+    stride, the fine bits fb, and the scatter variant (0 plain, 1 range, 2 indexed).  Applies the
+    argument rules that need no device (MsmError -1).  No device needed."""
+    o, op_ = _out(5)
+    _check(load().msm_test_subset_plan(n_handle, levels, window_size, first, m, 1 if indexed else 0, op_),
+           "msm_test_subset_plan")
+    return {"n": int(o[0]), "packed": int(o[1]), "stride": int(o[2]), "fb": int(o[3]), "sub": int(o[4])}
 
 
 def _test_bases_records(bases: "Bases", level: int) -> np.ndarray:
