@@ -13,7 +13,9 @@
  *                   coordinate must be < p (MSM_ERR_COORD_RANGE otherwise), but the MSM itself
  *                   uses only x, y and z -- d t is recomputed from the affine x y, as the oracle
  *                   (Aleo's msm over affine points) does, so an inconsistent t does not change it
- *   scalar        : 8 x uint32 big-endian = full 256-bit integer (not reduced mod r)
+ *   scalar        : 8 x uint32 big-endian = full 256-bit integer (not reduced mod r); the
+ *                   msm_bases_compute* entries also take narrow scalars of ceil(b / 32) words
+ *                   (MSM_FLAG_SCALAR_BITS below)
  *   result        : x | y affine = 16 x uint32; identity = (0, 1)
  */
 #ifndef MSM_MI355X_H
@@ -45,6 +47,7 @@ extern "C" {
 #define MSM_FLAG_DEVICES 2u /* the device-list fields (devices, n_devices) are set: see below     */
 #define MSM_FLAG_WINDOWS 4u /* the window-range fields (window_lo, window_hi) are set: see below  */
 #define MSM_FLAG_HALF_WINDOWS 8u /* with MSM_FLAG_WINDOWS: window_lo / window_hi count half windows */
+#define MSM_FLAG_SCALAR_BITS 16u /* scalar_bits is set: narrow scalars (msm_bases_compute* only, below) */
 
 #define MSM_MAX_DEVICES 16
 
@@ -75,7 +78,8 @@ typedef struct msm_opts {
   /* --- read only when flags & MSM_FLAG_DEVICES --- */
   const int32_t* devices; /* n_devices HIP ordinals                                                */
   uint32_t n_devices;
-  uint32_t reserved; /* 0 */
+  /* --- read only when flags & MSM_FLAG_SCALAR_BITS --- */
+  uint32_t scalar_bits; /* b, 1..256: every scalar is ceil(b / 32) words and below 2^b (below)        */
   /* --- read only when flags & MSM_FLAG_WINDOWS --- */
   uint32_t window_lo, window_hi; /* the MSM's windows [window_lo, window_hi) only (below)             */
 } msm_opts;
@@ -98,6 +102,39 @@ typedef struct msm_opts {
  * half, so a range may start or end in the middle of a window (an odd number of windows can be
  * cut into equal shares). */
 uint32_t msm_window_count(uint32_t window_bits);
+
+/* Narrow scalars (MSM_FLAG_SCALAR_BITS, b = scalar_bits, 1 <= b <= 256): a prover's witness and
+ * lookup columns hold booleans, bytes and 16/32/64-bit limbs, its folding challenges 128 bits.  With
+ * the flag every scalar vector of the call holds words = ceil(b / 32) u32 words per scalar, big-endian
+ * word order (index 0 most significant) as the 8-word format; the scalar is that integer, and its bits
+ * at and above b must be zero.  The result is the group element the same entry gives for those scalars
+ * zero-extended to 8 words.  The upload is `words` words per scalar, and for b <= 253 the launch runs
+ * windows balanced over the scalar's own bits: with the width c (window_bits; 0 = the size's usual
+ * choice, or 17 where that choice would put 64 entries or more into every bucket of so short a
+ * scalar) and T = max(b + 1, 4), W' = ceil(T / c) windows of floor(T / W') bits, the
+ * lowest T mod W' of them one bit wider -- 5 windows for b = 64 at c = 16 against the 17 of a 256-bit
+ * scalar.  For b >= 254 the call is the 8-word one as it is.
+ *
+ * Honoured by the eight msm_bases_compute* entries (the subset forms included: a subset picks the
+ * records, the width the digits; neither knows of the other).  Every other entry that takes msm_opts,
+ * msm_bases_create* included, returns MSM_ERR_INVALID_ARG when the flag is set, before any device work.
+ * b = 0 or b > 256 gives MSM_ERR_INVALID_ARG.  A caller of the 16-byte struct never sets the flag.
+ *
+ * A scalar with a bit set at or above b (possible only when b is not a multiple of 32) gives
+ * MSM_ERR_INVALID_ARG, by the rule of the subset indices: the host entries check every vector before
+ * anything is uploaded or enqueued; the device entries check on the device (b <= 253: the recode
+ * kernel masks the excess bits, so the launch runs to its end, and the entry then returns the error
+ * with its results unspecified; b = 254 and 255 run the 8-word launch, which takes the whole 256-bit
+ * integer and checks nothing).
+ *
+ * On a handle of levels > 1 a narrow call (b <= 253) runs UNFOLDED on the level-0 records -- they are
+ * plain prepared records -- so any window_bits is accepted, as on a levels = 1 handle.
+ * msm_profile_t.windows reports the launch's W'.
+ *
+ * Alignment: device scalar pointers (every *_device entry, 8-word and narrow alike) must be 16-byte
+ * aligned -- the kernels read scalars with 16-byte vector loads.  The narrow recode reads a vector
+ * that is only 4-byte aligned (a slice of a larger tensor at b <= 32, say) word by word instead, at
+ * a lower rate; host arrays need only their natural 4-byte alignment. */
 
 /* Per-phase device times (ms) of the most recent MSM on the calling thread's device when
  * profiling is enabled (hipEvents on the library's stream). */

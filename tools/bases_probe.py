@@ -27,6 +27,16 @@ each with the awaited call from host arrays and from device-resident ones and th
 over `count` MSMs, both ways, plus the per-phase device times of one profiled awaited call
 (msm_set_profiling(1)).
 
+With --narrow the pass is the narrow-scalar sweep of DESIGN.md §9 (MSM_FLAG_SCALAR_BITS): on a
+levels-1 handle of each size, for b in --narrow-bits (default 8,16,32,64,128,253) one line per way of
+computing the MSM of n random b-bit scalars:
+
+  {"entry": "narrow", "form": "extended", ...}   the existing entry on the scalars zero-extended to 8 words
+  {"entry": "narrow", "form": "narrow", "c": 0}  Bases.compute*(scalar_bits=b) at the auto width
+  {"entry": "narrow", "form": "narrow", "c": c}  the same at c in --narrow-widths (13..17 and 19)
+
+with the same four timings and the per-phase times of one profiled awaited call.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -232,6 +242,85 @@ def subset_pass(a):
     return 1 if bad else 0
 
 
+def narrow_pass(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import as_xy, closed_form
+
+    n, count, k0, step = a.n, a.count, 3, 5
+    bad = []
+
+    def emit(d):
+        d = {"n": n, **d}
+        if not d.get("correct", True):
+            bad.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    phases = ("recode_count", "coarse_scatter", "fine_sort", "accumulate", "bucket_reduce_1", "bucket_reduce_2",
+              "device_total")
+
+    def profile(fn):
+        M.set_profiling(1)
+        try:
+            fn()
+            p = M.last_profile()
+        finally:
+            M.set_profiling(0)
+        return {**{k: round(float(p[k]), 4) for k in phases}, "windows": int(p["windows"]), "c": int(p["window_bits"])}
+
+    def measure(row, exp, host1, dev1, host_many, dev_many):
+        ok = True
+        for key, fn, many in (("single_host", host1, False), ("single_device", dev1, False),
+                              ("pipelined_host", host_many, True), ("pipelined_device", dev_many, True)):
+            ms, runs, res = timed(fn, a.runs)
+            if many:
+                row[key + "_ms_per_msm"] = round(ms / count, 4)
+                ok = ok and [as_xy(r) for r in res] == [exp] * count
+            else:
+                row[key + "_ms"] = round(ms, 4)
+                ok = ok and res == exp
+            row[key + "_runs_ms"] = runs
+        row["phases_ms"] = profile(dev1)
+        row["correct"] = ok
+        emit(row)
+
+    pts = M.gen_points(n, k0=k0, step=step)
+    d_pts = dev(pts)
+    rnd = np.random.RandomState(29)
+    with M.Bases.from_device(d_pts, n, levels=1) as b:
+        for bits in a.narrow_bits:
+            words = (bits + 31) // 32
+            if bits == 253:
+                sc8 = M.gen_scalars(n, seed=700)  # canonical field elements: below 2^253
+            else:
+                sc8 = np.zeros((n, 8), np.uint32)
+                sc8[:, 8 - words:] = rnd.randint(0, 1 << 32, size=(n, words), dtype=np.uint64).astype(np.uint32)
+                if bits % 32:
+                    sc8[:, 8 - words] &= (1 << (bits % 32)) - 1
+            sc = np.ascontiguousarray(sc8[:, 8 - words:])
+            exp = closed_form(k0, step, sc8)
+            d_sc8, d_sc = dev(sc8), dev(sc)
+            base = {"entry": "narrow", "bits": bits, "words": words, "count": count}
+            measure({**base, "form": "extended"}, exp,
+                    lambda: b.compute(sc8), lambda: b.compute_device(d_sc8),
+                    lambda: b.compute_many([sc8] * count), lambda: b.compute_many_device([d_sc8] * count))
+            for c in [0] + list(a.narrow_widths):
+                kw = {"window_size": c or None, "scalar_bits": bits}
+                measure({**base, "form": "narrow", "c": c}, exp,
+                        lambda: b.compute(sc, **kw), lambda: b.compute_device(d_sc, **kw),
+                        lambda: b.compute_many([sc] * count, **kw),
+                        lambda: b.compute_many_device([d_sc] * count, **kw))
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=0, help="run this one size in-process")
@@ -243,6 +332,9 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--subset", action="store_true", help="the subset sweep (msm_bases_compute_subset*) instead")
     ap.add_argument("--subset-sizes", default="12,16,18,20", help="log2 term counts m of the subset sweep")
+    ap.add_argument("--narrow", action="store_true", help="the narrow-scalar sweep (MSM_FLAG_SCALAR_BITS) instead")
+    ap.add_argument("--narrow-bits", default="8,16,32,64,128,253", help="scalar widths b of the narrow sweep")
+    ap.add_argument("--narrow-widths", default="13,14,15,16,17,19", help="explicit window widths of the narrow sweep")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
@@ -255,6 +347,20 @@ def main():
                "--subset", "--subset-sizes", ",".join(map(str, a.subset_sizes)), "--count", str(a.count),
                "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
         return subprocess.run(cmd).returncode
+    if a.narrow:
+        a.narrow_bits = [int(x) for x in str(a.narrow_bits).split(",")]
+        a.narrow_widths = [int(x) for x in str(a.narrow_widths).split(",") if x]
+        if a.n:
+            return narrow_pass(a)
+        for lg in (int(x) for x in a.sizes.split(",")):
+            cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n",
+                   str(1 << lg), "--narrow", "--narrow-bits", ",".join(map(str, a.narrow_bits)), "--narrow-widths",
+                   ",".join(map(str, a.narrow_widths)), "--count", str(a.count), "--runs", str(a.runs)]
+            rc = subprocess.run(cmd + (["--out", a.out] if a.out else [])).returncode
+            if rc != 0:
+                print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)
+                return rc
+        return 0
     if a.n:
         return one_size(a)
     for lg in (int(x) for x in a.sizes.split(",")):

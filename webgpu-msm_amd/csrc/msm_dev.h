@@ -49,6 +49,14 @@ struct MsmDims {
   uint32_t rstride;  // records per level of the handle: its n
   uint32_t first;    // range form: the first base of the range
   uint32_t sm;       // terms per level: n / levels
+  // Narrow-scalar launches (msm_opts MSM_FLAG_SCALAR_BITS below 254 bits, msm_bases_compute*): the
+  // wire scalars are sw words of sbits value bits each, and the windows [0, Wm - 1) are balanced over
+  // T = max(sbits + 1, 4) bits by the same (q, nhi) rule.  Wm still counts an overflow window, but the
+  // launch's range [0, Wr = Wm - 1) never reaches it: win_bits / win_off, and so every kernel and
+  // the host Horner, see the narrow geometry with nothing else to tell them.  Both zero for every
+  // other launch (8-word scalars on the 254-bit geometry); only k_recode_narrow reads them.
+  uint32_t sw;       // u32 words per wire scalar, 1..8 (0: the 8-word format)
+  uint32_t sbits;    // value bits per scalar, 1..253: a set bit at or above it is an error
 };
 constexpr uint32_t MSM_SUB_NONE = 0, MSM_SUB_RANGE = 1, MSM_SUB_INDEXED = 2;
 
@@ -82,5 +90,12 @@ constexpr uint32_t KEY_PASS = 0x80000000u;
 constexpr uint32_t MSM_DEV_ERR_COORD_RANGE = 1u;  // a coordinate >= p (bytes.rs:19 panics)
 constexpr uint32_t MSM_DEV_ERR_BAD_POINT = 2u;    // z == 0
 constexpr uint32_t MSM_DEV_ERR_BAD_INDEX = 4u;    // a subset's base index >= the handle's n (k_stage_indices)
+constexpr uint32_t MSM_DEV_ERR_SCALAR_RANGE = 8u; // a narrow scalar with a bit at or above sbits (k_recode_narrow)
+
+// k_recode_narrow's bias (kernel argument, by value): C = sum_w (2^(b_w - 1) - 1) 2^off_w over the
+// narrow geometry's windows, little-endian words (narrow_bias builds it on the host).
+struct NarrowBias {
+  uint32_t v[8];
+};
 
 }  // namespace msm

@@ -145,7 +145,7 @@ bool plan_eq(const Plan& a, const Plan& b) {
          x.nm == y.nm && x.q == y.q &&
          x.nhi == y.nhi && x.fb == y.fb && x.nbc == y.nbc && x.nbins == y.nbins && x.ch == y.ch && x.nch == y.nch &&
          x.packed == y.packed && x.shared == y.shared && x.sub == y.sub && x.rstride == y.rstride &&
-         x.first == y.first && x.sm == y.sm && a.K == b.K && a.L == b.L &&
+         x.first == y.first && x.sm == y.sm && x.sw == y.sw && x.sbits == y.sbits && a.K == b.K && a.L == b.L &&
          a.nchunks == b.nchunks && a.nv == b.nv && a.nterms == b.nterms && a.Mmax == b.Mmax &&
          a.runs_max == b.runs_max && a.pfmt == b.pfmt;
 }
@@ -430,7 +430,9 @@ uint32_t run_length_skew_floor(const MsmDims& d) {
     const uint32_t w = d.w0 + l;
     if (w + 1 >= d.Wm) continue;  // the overflow window: empty for canonical scalars
     double vals = (double)(1u << (win_bits(d, w) - 1));
-    if (w + 2 == d.Wm) {  // the top main window: digits below (p >> off) + 1
+    // (a narrow launch's top window holds 2^(width - 1) values like the others: its top bit is
+    // clear, and so are its negative digits)
+    if (w + 2 == d.Wm && !d.sw) {  // the top main window: digits below (p >> off) + 1
       const uint32_t off = win_off(d, w);
       const double top = off >= 192 ? (double)(P[3] >> (off - 192)) + 1.0 : vals;
       vals = std::min(vals, top);
@@ -497,6 +499,8 @@ struct SubsetGeo {
   size_t first = 0;  // range form
 };
 
+constexpr uint32_t NARROW_WIDE_C = 17, NARROW_DENSE = 64;  // the narrow launches' auto width (make_plan)
+
 int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined = false, uint32_t nm = 1,
               bool shared = false, const SubsetGeo* sub = nullptr) {
   *pl = Plan{};
@@ -515,6 +519,38 @@ int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pi
   d.w0 = 0;
   d.Wr = d.Wm;
   d.half_lo = d.half_hi = 0;
+  if (o && (o->flags & MSM_FLAG_SCALAR_BITS)) {
+    // Narrow scalars (msm_bases_compute* only; every other entry has refused the flag): below 254
+    // bits the windows are balanced over the scalar's own T = max(b + 1, 4) bits -- one bit more
+    // than the scalar has, so the top window's top bit is clear, its value plus the carry is at
+    // most 2^(width - 1) and nothing carries out.  Wm keeps counting an overflow window that the
+    // range [0, Wm - 1) leaves out (msm_dev.h).  254 bits and more are the 8-word launch as it is.
+    const uint32_t b = o->scalar_bits;
+    if (b < 1 || b > 256 || (o->flags & MSM_FLAG_WINDOWS)) return MSM_ERR_INVALID_ARG;
+    if (b < MAIN_BITS) {
+      const uint32_t T = std::max(b + 1, 4u);
+      auto widest = [&](uint32_t cw) { return (T + (T + cw - 1) / cw - 1) / ((T + cw - 1) / cw); };
+      // The auto width: a short scalar balanced at the size's usual width may end up with a few
+      // narrow windows whose buckets hold hundreds of entries each (b = 16 at c = 16 is 9 + 8 bits:
+      // 4,096 entries per bucket at 2^20, 9.89 ms against 0.26 ms as one 17-bit window).  From
+      // NARROW_DENSE entries per bucket of the widest window the launch takes NARROW_WIDE_C = 17
+      // where that widens the windows: profiles/bases_narrow_sweep.jsonl, every (n, b) row at that
+      // density or more is faster at c = 17 awaited and within 0.004 ms pipelined (2^20, b = 64: 0.41
+      // against 0.63 ms; b = 128: 0.63 against 0.77), the rows at 16 per bucket are not (2^16, b = 128:
+      // 0.110 against 0.070 ms per MSM pipelined), and c = 19 triples the reduction (same file,
+      // b = 128: 0.234 + 0.133 against 0.076 + 0.047 ms).
+      if (!o->window_bits && c < NARROW_WIDE_C && ((uint64_t)n >> (widest(c) - 1)) >= NARROW_DENSE &&
+          widest(NARROW_WIDE_C) > widest(c))
+        c = NARROW_WIDE_C;
+      const uint32_t wn = (T + c - 1) / c;
+      d.q = T / wn;
+      d.nhi = T - d.q * wn;
+      d.Wm = wn + 1;
+      d.Wr = wn;
+      d.sw = (b + 31) / 32;
+      d.sbits = b;
+    }
+  }
   if (o && (o->flags & MSM_FLAG_WINDOWS)) {
     // a window range needs an explicit width, so that every caller's ranges cut the same windows
     const uint32_t units = (o->flags & MSM_FLAG_HALF_WINDOWS) ? 2u : 1u;
@@ -715,9 +751,52 @@ void launch_recode_fixed(const MsmDims& d, const BatchPtrs& sc, void* digits, ui
     hipLaunchKernelGGL((k_recode_fixed<Q, NHI, false>), grid, dim3(RC_THREADS), lds, s, sc, d,
                        static_cast<uint16_t*>(digits), colsum);
 }
-void launch_recode(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, hipStream_t s) {
+// The narrow recode (MsmDims::sw): one k_recode_narrow instantiation per scalar word count and code
+// width, and its bias C = sum_w (2^(b_w - 1) - 1) 2^off_w over the launch's windows (the sum stays
+// below 2^(T - 1), so it fits the scalar's own words).
+template <typename T>
+const void* recode_narrow_fn(uint32_t sw) {
+  switch (sw) {
+    case 1: return reinterpret_cast<const void*>(&k_recode_narrow<T, 1>);
+    case 2: return reinterpret_cast<const void*>(&k_recode_narrow<T, 2>);
+    case 3: return reinterpret_cast<const void*>(&k_recode_narrow<T, 3>);
+    case 4: return reinterpret_cast<const void*>(&k_recode_narrow<T, 4>);
+    case 5: return reinterpret_cast<const void*>(&k_recode_narrow<T, 5>);
+    case 6: return reinterpret_cast<const void*>(&k_recode_narrow<T, 6>);
+    case 7: return reinterpret_cast<const void*>(&k_recode_narrow<T, 7>);
+    default: return reinterpret_cast<const void*>(&k_recode_narrow<T, 8>);
+  }
+}
+const void* recode_narrow_kernel(const MsmDims& d) {
+  return d.c > 16 ? recode_narrow_fn<uint32_t>(d.sw) : recode_narrow_fn<uint16_t>(d.sw);
+}
+NarrowBias narrow_bias(const MsmDims& d) {
+  NarrowBias nb{};
+  for (uint32_t w = 0; w < d.Wr; w++) {
+    const uint64_t h = (1ull << (win_bits(d, w) - 1)) - 1ull;  // < 2^20: spans at most two words
+    const uint32_t o = win_off(d, w), k = o / 32, sh = o % 32;
+    uint64_t carry = h << sh;
+    for (uint32_t j = k; j < 8 && carry; j++) {
+      const uint64_t x = (uint64_t)nb.v[j] + (carry & 0xffffffffull);
+      nb.v[j] = (uint32_t)x;
+      carry = (carry >> 32) + (x >> 32);
+    }
+  }
+  return nb;
+}
+
+void launch_recode(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
+                   hipStream_t s) {
   const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
   const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;  // histogram + window totals
+  if (d.sw) {
+    BatchPtrs scal = sc;
+    MsmDims dd = d;
+    NarrowBias nb = narrow_bias(d);
+    void* args[] = {&scal, &dd, &digits, &colsum, &nb, &err};
+    (void)hipLaunchKernel(recode_narrow_kernel(d), grid, dim3(RC_THREADS), args, lds, s);
+    return;
+  }
   if (d.c > 16) {
     hipLaunchKernelGGL(k_recode_hist<uint32_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint32_t*>(digits),
                        colsum);
@@ -745,6 +824,9 @@ bool is_recode_kernel(const void* f) {
                       reinterpret_cast<const void*>(&k_recode_fixed<12, 14, false>)};
   for (const void* k : ks)
     if (f == k) return true;
+  // the narrow recodes too: a replayed graph must not read the previous call's scalars
+  for (uint32_t sw = 1; sw <= 8; sw++)
+    if (f == recode_narrow_fn<uint16_t>(sw) || f == recode_narrow_fn<uint32_t>(sw)) return true;
   return false;
 }
 
@@ -790,7 +872,7 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
       mark(PH_START);
       mark(PH_PREPARE);
     }
-    launch_recode(d, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), s);
+    launch_recode(d, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), w.err.as<uint32_t>(), s);
     mark(PH_RECODE);
     mark(PH_SCAN);
     if (d.sub != MSM_SUB_NONE) {
@@ -1576,7 +1658,10 @@ int repoint_inputs(const Plan& pl, Slot& sl, Segment& sg, const BatchPtrs& d_poi
     MsmDims dd = d;
     void* digits = w.digits.p;
     uint32_t* hist = w.colsum.as<uint32_t>();
-    void* a_rc[] = {&scal, &dd, &digits, &hist};
+    // (k_recode_narrow takes two more arguments; the other recodes read the first four)
+    NarrowBias nb = d.sw ? narrow_bias(d) : NarrowBias{};
+    uint32_t* err = w.err.as<uint32_t>();
+    void* a_rc[] = {&scal, &dd, &digits, &hist, &nb, &err};
     hipKernelNodeParams kr = sg.p_recode;
     kr.kernelParams = a_rc;
     kr.extra = nullptr;
@@ -1729,6 +1814,7 @@ int wait_slot(DevCtx* c, int si, uint32_t* total_out = nullptr) {
   if (err & MSM_DEV_ERR_COORD_RANGE) return MSM_ERR_COORD_RANGE;
   if (err & MSM_DEV_ERR_BAD_POINT) return MSM_ERR_BAD_POINT;
   if (err & MSM_DEV_ERR_BAD_INDEX) return MSM_ERR_INVALID_ARG;  // a device-entry subset's index >= n
+  if (err & MSM_DEV_ERR_SCALAR_RANGE) return MSM_ERR_INVALID_ARG;  // a narrow scalar's bit at or above scalar_bits
   return MSM_OK;
 }
 
@@ -2126,6 +2212,12 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
   Plan pl;
   int rc = make_plan(np, o, c->shape, &pl, count > 1, nm, shared, &sg);
   if (rc != MSM_OK) return rc;
+  // Words per wire scalar (a narrow launch on a handle: pl.d.sw, else 8) and the words between the
+  // MSMs' scalars in a slot's wire buffer: a narrow MSM's vector is padded to whole 16-B units so
+  // that every MSM's scalars start aligned for k_recode_narrow's vector loads.
+  const bool narrow = pl.d.sw != 0;
+  const size_t sw = narrow ? pl.d.sw : 8;
+  const size_t scs = narrow ? (n * sw + 3) & ~(size_t)3 : n * 8;
   // host inputs: one more launch in flight, so its upload queues behind the running ones
   // (2^20 msm_compute 4.21 -> 4.05 ms with three, profiles/r2t_*; device inputs are best with two)
   const int want = pipeline_slots(n, o) + (host && !(o && (o->flags & MSM_FLAG_SERIAL)) && !getenv("MSM_SLOTS") ? 1 : 0);
@@ -2138,7 +2230,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     if (host) {
       Workspace& w = c->slot[si].ws;
       if ((!shared && (rc = w.wire_pts.ensure((size_t)nm * n * 128)) != MSM_OK) ||
-          (rc = w.wire_sc.ensure((size_t)nm * n * 32)) != MSM_OK)
+          (rc = w.wire_sc.ensure((size_t)nm * scs * 4)) != MSM_OK)
         return rc;
     }
   }
@@ -2180,7 +2272,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
       bs->p[m] = in.scalars[b];
       if (host) {  // padding MSMs of a short last launch read the last real MSM's wire buffers
         const uint32_t mr = std::min<uint32_t>(m, nreal - 1);
-        bs->p[m] = in.dev_scalars ? in.dev_scalars[j * nm + mr] : sl.ws.wire_sc.as<uint32_t>() + (size_t)mr * n * 8;
+        bs->p[m] = in.dev_scalars ? in.dev_scalars[j * nm + mr] : sl.ws.wire_sc.as<uint32_t>() + (size_t)mr * scs;
         if (!shared)
           bp->p[m] = in.dev_points ? in.dev_points[j * nm + mr] : sl.ws.wire_pts.as<uint32_t>() + (size_t)mr * n * 32;
       }
@@ -2266,12 +2358,14 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
       HIPCHECK(hipEventRecord(c->up_ev[2 * j + 1], c->copy_stream));
       return MSM_OK;
     }
-    auto up = [&](const uint32_t* const* src, const BatchPtrs& dst, size_t per) -> bool {
+    // (`stride`: words between the MSMs' regions in the slot's buffer; adjacent host arrays go up in
+    // one copy only where the regions are adjacent too)
+    auto up = [&](const uint32_t* const* src, const BatchPtrs& dst, size_t per, size_t stride) -> bool {
       for (uint32_t m0 = 0; m0 < nreal;) {
         const size_t b0 = std::min(j * nm + m0, count - 1);
         const uint32_t* h0 = src[b0];
         uint32_t m1 = m0 + 1;
-        if (len_of(b0) == n)
+        if (len_of(b0) == n && stride == n * per)
           while (m1 < nreal && len_of(j * nm + m1) == n && src[j * nm + m1] == h0 + (size_t)(m1 - m0) * n * per) m1++;
         const size_t words = (m1 - m0 == 1 ? len_of(b0) : (size_t)(m1 - m0) * n) * per;
         if (words && hipMemcpyAsync(const_cast<uint32_t*>(dst.p[m0]), h0, words * 4, hipMemcpyHostToDevice,
@@ -2281,7 +2375,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
       }
       return true;
     };
-    if (!in.dev_scalars && !up(in.scalars, bs, 8)) return MSM_ERR_HIP;
+    if (!in.dev_scalars && !up(in.scalars, bs, sw, scs)) return MSM_ERR_HIP;
     if (indexed) {
       // the launch's index vectors into the slot's own buffer (validated by the entry: no kernel);
       // the padding MSMs of a short last launch repeat the last real MSM's, as they do its scalars
@@ -2302,7 +2396,7 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     }
     HIPCHECK(hipEventRecord(c->up_ev[2 * j], c->copy_stream));
     scalars_done();
-    if (!shared && !up(in.points, bp, 32)) return MSM_ERR_HIP;
+    if (!shared && !up(in.points, bp, 32, n * 32)) return MSM_ERR_HIP;
     HIPCHECK(hipEventRecord(c->up_ev[2 * j + 1], c->copy_stream));
     return MSM_OK;
   };
@@ -2357,7 +2451,8 @@ int run_many(DevCtx* c, const ManyInputs& in, size_t n, size_t count, const msm_
     // An indexed subset fails at run time (MSM_DEV_ERR_BAD_INDEX) with other launches in flight:
     // each of those is waited for as usual, so that a skewed one still gets its second reduction,
     // which is what clears its slot's skew flags for the next call.
-    if (indexed && !host)
+    // (and so does a narrow launch whose scalars had excess bits, MSM_DEV_ERR_SCALAR_RANGE)
+    if ((indexed || narrow) && !host)
       for (size_t j = finished; j < enqueued.load(); j++) (void)wait_slot(c, (int)(j % nslot));
     return code;
   };
@@ -2717,6 +2812,9 @@ int many_entry(const ManyInputs& in, size_t n, size_t count, const msm_opts* opt
 // host thread each, and the join is projective (one EC add per shard, one inversion at the end).
 
 bool devices_listed(const msm_opts* o) { return o && (o->flags & MSM_FLAG_DEVICES); }
+// MSM_FLAG_SCALAR_BITS belongs to the msm_bases_compute* entries: every other entry refuses it
+// before it touches a device (their scalars are the 8-word format).
+bool narrow_flagged(const msm_opts* o) { return o && (o->flags & MSM_FLAG_SCALAR_BITS); }
 
 // The listed ordinals, checked for shape (non-null, 1..MSM_MAX_DEVICES entries, non-negative,
 // distinct) before any device is touched, then for being gfx950 devices.
@@ -2801,6 +2899,7 @@ int sharded_host(const uint32_t* points_be, const uint32_t* scalars_be, size_t n
 }
 
 int multi_host_entry(const uint32_t* points_be, const uint32_t* scalars_be, size_t n, const msm_opts* opts, Pt* r) {
+  if (narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
   if (!devices_listed(opts)) return host_entry(points_be, scalars_be, n, opts, r);
   if ((!points_be || !scalars_be) && n) return MSM_ERR_INVALID_ARG;
   std::vector<int> devs;
@@ -2896,6 +2995,7 @@ int sharded_device(const uint32_t* d_points_be, const uint32_t* d_scalars_be, si
 
 int multi_device_entry(const uint32_t* d_points_be, const uint32_t* d_scalars_be, size_t n, const msm_opts* opts,
                        void* hip_stream, Pt* r) {
+  if (narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
   if (!devices_listed(opts)) return device_entry(d_points_be, d_scalars_be, n, opts, hip_stream, r);
   if ((!d_points_be || !d_scalars_be) && n) return MSM_ERR_INVALID_ARG;
   std::vector<int> devs;
@@ -2907,6 +3007,7 @@ int multi_device_entry(const uint32_t* d_points_be, const uint32_t* d_scalars_be
 // (whole MSMs, nothing to join).  Device batches take one device.
 int multi_many_entry(const ManyInputs& in, size_t n, size_t count, const msm_opts* opts, void* hip_stream,
                      uint32_t* out, bool projective) {
+  if (narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
   if (!devices_listed(opts)) return many_entry(in, n, count, opts, hip_stream, out, projective);
   if (in.kind != ManyInputs::HOST) return MSM_ERR_INVALID_ARG;
   if (!out || (!in.scalars && count) || (!in.points && !in.shared_points && count)) return MSM_ERR_INVALID_ARG;
@@ -3015,7 +3116,7 @@ int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* op
                  hipStream_t user_stream, msm_bases** out) {
   if (!out) return MSM_ERR_INVALID_ARG;
   *out = nullptr;
-  if ((!points && n) || levels > 8 || !bases_flags_ok(opts)) return MSM_ERR_INVALID_ARG;
+  if ((!points && n) || levels > 8 || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
   const uint32_t wb = opts ? opts->window_bits : 0;
   if (wb && (wb < 4 || wb > 20)) return MSM_ERR_UNSUPPORTED_WINDOW;
   if (!levels) levels = bases_auto_levels(n);
@@ -3119,8 +3220,15 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   if (!b) return MSM_ERR_INVALID_ARG;
   const bool indexed = sub && sub->indices;
   const size_t terms = sub ? (size_t)sub->m : b->n;  // scalars per vector
+  // Narrow scalars (MSM_FLAG_SCALAR_BITS): below 254 bits the call runs unfolded on the level-0
+  // records, whatever the handle's levels -- they are plain prepared records -- over the scalars'
+  // own geometry (make_plan); 254 bits and more are the 8-word call as it is.
+  const uint32_t sbits = narrow_flagged(opts) ? opts->scalar_bits : 256;
+  if (sbits < 1 || sbits > 256) return MSM_ERR_INVALID_ARG;
+  const bool narrow = sbits < MAIN_BITS;
+  const uint32_t levels = narrow ? 1u : b->levels;
   if (sub) {
-    if (int rc = subset_check(b->n, b->levels, sub->first, sub->m, indexed)) return rc;
+    if (int rc = subset_check(b->n, levels, sub->first, sub->m, indexed)) return rc;
     for (size_t k = 0; indexed && terms && k < count; k++) {
       const uint32_t* ix = sub->indices[k];
       if (!ix) return MSM_ERR_INVALID_ARG;
@@ -3137,7 +3245,11 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   o.flags = opts ? (opts->flags & MSM_FLAG_SERIAL) : 0;
   o.device = b->device;
   o.window_bits = opts ? opts->window_bits : 0;
-  if (b->levels > 1) {
+  if (narrow) {
+    o.flags |= MSM_FLAG_SCALAR_BITS;
+    o.scalar_bits = sbits;
+  }
+  if (levels > 1) {
     if (o.window_bits && o.window_bits != b->window_bits) return MSM_ERR_INVALID_ARG;
     o.window_bits = b->window_bits;
     o.flags |= MSM_FLAG_WINDOWS;
@@ -3147,16 +3259,40 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   if (count == 0) return MSM_OK;
   for (size_t k = 0; k < count; k++)
     if (!scalars[k] && terms) return MSM_ERR_INVALID_ARG;
+  // A bit at or above scalar_bits: host vectors are checked on the host, before anything is uploaded
+  // or enqueued (the device entries' by k_recode_narrow); only the most significant word can hold
+  // one.  Large vectors go over the device context's parked packing threads (the strided read of
+  // 2^20 8-word scalars is ~0.5 ms on one thread); a vector given again is checked once.
+  auto host_scalars_ok = [&](DevCtx* c) -> bool {
+    if (!host || sbits == 256 || !(sbits & 31u)) return true;
+    const size_t sw = (sbits + 31) / 32;
+    const uint32_t excess = ~((1u << (sbits & 31u)) - 1u);
+    for (size_t k = 0; k < count; k++) {
+      if (k && scalars[k] == scalars[k - 1]) continue;
+      const uint32_t* v = scalars[k];
+      std::atomic<uint32_t> any{0};
+      auto scan = [&](int t, int nt) {
+        uint32_t a = 0;
+        for (size_t i = terms * t / nt, e = terms * (t + 1) / nt; i < e; i++) a |= v[i * sw];
+        any.fetch_or(a);
+      };
+      if (terms >= (1u << 17)) ctx_packer(c)->run(scan);
+      else scan(0, 1);
+      if (any.load() & excess) return false;
+    }
+    return true;
+  };
   return on_device(&o, [&](DevCtx* c) -> int {
     if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    if (!host_scalars_ok(c)) return MSM_ERR_INVALID_ARG;
     ManyInputs in;
     in.kind = host ? ManyInputs::HOST : ManyInputs::DEVICE;
     in.scalars = scalars;
     in.prepared = b->rec.as<uint32_t>();
-    in.levels = b->levels;
+    in.levels = levels;
     in.chunk_bits = b->geo.S;
     if (sub) {
-      in.sub = subset_kind(b->levels, sub->first, indexed);
+      in.sub = subset_kind(levels, sub->first, indexed);
       in.sub_first = (size_t)sub->first;
       in.rec_n = b->n;
       in.indices = sub->indices;
@@ -3320,7 +3456,7 @@ int msm_compute_cocompute(const uint32_t* points_be, const uint32_t* scalars_be,
   if (!out_xy_be || ((!points_be || !scalars_be) && n) || !(cpu_work_ratio >= 0.0)) return MSM_ERR_INVALID_ARG;
   // a window range has no CPU counterpart (the host Pippenger computes every window): joining a
   // range's GPU share with a whole CPU share would be silently wrong
-  if (opts && (opts->flags & MSM_FLAG_WINDOWS)) return MSM_ERR_INVALID_ARG;
+  if (opts && (opts->flags & (MSM_FLAG_WINDOWS | MSM_FLAG_SCALAR_BITS))) return MSM_ERR_INVALID_ARG;
   // cpuShare = floor(cpuWorkRatio * n) (submission.ts:98); >= n is the reference's CPU-only branch
   const double share_d = cpu_work_ratio * (double)n;
   const size_t share = share_d >= (double)n ? n : (size_t)share_d;
@@ -3982,6 +4118,23 @@ int msm_test_bases_plan(size_t n, uint32_t levels, uint32_t window_bits, uint32_
   out[1] = g.Wc;
   out[2] = g.S;
   out[3] = (uint32_t)(n * levels);
+  return MSM_OK;
+}
+
+// The geometry of one narrow-scalar MSM (MSM_FLAG_SCALAR_BITS) of n terms at width window_bits (0:
+// the lone launch's auto width for n): out = {widest window c, windows in the launch W', base width
+// q, windows of q + 1 bits nhi, words per wire scalar, d.packed}.  254 bits and more report the plain
+// launch (Wr counts its overflow window; 8 words).  Host code only.
+int msm_test_narrow_plan(size_t n, uint32_t scalar_bits, uint32_t window_bits, uint32_t out[6]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  msm_opts op{};
+  op.window_bits = window_bits;
+  op.flags = MSM_FLAG_SCALAR_BITS;
+  op.scalar_bits = scalar_bits;
+  Plan pl;
+  if (int rc = make_plan(n, &op, DevShape{}, &pl, false, 1, true)) return rc;
+  const uint32_t v[6] = {pl.d.c, pl.d.Wr, pl.d.q, pl.d.nhi, pl.d.sw ? pl.d.sw : 8u, pl.d.packed};
+  memcpy(out, v, sizeof(v));
   return MSM_OK;
 }
 

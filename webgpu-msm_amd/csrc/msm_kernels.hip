@@ -7,7 +7,9 @@
 //                      ((y-x)/2, (y+x)/2, d t) in 29-bit Montgomery limbs, 128 B (one cache line)
 //   k_recode_hist      signed c-bit digits per scalar (window-carry recoding, |d| <= 2^(c-1)),
 //                      written window-major (= first sort level: one contiguous array per window),
-//                      with the coarse-bin totals (LDS histogram, flushed with global atomics)
+//                      with the coarse-bin totals (LDS histogram, flushed with global atomics);
+//                      k_recode_narrow is the same for scalars of 1..8 words over the windows of
+//                      their own bits (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
 //   k_part_scatter     digits -> coarse bins (each chunk reserves and writes one contiguous slice
 //                      per bin); its range / indexed variants map a subset launch's positions to
 //                      a handle's records (k_stage_indices checks a device caller's indices first)
@@ -761,6 +763,112 @@ __global__ void __launch_bounds__(RC_THREADS, 8) k_recode_fixed(BatchPtrs scalar
   PROBE(0, pwg, 2);
   flush_hist(lds_hist, d, w0, colsum);
   PROBE(0, pwg, 7);
+}
+
+// Narrow scalars (MsmDims::sw words of MsmDims::sbits bits each, big-endian words like the 8-word
+// format) over the launch's own balanced geometry: windows [0, d.Wr) of q + 1 / q bits that sum to
+// T = max(sbits + 1, 4) bits, no overflow window.  The bias-add form of k_recode_fixed with the
+// geometry at run time: t = s + C (C from the host, NarrowBias) makes the windows independent, and
+// since the widths sum to more than sbits the top window's top bit is clear before the add, so t
+// < 2^T and nothing carries out.  t is SW + 1 words (T may be 32 SW + 1) and is shifted down one
+// window at a time -- SW funnel shifts by a uniform amount per window, which is what a run-time
+// geometry costs without indexing the register array dynamically (see `recode`).
+// A lane takes R adjacent scalars (16 or 32 B at one or two words each, so a wave's loads are whole
+// cache lines; two scalars at three words and more) as vector loads where the MSM's scalar
+// pointer is 16-B aligned, and stores their 16-bit codes in pairs as k_recode_fixed does.
+// Bits at or above sbits are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE in the slot's err
+// word), so the digits stay inside their windows and the launch runs to its end.
+template <typename T, uint32_t SW>
+__global__ void __launch_bounds__(RC_THREADS) k_recode_narrow(BatchPtrs scalar_sets, MsmDims d,
+                                                              T* __restrict__ digits, uint32_t* __restrict__ colsum,
+                                                              NarrowBias bias, uint32_t* __restrict__ err) {
+  using DC = DigitCode<T>;
+  constexpr uint32_t R = SW <= 2 ? 4 : 2;  // scalars per lane
+  constexpr uint32_t LW = R * SW;          // words per lane
+  extern __shared__ uint32_t lds_hist[];   // [Wr][nbc]
+  const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
+  const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
+  const uint32_t w0 = blockIdx.y * d.Wr;
+  const uint32_t nh = d.Wr * d.nbc;
+  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
+  // value bits of the most significant word
+  const uint32_t top_mask = (d.sbits & 31u) ? (1u << (d.sbits & 31u)) - 1u : 0xffffffffu;
+  const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
+  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
+  bool bad = false;
+  __syncthreads();
+  for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
+    const uint32_t cnt = min(R, hi - i);
+    uint32_t raw[LW];
+    const uint32_t* p = scalars + (size_t)i * SW;
+    if (cnt == R && vec) {
+      // lane runs are LW * 4 bytes apart: 16-B aligned when LW is a multiple of 4, else 8-B
+      if (LW % 4 == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < LW / 4; k++) {
+          const uint4 v = reinterpret_cast<const uint4*>(p)[k];
+          raw[4 * k] = v.x, raw[4 * k + 1] = v.y, raw[4 * k + 2] = v.z, raw[4 * k + 3] = v.w;
+        }
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < LW / 2; k++) {
+          const uint2 v = reinterpret_cast<const uint2*>(p)[k];
+          raw[2 * k] = v.x, raw[2 * k + 1] = v.y;
+        }
+      }
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < LW; k++) raw[k] = k < cnt * SW ? p[k] : 0u;
+    }
+    uint32_t t[R][SW + 1];
+#pragma unroll
+    for (uint32_t r = 0; r < R; r++) {
+      bad = bad || (raw[r * SW] & ~top_mask) != 0;
+      raw[r * SW] &= top_mask;
+      uint32_t cy = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < SW; k++) {  // big-endian words: raw[r SW] is the most significant
+        const uint64_t x = (uint64_t)raw[r * SW + SW - 1 - k] + bias.v[k] + cy;
+        t[r][k] = (uint32_t)x;
+        cy = (uint32_t)(x >> 32);
+      }
+      t[r][SW] = cy;
+    }
+    T* row = digits + (size_t)w0 * d.n + i;
+    uint32_t* h = lds_hist;
+    for (uint32_t w = 0; w < d.Wr; w++) {
+      const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
+      const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
+      const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
+      uint32_t code[R];
+#pragma unroll
+      for (uint32_t r = 0; r < R; r++) {
+        const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
+#pragma unroll
+        for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
+        t[r][SW] >>= b;
+        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+        const bool live = digit != 0 && r < cnt;
+        // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
+        atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
+        code[r] = live ? mag | (digit < 0 ? DC::SIGN : 0u) : DC::ZERO;
+      }
+#pragma unroll
+      for (uint32_t r = 0; r < R; r += 2) {
+        if (pair_store && r + 1 < cnt) {
+          *reinterpret_cast<uint32_t*>(row + r) = code[r] | code[r + 1] << 16;
+        } else {
+          if (r < cnt) row[r] = (T)code[r];
+          if (r + 1 < cnt) row[r + 1] = (T)code[r + 1];
+        }
+      }
+      row += d.n;
+      h += d.nbc;
+    }
+  }
+  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  __syncthreads();
+  flush_hist(lds_hist, d, w0, colsum);
 }
 
 // k_fine_sort geometry

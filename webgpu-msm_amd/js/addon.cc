@@ -28,7 +28,8 @@
 // addon's enumerable surface):
 //   prepareBases(points: Uint32Array(32n), levels?, windowSize?) -> { id, n, levels, windowSize, bytes }
 //   computeMsmPrepared(id, scalars: Uint32Array(8n)) -> Promise<Uint32Array(16)>
-//   computeMsmPrepared(id, scalars: Uint32Array(8m), first?: number, indices?: Uint32Array(m))
+//   computeMsmPrepared(id, scalars: Uint32Array(8m), first?: number, indices?: Uint32Array(m),
+//                      scalarBits?: number)   (scalarBits = b: ceil(b / 32) words per scalar)
 //       over a subset of the bases: the range [first, first + m), or bases indices[0..m)
 //   releaseBases(id) -> number (0 ok, -1 for a handle already released)
 //   Handles left open are freed by the cleanup hook's msm_shutdown.
@@ -123,6 +124,7 @@ struct Job {
   bool subset = false, indexed = false;
   uint64_t first = 0;
   std::vector<uint32_t> indices;
+  uint32_t scalar_bits = 0;  // computeMsmPrepared: narrow scalars (MSM_FLAG_SCALAR_BITS); 0 = the 8-word format
   uint32_t out[16] = {0};
   int rc = 0;
 };
@@ -140,17 +142,24 @@ void execute(napi_env, void* data) {
   }
   const uint32_t* pts = j->p_points ? j->p_points : j->stage ? j->stage->points.data() : j->points.data();
   const uint32_t* sc = j->p_scalars ? j->p_scalars : j->stage ? j->stage->scalars.data() : j->scalars.data();
+  msm_opts ob;  // the handle entries' options: the scalars' width only
+  memset(&ob, 0, sizeof(ob));
+  ob.device = -1;
+  if (j->scalar_bits) {
+    ob.flags = MSM_FLAG_SCALAR_BITS;
+    ob.scalar_bits = j->scalar_bits;
+  }
   if (j->bases && j->subset) {
     const uint32_t* ix = j->indices.data();
     msm_subset_t sub;
     sub.first = j->first;
     sub.m = j->n;
     sub.indices = j->indexed ? &ix : nullptr;
-    j->rc = msm_bases_compute_subset(j->bases, &sub, sc, nullptr, j->out);
+    j->rc = msm_bases_compute_subset(j->bases, &sub, sc, &ob, j->out);
     return;
   }
   if (j->bases) {
-    j->rc = msm_bases_compute(j->bases, sc, nullptr, j->out);
+    j->rc = msm_bases_compute(j->bases, sc, &ob, j->out);
     return;
   }
   j->rc = j->cpu_work_ratio != 0 ? msm_compute_cocompute(pts, sc, j->n, &o, j->cpu_work_ratio, 0, j->out)
@@ -543,10 +552,11 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
 
 // computeMsmPrepared(id, scalars[, first, indices]): with `first` (a number) or `indices` (a
 // Uint32Array) the MSM runs over a subset of the handle's bases and the scalar array gives its
-// length (msm_bases_compute_subset); with neither (absent or undefined) over all of them.
+// length (msm_bases_compute_subset); with neither (absent or undefined) over all of them.  With
+// `scalarBits` = b (1..256) the scalars are narrow: ceil(b / 32) words each (MSM_FLAG_SCALAR_BITS).
 napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 5;
+  napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   const uint32_t* sc;
   size_t slen;
@@ -556,33 +566,38 @@ napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
     napi_valuetype vt = napi_undefined;
     return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
   };
-  const bool has_first = given(2), has_idx = given(3);
-  double first = 0;
+  const bool has_first = given(2), has_idx = given(3), has_bits = given(4);
+  double first = 0, bits = 0;
   const uint32_t* ix = nullptr;
   size_t ilen = 0;
   if (argc < 2 || !h || !get_u32_array(env, argv[1], &sc, &slen, &sshared) ||
       (has_first && (napi_get_value_double(env, argv[2], &first) != napi_ok || !(first >= 0) ||
                      first > 9007199254740992.0 || first != (double)(uint64_t)first)) ||
-      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen))) {
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen)) ||
+      (has_bits && (napi_get_value_double(env, argv[4], &bits) != napi_ok || bits != (double)(uint32_t)bits))) {
     napi_throw_type_error(env, nullptr,
-                          "computeMsmPrepared(id: number, scalars: Uint32Array, first?: number, indices?: Uint32Array)");
+                          "computeMsmPrepared(id: number, scalars: Uint32Array, first?: number, indices?: Uint32Array, "
+                          "scalarBits?: number)");
     return nullptr;
   }
+  if (has_bits && (bits < 1 || bits > 256)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  const size_t sw = has_bits ? ((size_t)bits + 31) / 32 : 8;  // words per scalar
   msm_bases_info_t inf;
   int rc = msm_bases_info(h, &inf);
   if (rc != MSM_OK) return throw_rc(env, rc);  // released, or never a handle
   const bool subset = has_first || has_idx;
-  if (!subset && slen / 8 < inf.n) {
+  if (!subset && slen / sw < inf.n) {
     napi_throw_range_error(env, nullptr, "fewer scalars than the handle has points");
     return nullptr;
   }
-  if (has_idx && ilen != slen / 8) {
+  if (has_idx && ilen != slen / sw) {
     napi_throw_range_error(env, nullptr, "one index per scalar");
     return nullptr;
   }
   Job* j = new Job();
   j->bases = h;
-  j->n = subset ? slen / 8 : (size_t)inf.n;
+  j->n = subset ? slen / sw : (size_t)inf.n;
+  j->scalar_bits = has_bits ? (uint32_t)bits : 0;
   j->subset = subset;
   j->indexed = has_idx;
   j->first = (uint64_t)first;
@@ -595,8 +610,8 @@ napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
       return nullptr;
     }
   } else {  // detachable memory: the worker reads a copy
-    j->scalars.resize(j->n * 8);
-    copy_words(j->scalars.data(), sc, j->n * 8);
+    j->scalars.resize(j->n * sw);
+    copy_words(j->scalars.data(), sc, j->n * sw);
   }
   return start_job(env, j);
 }

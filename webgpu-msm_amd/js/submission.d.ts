@@ -23,7 +23,10 @@ export declare function prepare_bases(
 // With `subset` the MSM runs over a subset of the handle's bases and `scalars` gives its length m:
 // the range [first, first + m), or the bases indices[0..m) (each < handle.n, repeats allowed;
 // `first` must then be absent or 0).  An index or a range outside the handle rejects.
-export type BasesSubset = { first?: number; indices?: Uint32Array };
+// `scalarBits` = b (1..256), alone or beside either: narrow scalars -- a flat Uint32Array holds
+// ceil(b / 32) big-endian words per scalar, bigints are packed to that many words (one at or above
+// 2^b rejects) -- and the MSM runs the windows of a b-bit scalar only.
+export type BasesSubset = { first?: number; indices?: Uint32Array; scalarBits?: number };
 export declare const compute_msm_prepared: (
   handle: BasesHandle,
   scalars: bigint[] | Uint32Array[] | Uint32Array,

@@ -183,12 +183,30 @@ function pointWords(points) {
   return pb;
 }
 
-function scalarWords(scalars) {
+// (`bits`: narrow scalars of ceil(bits / 32) words each; a bigint at or above 2^bits throws)
+function scalarWords(scalars, bits) {
   if (scalars instanceof Uint32Array) return scalars;
-  const sb = new Uint32Array(scalars.length * nUint32PerScalar);
+  if (bits === undefined) {
+    const sb = new Uint32Array(scalars.length * nUint32PerScalar);
+    scalars.forEach((s, i) => {
+      if (typeof s === "bigint") wordsOf(s, sb, 8 * i);
+      else sb.set(s.subarray(0, 8), 8 * i);
+    });
+    return sb;
+  }
+  const words = Math.ceil(bits / 32);
+  const sb = new Uint32Array(scalars.length * words);
   scalars.forEach((s, i) => {
-    if (typeof s === "bigint") wordsOf(s, sb, 8 * i);
-    else sb.set(s.subarray(0, 8), 8 * i);
+    if (typeof s !== "bigint") {
+      sb.set(s.subarray(0, words), words * i);
+      return;
+    }
+    let b = s;
+    if (b < 0n || b >> BigInt(bits)) throw new RangeError(`scalar must be a bigint in [0, 2^${bits})`);
+    for (let k = words - 1; k >= 0; k--) {
+      sb[words * i + k] = Number(b & 0xffffffffn);
+      b >>= 32n;
+    }
   });
   return sb;
 }
@@ -202,14 +220,21 @@ export function prepare_bases(baseAffinePoints, options) {
 // length m (msm_bases_compute_subset): { first } the range [first, first + m), { indices } (a
 // Uint32Array of m base indices, repeats allowed) the bases indices[i].  An index >= handle.n, or a
 // range past the end, rejects.  Without it the call is what it always was: all n bases.
+// { scalarBits: b } (1..256, alone or beside either) declares narrow scalars (msm_opts
+// MSM_FLAG_SCALAR_BITS): a flat Uint32Array then holds ceil(b / 32) big-endian words per scalar,
+// bigints are packed to that many words (one at or above 2^b rejects), and the MSM runs the windows
+// of a b-bit scalar only -- 5 instead of 17 for 64-bit limbs.
 export const compute_msm_prepared = async (handle, scalars, subset) => {
   if (!handle || typeof handle.id !== "number") throw new TypeError("compute_msm_prepared(handle, scalars): not a handle");
   if (subset !== undefined && subset !== null) {
-    const { first, indices } = subset;
+    const { first, indices, scalarBits } = subset;
+    if (scalarBits !== undefined && !(Number.isInteger(scalarBits) && scalarBits >= 1 && scalarBits <= 256))
+      throw new RangeError("subset.scalarBits: an integer in 1..256");
     if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("subset.indices: a Uint32Array");
     if (first !== undefined && !(Number.isSafeInteger(first) && first >= 0)) throw new RangeError("subset.first: a non-negative integer");
     // an empty options object is still a subset call: the prefix of as many bases as scalars
-    const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars), first === undefined ? 0 : first, indices);
+    const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars, scalarBits),
+                                                  first === undefined ? 0 : first, indices, scalarBits);
     const [x, y] = u32ArrayToBigInts(result);
     return { x, y };
   }

@@ -25,7 +25,8 @@ __all__ = [
     "compute_msm_shared_device", "compute_msm_many", "compute_msm_shared", "compute_msm_cpu", "MSM_FLAG_SERIAL",
     "combine_partials", "combine_partials_many", "point_add_affine",
     "split_dynamic", "get_best_window_size", "set_profiling", "last_profile", "device_count", "device_ordinals",
-    "MSM_FLAG_DEVICES", "MSM_FLAG_WINDOWS", "MSM_FLAG_HALF_WINDOWS", "MSM_MAX_DEVICES", "window_count",
+    "MSM_FLAG_DEVICES", "MSM_FLAG_WINDOWS", "MSM_FLAG_HALF_WINDOWS", "MSM_FLAG_SCALAR_BITS", "MSM_MAX_DEVICES",
+    "window_count",
     "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P", "Bases", "BasesInfo",
 ]
 
@@ -45,11 +46,12 @@ class MsmError(RuntimeError):
 
 class MsmOpts(ctypes.Structure):
     """include/msm.h msm_opts: the original four fields, then the device list (read by libmsm only
-    when flags has MSM_FLAG_DEVICES), then the window range (MSM_FLAG_WINDOWS)."""
+    when flags has MSM_FLAG_DEVICES), the scalar width (MSM_FLAG_SCALAR_BITS), then the window range
+    (MSM_FLAG_WINDOWS)."""
     _fields_ = [("window_bits", ctypes.c_uint32), ("run_length", ctypes.c_uint32),
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("devices", ctypes.POINTER(ctypes.c_int32)), ("n_devices", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32), ("window_lo", ctypes.c_uint32), ("window_hi", ctypes.c_uint32)]
+                ("scalar_bits", ctypes.c_uint32), ("window_lo", ctypes.c_uint32), ("window_hi", ctypes.c_uint32)]
 
 
 class MsmProfile(ctypes.Structure):
@@ -77,6 +79,7 @@ MSM_FLAG_SERIAL = 1  # pipelined entries: one launch in flight at a time
 MSM_FLAG_DEVICES = 2  # msm_opts carries a device list (include/msm.h)
 MSM_FLAG_WINDOWS = 4  # msm_opts carries a window range
 MSM_FLAG_HALF_WINDOWS = 8  # with MSM_FLAG_WINDOWS: the range counts half windows
+MSM_FLAG_SCALAR_BITS = 16  # msm_opts carries the scalars' width (narrow scalars, Bases.compute* only)
 MSM_MAX_DEVICES = 16
 MSM_STREAM_NULL = 1  # hip_stream value: order after the null (legacy default) stream
 
@@ -155,6 +158,7 @@ def load() -> ctypes.CDLL:
         "msm_test_subset_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_narrow_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
@@ -220,13 +224,20 @@ def _out(n: int) -> Tuple[np.ndarray, ctypes.POINTER(ctypes.c_uint32)]:
 
 
 def _opts(window_size: Optional[int], run_length: Optional[int] = None, device: int = -1, flags: int = 0,
-          devices: Optional[Sequence[int]] = None, windows: Optional[Tuple[int, int]] = None):
+          devices: Optional[Sequence[int]] = None, windows: Optional[Tuple[int, int]] = None,
+          scalar_bits: Optional[int] = None):
     """A msm_opts by reference.  `devices` (a list of HIP ordinals) runs the call on several
     devices (MSM_FLAG_DEVICES); the array is kept alive by the returned object.  `windows` =
     (lo, hi) restricts the MSM to those signed-digit windows (MSM_FLAG_WINDOWS; needs an explicit
     window_size); (lo, hi, 2) counts the range in half windows (MSM_FLAG_HALF_WINDOWS: half window
-    2w is window w's lower-half buckets, 2w + 1 its upper half)."""
+    2w is window w's lower-half buckets, 2w + 1 its upper half).  `scalar_bits` = b declares narrow
+    scalars of ceil(b / 32) words (MSM_FLAG_SCALAR_BITS; the Bases.compute* calls only)."""
     o = MsmOpts(int(window_size or 0), int(run_length or 0), int(device), int(flags))
+    if scalar_bits is not None:
+        if not 0 <= int(scalar_bits) < 1 << 32:
+            raise ValueError("scalar_bits out of range")
+        o.scalar_bits = int(scalar_bits)
+        o.flags |= MSM_FLAG_SCALAR_BITS
     if windows is not None:
         o.window_lo, o.window_hi = int(windows[0]), int(windows[1])
         o.flags |= MSM_FLAG_WINDOWS
@@ -287,17 +298,35 @@ def points_to_wire(points) -> np.ndarray:
     return out
 
 
-def scalars_to_wire(scalars) -> np.ndarray:
-    """bigint[] or Uint32Array[] (BE u32[8]) -> [n, 8] u32."""
+def _scalar_words(scalar_bits: Optional[int]) -> int:
+    """u32 words per wire scalar: 8, or ceil(b / 32) for narrow scalars of b bits (0 for a width
+    outside 1..256: arrays then go to the library as they are, and it reports the width)."""
+    if scalar_bits is None:
+        return 8
+    return (int(scalar_bits) + 31) // 32 if 1 <= int(scalar_bits) <= 256 else 0
+
+
+def scalars_to_wire(scalars, scalar_bits: Optional[int] = None) -> np.ndarray:
+    """bigint[] or Uint32Array[] (BE u32[8]) -> [n, 8] u32.  With `scalar_bits` = b the narrow
+    format of the Bases.compute* calls: [n, ceil(b / 32)] u32, big-endian words; a value >= 2^b
+    raises ValueError."""
+    words = _scalar_words(scalar_bits)
     if isinstance(scalars, np.ndarray):
-        return _u32(scalars).reshape(-1, 8)
+        return _u32(scalars).reshape(-1, words) if words else np.atleast_2d(_u32(scalars))
+    if not words:
+        raise ValueError("scalar_bits must be 1..256")
     sc = list(scalars)
     if not sc:
-        return np.zeros((0, 8), dtype=np.uint32)
+        return np.zeros((0, words), dtype=np.uint32)
     if isinstance(sc[0], (int, np.integer)):
-        buf = b"".join(_int_be_words(int(s)) for s in sc)
-        return np.frombuffer(buf, dtype=">u4").astype(np.uint32).reshape(-1, 8)
-    return np.stack([np.asarray(s, dtype=np.uint32).reshape(8) for s in sc])
+        if scalar_bits is None:
+            buf = b"".join(_int_be_words(int(s)) for s in sc)
+        else:
+            if any(int(s) < 0 or int(s) >> int(scalar_bits) for s in sc):
+                raise ValueError(f"a scalar does not fit {int(scalar_bits)} bits")
+            buf = b"".join(int(s).to_bytes(4 * words, "big") for s in sc)
+        return np.frombuffer(buf, dtype=">u4").astype(np.uint32).reshape(-1, words)
+    return np.stack([np.asarray(s, dtype=np.uint32).reshape(words) for s in sc])
 
 
 def _xy(o: np.ndarray) -> Tuple[int, int]:
@@ -482,7 +511,7 @@ def compute_msm_shared_device(d_points, scalars_list, n: int, window_size: Optio
 
 
 def _host_list(arrs, words: int):
-    keep = [np.ascontiguousarray(_u32(a).reshape(-1, words)) for a in arrs]
+    keep = [np.ascontiguousarray(_u32(a).reshape(-1, words) if words else np.atleast_2d(_u32(a))) for a in arrs]
     ptrs = (ctypes.c_void_p * max(len(keep), 1))(*[a.ctypes.data for a in keep])
     return keep, ptrs
 
@@ -525,45 +554,53 @@ class Bases:
         _check(load().msm_bases_info(self._h or None, ctypes.byref(inf)), "msm_bases_info")
         return {name: int(getattr(inf, name)) for name, _ in BasesInfo._fields_ if name != "reserved"}
 
-    def compute(self, scalars, window_size: Optional[int] = None, run_length: Optional[int] = None) -> Tuple[int, int]:
+    # Every compute call takes `scalar_bits` = b (include/msm.h MSM_FLAG_SCALAR_BITS): the scalars are
+    # then narrow -- [n, ceil(b / 32)] words each, big-endian words, below 2^b (scalars_to_wire(...,
+    # scalar_bits=b) packs ints) -- and the MSM runs the windows of a b-bit scalar only.
+
+    def compute(self, scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
+                scalar_bits: Optional[int] = None) -> Tuple[int, int]:
         """One MSM of host scalars ([n, 8] wire words, or anything scalars_to_wire takes)."""
         n = self.info["n"]
-        sc = np.ascontiguousarray(scalars_to_wire(scalars))
+        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
         if sc.shape[0] < n:
             raise ValueError("fewer scalars than the handle has points")
         o, op = _out(16)
-        _check(load().msm_bases_compute(self._h, _ptr(sc), _opts(window_size, run_length), op), "msm_bases_compute")
+        _check(load().msm_bases_compute(self._h, _ptr(sc), _opts(window_size, run_length, scalar_bits=scalar_bits), op),
+               "msm_bases_compute")
         return _xy(o)
 
     def compute_device(self, d_scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                       stream: int = 0) -> Tuple[int, int]:
+                       stream: int = 0, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
         """One MSM of device-resident scalars (a torch tensor or a raw device pointer, n x 8 words)."""
         o, op = _out(16)
-        _check(load().msm_bases_compute_device(self._h or None, _dev_ptr(d_scalars), _opts(window_size, run_length),
+        _check(load().msm_bases_compute_device(self._h or None, _dev_ptr(d_scalars),
+                                               _opts(window_size, run_length, scalar_bits=scalar_bits),
                                                _stream(stream, d_scalars), op), "msm_bases_compute_device")
         return _xy(o)
 
     def compute_many(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                     flags: int = 0) -> np.ndarray:
+                     flags: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
         """len(scalars_list) pipelined MSMs of host scalar vectors.  [count][16] BE words."""
         n = self.info["n"]
-        ks, ss = _host_list(scalars_list, 8)
+        ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
         if any(b.shape[0] < n for b in ks):
             raise ValueError("fewer scalars than the handle has points")
         count = len(ks)
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_many(self._h, ctypes.cast(ss, ctypes.c_void_p), count,
-                                             _opts(window_size, run_length, -1, flags), op), "msm_bases_compute_many")
+                                             _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits), op),
+               "msm_bases_compute_many")
         return o[:16 * count].reshape(count, 16)
 
     def compute_many_device(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                            flags: int = 0, stream: int = 0) -> np.ndarray:
+                            flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
         """The same with device-resident scalar vectors."""
         count = len(scalars_list)
         ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_many_device(self._h or None, ctypes.cast(ss, ctypes.c_void_p), count,
-                                                    _opts(window_size, run_length, -1, flags),
+                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits),
                                                     _stream(stream, _first(scalars_list)), op),
                "msm_bases_compute_many_device")
         return o[:16 * count].reshape(count, 16)
@@ -612,38 +649,40 @@ class Bases:
         return [_dev_ptr(t) for t in vecs]
 
     def compute_subset(self, scalars, first: int = 0, indices=None, window_size: Optional[int] = None,
-                       run_length: Optional[int] = None) -> Tuple[int, int]:
+                       run_length: Optional[int] = None, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
         """One MSM of the m = len(scalars) host scalars over bases [first, first + m), or over
         bases indices[0..m) (a uint32 array)."""
-        sc = np.ascontiguousarray(scalars_to_wire(scalars))
+        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
         m = sc.shape[0]
         keep, ptrs = self._host_indices(indices, m, 1)
         sub = self._subset(first, m, ptrs)
         o, op = _out(16)
         _check(load().msm_bases_compute_subset(self._h or None, ctypes.byref(sub), _ptr(sc),
-                                               _opts(window_size, run_length), op), "msm_bases_compute_subset")
+                                               _opts(window_size, run_length, scalar_bits=scalar_bits), op),
+               "msm_bases_compute_subset")
         return _xy(o)
 
     def compute_subset_device(self, d_scalars, first: int = 0, indices=None, m: Optional[int] = None,
                               window_size: Optional[int] = None, run_length: Optional[int] = None,
-                              stream: int = 0) -> Tuple[int, int]:
+                              stream: int = 0, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
         """The same with device-resident scalars (a torch tensor [m, 8], or a raw device pointer with
         `m`) and, in indexed form, a device-resident int32/uint32 index tensor (or pointer)."""
         m = len(d_scalars) if m is None else int(m)
         sub = self._subset(first, m, self._device_indices(indices, 1))
         o, op = _out(16)
         _check(load().msm_bases_compute_subset_device(self._h or None, ctypes.byref(sub), _dev_ptr(d_scalars),
-                                                      _opts(window_size, run_length),
+                                                      _opts(window_size, run_length, scalar_bits=scalar_bits),
                                                       _stream(stream, d_scalars, indices), op),
                "msm_bases_compute_subset_device")
         return _xy(o)
 
     def compute_subset_many(self, scalars_list, first: int = 0, indices=None, window_size: Optional[int] = None,
-                            run_length: Optional[int] = None, flags: int = 0) -> np.ndarray:
+                            run_length: Optional[int] = None, flags: int = 0,
+                            scalar_bits: Optional[int] = None) -> np.ndarray:
         """len(scalars_list) pipelined MSMs of host scalar vectors of one length m, over one range
         or over each MSM's own index vector (`indices`: a list of arrays, or one array for all).
         [count][16] BE words."""
-        ks, ss = _host_list(scalars_list, 8)
+        ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
         count = len(ks)
         m = ks[0].shape[0] if count else 0
         if any(b.shape[0] != m for b in ks):
@@ -652,13 +691,15 @@ class Bases:
         sub = self._subset(first, m, ptrs)
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_subset_many(self._h or None, ctypes.byref(sub), ctypes.cast(ss, ctypes.c_void_p),
-                                                    count, _opts(window_size, run_length, -1, flags), op),
+                                                    count,
+                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits),
+                                                    op),
                "msm_bases_compute_subset_many")
         return o[:16 * count].reshape(count, 16)
 
     def compute_subset_many_device(self, scalars_list, first: int = 0, indices=None, m: Optional[int] = None,
                                    window_size: Optional[int] = None, run_length: Optional[int] = None,
-                                   flags: int = 0, stream: int = 0) -> np.ndarray:
+                                   flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
         """The same with device-resident scalar (and index) vectors."""
         count = len(scalars_list)
         if m is None:
@@ -669,7 +710,8 @@ class Bases:
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_subset_many_device(self._h or None, ctypes.byref(sub),
                                                            ctypes.cast(ss, ctypes.c_void_p), count,
-                                                           _opts(window_size, run_length, -1, flags),
+                                                           _opts(window_size, run_length, -1, flags,
+                                                                 scalar_bits=scalar_bits),
                                                            _stream(stream, *tensors), op),
                "msm_bases_compute_subset_many_device")
         return o[:16 * count].reshape(count, 16)
@@ -923,6 +965,17 @@ def _test_bases_plan(n: int, levels: int, window_size: int = 0) -> dict:
     o, op_ = _out(4)
     _check(load().msm_test_bases_plan(n, levels, window_size, op_), "msm_test_bases_plan")
     return dict(zip(("c", "windows", "chunk_bits", "points"), (int(v) for v in o)))
+
+
+def _test_narrow_plan(n: int, scalar_bits: int, window_size: int = 0) -> dict:
+    """The geometry of a narrow-scalar launch (msm_test_narrow_plan; no GPU needed): the widest
+    window c, the windows W', the base width q, the nhi windows of q + 1 bits, the words per scalar
+    and the packed flag.  254 bits and more report the plain launch's (8 words, overflow window
+    included in `windows`)."""
+    out = np.zeros(6, np.uint32)
+    _check(load().msm_test_narrow_plan(n, int(scalar_bits), int(window_size),
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_narrow_plan")
+    return dict(zip(("c", "windows", "q", "nhi", "words", "packed"), (int(v) for v in out)))
 
 
 def _test_subset_plan(n_handle: int, levels: int, window_size: int, first: int, m: int, indexed: bool) -> dict:
