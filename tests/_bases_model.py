@@ -8,7 +8,7 @@ MAIN_BITS = 254  # msm_dev.h: bits the main windows cover; one 3-bit overflow wi
 
 
 def geometry(c):
-    """The library's balanced windows at width c (msm_host.hip make_plan): widths and bit offsets of
+    """The library's balanced windows at width c (host_plan.h make_plan): widths and bit offsets of
     the Wm = wm + 1 windows, least significant first."""
     wm = (MAIN_BITS + c - 1) // c
     q = MAIN_BITS // wm

@@ -348,7 +348,7 @@ def test_many_device_pipelined_distinct_inputs():
 @pytest.mark.parametrize("n,c", [(1 << 16, 14), (1 << 17, 15), ((7 << 16) - 1, 15), (7 << 16, 16)])
 def test_many_device_throughput_window(n, c):
     # below 2^20 the pipelined entry picks a narrower window than a lone MSM (c = 14 at 2^16,
-    # 15 at 2^17, 16 from 7/8 of 2^19: msm_host.hip pipelined_window); results must not depend on it
+    # 15 at 2^17, 16 from 7/8 of 2^19: host_plan.h pipelined_window); results must not depend on it
     torch = pytest.importorskip("torch")
     d_pts = torch.from_numpy(O.gen_points(n, k0=1, step=1).view(np.int32)).cuda()
     scs, exps = [], []

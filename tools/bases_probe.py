@@ -1,5 +1,5 @@
 """Resident prepared bases (msm_amd.Bases) against the entries that take the points on every call:
-the sweep behind the auto table in msm_host.hip (BASES_AUTO) and DESIGN.md §9.
+the sweep behind the auto table in host_plan.h (BASES_AUTO) and DESIGN.md §9.
 
     python tools/bases_probe.py [--sizes 16,18,20] [--levels 1,2,4] [--count 20] [--out FILE]
 

@@ -1,4 +1,4 @@
-# Pipelined device-resident ms per MSM just below the window thresholds of pipelined_window (msm_host.hip),
+# Pipelined device-resident ms per MSM just below the window thresholds of pipelined_window (host_plan.h),
 # each with the two candidate widths.  Run on the GPU box: bash tools/window_boundary_probe.sh
 set -e
 cd "${GRAFT_REPO_ROOT:-/root/repo}"

@@ -1,0 +1,213 @@
+// Layer 11, resident prepared bases: the handle registry, creation, and the compute entries' common path.
+// Depends on the layers above it (knobs .. multi).
+#pragma once
+// A handle's state.  The caller's msm_bases* is a token (the registry key, never an address), so a
+// stale or foreign handle is a failed lookup, not a dereference.  `rec` is freed, and `alive`
+// cleared, under the owning device context's lock (msm_bases_destroy, msm_shutdown); a compute
+// call holds a reference and checks `alive` under that lock before it reads the records.
+struct Bases {
+  int device = -1;
+  size_t n = 0;
+  uint32_t levels = 1;
+  uint32_t window_bits = 0;  // levels > 1: the width the levels were shifted for
+  BasesGeo geo{};            // levels > 1
+  Buf rec;                   // levels * n records, level j at [j n, (j + 1) n)
+  bool alive = false;
+};
+std::map<uintptr_t, std::shared_ptr<Bases>> g_bases;  // under g_mu
+uintptr_t g_bases_next = 1;
+
+std::shared_ptr<Bases> find_bases(const msm_bases* h) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_bases.find(reinterpret_cast<uintptr_t>(h));
+  return it == g_bases.end() ? nullptr : it->second;
+}
+
+// Every live handle's records on `device` (DevCtx::destroy, under g_mu and the context's lock); its
+// next use fails the registry lookup.
+void release_bases_on(int device) {
+  for (auto& kv : g_bases)
+    if (kv.second->device == device) {
+      kv.second->alive = false;
+      kv.second->rec.release();
+    }
+}
+
+bool bases_flags_ok(const msm_opts* o) {  // a handle lives on one device and runs whole MSMs
+  return !o || !(o->flags & (MSM_FLAG_DEVICES | MSM_FLAG_WINDOWS | MSM_FLAG_HALF_WINDOWS));
+}
+
+int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* opts, uint32_t levels,
+                 hipStream_t user_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  *out = nullptr;
+  if ((!points && n) || levels > 8 || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  const uint32_t wb = opts ? opts->window_bits : 0;
+  if (wb && (wb < 4 || wb > 20)) return MSM_ERR_UNSUPPORTED_WINDOW;
+  if (!levels) levels = bases_auto_levels(n);
+  auto b = std::make_shared<Bases>();
+  b->n = n;
+  b->levels = levels;
+  if (levels > 1) {
+    b->window_bits = wb ? wb : bases_auto_window(n, levels);
+    if (!bases_geometry(b->window_bits, levels, &b->geo)) return MSM_ERR_INVALID_ARG;
+  }
+  if ((uint64_t)levels * n >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  msm_opts od{};
+  od.device = opts ? opts->device : -1;
+  int rc = on_device(&od, [&](DevCtx* c) -> int {
+    b->device = c->device;
+    if (!n) return MSM_OK;
+    {  // the launch plan of one MSM on these records must exist (finish_plan's Mmax limit)
+      msm_opts op{};
+      op.window_bits = levels > 1 ? b->window_bits : wb;
+      if (levels > 1) {
+        op.flags = MSM_FLAG_WINDOWS;
+        op.window_hi = b->geo.Wc;
+      }
+      Plan pl;
+      if (int prc = make_plan(n * levels, &op, c->shape, &pl, false, 1, true)) return prc;
+    }
+    Slot& s0 = c->slot[0];
+    Buf errb;  // the preparation's error word
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if ((r = b->rec.ensure((size_t)levels * n * PRE_WORDS * 4)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    auto done = [&](int code) {  // every exit past the allocations: a failure leaves nothing allocated
+      drain_streams(c, 1, code);
+      errb.release();
+      if (code != MSM_OK) b->rec.release();
+      return code;
+    };
+    uint32_t* rec = b->rec.as<uint32_t>();
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    const uint32_t nt = prep_nt((size_t)levels * n);
+    if (host) {
+      if ((r = s0.ws.wire_pts.ensure(n * 128)) != MSM_OK) return done(r);
+      if ((r = upload_points(c, points, n, s0.ws.wire_pts.as<uint32_t>(), rec, errp, s0.stream)) != MSM_OK)
+        return done(r);
+    } else {
+      launch_prepare(points, rec, (uint32_t)n, errp, nt, s0.stream);
+    }
+    for (uint32_t j = 1; j < levels; j++)
+      hipLaunchKernelGGL(k_shift_bases, dim3(grid_for(n, PP_THREADS)), dim3(PP_THREADS), 0, s0.stream,
+                         rec + (size_t)(j - 1) * n * PRE_WORDS, rec + (size_t)j * n * PRE_WORDS, (uint32_t)n,
+                         b->geo.S, nt);
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+  if (rc != MSM_OK) return rc;
+  b->alive = true;  // n = 0: nothing allocated
+  std::lock_guard<std::mutex> lk(g_mu);
+  // msm_shutdown may have run since the records were made (it frees only registered handles)
+  if (n && ((int)g_ctx.size() <= b->device || !g_ctx[b->device])) {
+    b->rec.release();
+    return MSM_ERR_INVALID_ARG;
+  }
+  const uintptr_t id = g_bases_next++;
+  g_bases[id] = b;
+  *out = reinterpret_cast<msm_bases*>(id);
+  return MSM_OK;
+}
+
+// `count` MSMs over a handle's records: run_many's pipelined path with the records in the place
+// of a shared base vector's (count = 1: the single entries, which then have no preparation to fork).
+// With `sub`, over a subset of the bases (msm_bases_compute_subset*).
+int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host, size_t count, const msm_opts* opts,
+                  void* hip_stream, uint32_t* out, const msm_subset_t* sub = nullptr, bool is_subset = false) {
+  if (!h || !out || (!scalars && count) || !bases_flags_ok(opts) || (is_subset && !sub)) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b) return MSM_ERR_INVALID_ARG;
+  const bool indexed = sub && sub->indices;
+  const size_t terms = sub ? (size_t)sub->m : b->n;  // scalars per vector
+  // Narrow scalars (MSM_FLAG_SCALAR_BITS): below 254 bits the call runs unfolded on the level-0
+  // records, whatever the handle's levels -- they are plain prepared records -- over the scalars'
+  // own geometry (make_plan); 254 bits and more are the 8-word call as it is.
+  const uint32_t sbits = narrow_flagged(opts) ? opts->scalar_bits : 256;
+  if (sbits < 1 || sbits > 256) return MSM_ERR_INVALID_ARG;
+  const bool narrow = sbits < MAIN_BITS;
+  const uint32_t levels = narrow ? 1u : b->levels;
+  if (sub) {
+    if (int rc = subset_check(b->n, levels, sub->first, sub->m, indexed)) return rc;
+    for (size_t k = 0; indexed && terms && k < count; k++) {
+      const uint32_t* ix = sub->indices[k];
+      if (!ix) return MSM_ERR_INVALID_ARG;
+      // host index vectors are checked here, before anything is uploaded or enqueued (the device
+      // entries' are checked by k_stage_indices); a vector given again is checked once
+      if (!host || (k && ix == sub->indices[k - 1])) continue;
+      for (size_t i = 0; i < terms; i++)
+        if (ix[i] >= b->n) return MSM_ERR_INVALID_ARG;
+    }
+  }
+  if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
+  msm_opts o{};
+  o.run_length = opts ? opts->run_length : 0;
+  o.flags = opts ? (opts->flags & MSM_FLAG_SERIAL) : 0;
+  o.device = b->device;
+  o.window_bits = opts ? opts->window_bits : 0;
+  if (narrow) {
+    o.flags |= MSM_FLAG_SCALAR_BITS;
+    o.scalar_bits = sbits;
+  }
+  if (levels > 1) {
+    if (o.window_bits && o.window_bits != b->window_bits) return MSM_ERR_INVALID_ARG;
+    o.window_bits = b->window_bits;
+    o.flags |= MSM_FLAG_WINDOWS;
+    o.window_lo = 0;
+    o.window_hi = b->geo.Wc;
+  }
+  if (count == 0) return MSM_OK;
+  for (size_t k = 0; k < count; k++)
+    if (!scalars[k] && terms) return MSM_ERR_INVALID_ARG;
+  // A bit at or above scalar_bits: host vectors are checked on the host, before anything is uploaded
+  // or enqueued (the device entries' by k_recode_narrow); only the most significant word can hold
+  // one.  Large vectors go over the device context's parked packing threads (the strided read of
+  // 2^20 8-word scalars is ~0.5 ms on one thread); a vector given again is checked once.
+  auto host_scalars_ok = [&](DevCtx* c) -> bool {
+    if (!host || sbits == 256 || !(sbits & 31u)) return true;
+    const size_t sw = (sbits + 31) / 32;
+    const uint32_t excess = ~((1u << (sbits & 31u)) - 1u);
+    for (size_t k = 0; k < count; k++) {
+      if (k && scalars[k] == scalars[k - 1]) continue;
+      const uint32_t* v = scalars[k];
+      std::atomic<uint32_t> any{0};
+      auto scan = [&](int t, int nt) {
+        uint32_t a = 0;
+        for (size_t i = terms * t / nt, e = terms * (t + 1) / nt; i < e; i++) a |= v[i * sw];
+        any.fetch_or(a);
+      };
+      if (terms >= (1u << 17)) ctx_packer(c)->run(scan);
+      else scan(0, 1);
+      if (any.load() & excess) return false;
+    }
+    return true;
+  };
+  return on_device(&o, [&](DevCtx* c) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    if (!host_scalars_ok(c)) return MSM_ERR_INVALID_ARG;
+    ManyInputs in;
+    in.kind = host ? ManyInputs::HOST : ManyInputs::DEVICE;
+    in.scalars = scalars;
+    in.prepared = b->rec.as<uint32_t>();
+    in.levels = levels;
+    in.chunk_bits = b->geo.S;
+    if (sub) {
+      in.sub = subset_kind(levels, sub->first, indexed);
+      in.sub_first = (size_t)sub->first;
+      in.rec_n = b->n;
+      in.indices = sub->indices;
+    }
+    return run_many(c, in, terms, count, &o, (hipStream_t)hip_stream, out, false);
+  });
+}

@@ -1,0 +1,704 @@
+// Layer 5, one launch: workspaces, the kernel launch sequence, its captured graphs, waiting for a slot and
+// finishing its MSMs.  Depends on the layers above it (knobs, ctx, plan, tail).
+#pragma once
+// (`own_pts` false: the launch reads a handle's resident records, the slot needs no record buffer.)
+int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
+  Slot& sl0 = c->slot[si];
+  Workspace& w = sl0.ws;
+  const MsmDims& d = pl.d;
+  const size_t nb = (size_t)d.W * d.B;
+  int rc;
+  const uint64_t gen0 = g_alloc_gen.load();
+#define ENS(buf, bytes) \
+  if ((rc = w.buf.ensure(bytes)) != MSM_OK) return rc
+  ENS(pts, own_pts ? (size_t)(d.shared ? 1 : d.nm) * d.n * PRE_WORDS * 4 : 0);
+  ENS(err, 16);
+  ENS(digits, (size_t)d.W * d.n * 4);
+  ENS(colsum, ((size_t)d.nbins + d.W) * 4);  // bin totals, then window totals
+  ENS(bin_base, ((size_t)d.nbins + 1) * 4);
+  ENS(bin_cur, (size_t)d.nbins * 4);
+  ENS(part_entry, pl.Mmax * 4);
+  ENS(part_fine, pl.Mmax * 2);
+  ENS(sorted_entry, pl.Mmax * 4 + 16);  // + a 16-B tail for k_accumulate's vector entry loads
+  ENS(bucket_start, (nb + 2) * 4);
+  ENS(run_key, pl.runs_max * 4);
+#ifdef MSM_DUMMY_ALLOC
+  ENS(dummy_tiles, (pl.Mmax / FS_CAP + d.nbins + 1) * 8 + 8);
+  ENS(dummy_cursor, nb * 4);
+#endif
+  ENS(buckets, nb * PT_WORDS * 4);
+  const size_t nwg = pl.runs_max / ACC_THREADS + 2;
+  ENS(lead_val, nwg * PT_WORDS * 4);
+  ENS(lead_open, nwg * 4);
+  ENS(cross_key, nwg * 4);
+  ENS(lead_flag, 16);
+  ENS(skew_list, (nwg + 1) * 4);
+  ENS(g_head, pl.runs_max * PT_WORDS * 4);  // touched only by skewed workgroups
+  ENS(g_hkey, pl.runs_max * 4);
+  ENS(g_tkey, pl.runs_max * 4);
+  ENS(red_U, (size_t)d.W * pl.nchunks * PT_WORDS * 4);
+  ENS(red_T, (size_t)d.W * pl.nchunks * PT_WORDS * 4);
+  if (red2_tree(pl)) ENS(red_G, (size_t)d.W * red2_groups(pl) * RG_OUT * PT_WORDS * 4);
+#undef ENS
+  if (g_alloc_gen.load() != gen0) {
+    // err, lead_flag, colsum and bin_cur are kept all-zero between MSMs by the kernels themselves
+    // (k_bucket_reduce_2 clears the flags, k_fine_sort the bin totals and cursors), so a
+    // replayed graph needs no memset nodes; fresh allocations start that invariant here.
+    hipStream_t st = sl0.stream;
+    if (hipMemsetAsync(w.err.p, 0, w.err.cap, st) != hipSuccess ||
+        hipMemsetAsync(w.lead_flag.p, 0, w.lead_flag.cap, st) != hipSuccess ||
+        hipMemsetAsync(w.skew_list.p, 0, 4, st) != hipSuccess ||
+        hipMemsetAsync(w.colsum.p, 0, w.colsum.cap, st) != hipSuccess ||
+        hipMemsetAsync(w.bin_cur.p, 0, w.bin_cur.cap, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return MSM_ERR_HIP;
+  }
+  const size_t hbytes = (size_t)d.W * pl.nterms * 32 * 4 + 64;
+  if (hbytes > sl0.h_out.cap || !sl0.h_out_dev) {
+    if ((rc = sl0.h_out.ensure(hbytes)) != MSM_OK) return rc;
+    if (hipHostGetDevicePointer(&sl0.h_out_dev, sl0.h_out.p, 0) != hipSuccess) return MSM_ERR_HIP;
+  }
+  return MSM_OK;
+}
+
+inline unsigned grid_for(size_t threads, unsigned block) { return (unsigned)((threads + block - 1) / block); }
+
+bool slot_forks(const Slot& sl) { return sl.pipelined ? fork_prepare() && fork_prepare_pipelined() : fork_prepare(); }
+
+// Whether k_prepare_points writes `records` point records with nontemporal stores: only when they
+// outgrow the Infinity Cache (>= 128 MiB, i.e. 2^20 records; MSM_PP_NT=0/1 forces it).
+uint32_t prep_nt(size_t records) {
+  if (knob_pp_nt() >= 0) return knob_pp_nt() ? 1u : 0u;
+  return records * 128 >= (size_t(1) << 27) ? 1u : 0u;
+}
+
+// k_prepare_points over `cnt` points of one wire buffer into `pts_out` (one MSM, or one uploaded
+// chunk of it); `nt` from prep_nt of the whole record buffer.
+void launch_prepare(const uint32_t* wire, uint32_t* pts_out, uint32_t cnt, uint32_t* err, uint32_t nt,
+                    hipStream_t s, uint32_t fmt = PT_FMT_WIRE) {
+  BatchPtrs bp{};
+  bp.p[0] = wire;
+  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(cnt, PP_THREADS), 1), dim3(PP_THREADS), 0, s, bp, pts_out, cnt,
+                     err, nt, fmt);
+}
+
+template <uint32_t Q, uint32_t NHI>
+void launch_recode_fixed(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, hipStream_t s) {
+  const bool full = d.w0 == 0 && d.Wr == d.Wm && !d.half_lo && !d.half_hi;
+  const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
+  const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;
+  if (full)
+    hipLaunchKernelGGL((k_recode_fixed<Q, NHI, true>), grid, dim3(RC_THREADS), lds, s, sc, d,
+                       static_cast<uint16_t*>(digits), colsum);
+  else
+    hipLaunchKernelGGL((k_recode_fixed<Q, NHI, false>), grid, dim3(RC_THREADS), lds, s, sc, d,
+                       static_cast<uint16_t*>(digits), colsum);
+}
+// The narrow recode (MsmDims::sw): one k_recode_narrow instantiation per scalar word count and code
+// width, and its bias C = sum_w (2^(b_w - 1) - 1) 2^off_w over the launch's windows (the sum stays
+// below 2^(T - 1), so it fits the scalar's own words).
+template <typename T>
+const void* recode_narrow_fn(uint32_t sw) {
+  switch (sw) {
+    case 1: return reinterpret_cast<const void*>(&k_recode_narrow<T, 1>);
+    case 2: return reinterpret_cast<const void*>(&k_recode_narrow<T, 2>);
+    case 3: return reinterpret_cast<const void*>(&k_recode_narrow<T, 3>);
+    case 4: return reinterpret_cast<const void*>(&k_recode_narrow<T, 4>);
+    case 5: return reinterpret_cast<const void*>(&k_recode_narrow<T, 5>);
+    case 6: return reinterpret_cast<const void*>(&k_recode_narrow<T, 6>);
+    case 7: return reinterpret_cast<const void*>(&k_recode_narrow<T, 7>);
+    default: return reinterpret_cast<const void*>(&k_recode_narrow<T, 8>);
+  }
+}
+const void* recode_narrow_kernel(const MsmDims& d) {
+  return d.c > 16 ? recode_narrow_fn<uint32_t>(d.sw) : recode_narrow_fn<uint16_t>(d.sw);
+}
+NarrowBias narrow_bias(const MsmDims& d) {
+  NarrowBias nb{};
+  for (uint32_t w = 0; w < d.Wr; w++) {
+    const uint64_t h = (1ull << (win_bits(d, w) - 1)) - 1ull;  // < 2^20: spans at most two words
+    const uint32_t o = win_off(d, w), k = o / 32, sh = o % 32;
+    uint64_t carry = h << sh;
+    for (uint32_t j = k; j < 8 && carry; j++) {
+      const uint64_t x = (uint64_t)nb.v[j] + (carry & 0xffffffffull);
+      nb.v[j] = (uint32_t)x;
+      carry = (carry >> 32) + (x >> 32);
+    }
+  }
+  return nb;
+}
+
+void launch_recode(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
+                   hipStream_t s) {
+  const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
+  const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;  // histogram + window totals
+  if (d.sw) {
+    BatchPtrs scal = sc;
+    MsmDims dd = d;
+    NarrowBias nb = narrow_bias(d);
+    void* args[] = {&scal, &dd, &digits, &colsum, &nb, &err};
+    (void)hipLaunchKernel(recode_narrow_kernel(d), grid, dim3(RC_THREADS), args, lds, s);
+    return;
+  }
+  if (d.c > 16) {
+    hipLaunchKernelGGL(k_recode_hist<uint32_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint32_t*>(digits),
+                       colsum);
+    return;
+  }
+  if (recode_fixed_on()) {
+    if (d.q == 15 && d.nhi == 14) return launch_recode_fixed<15, 14>(d, sc, digits, colsum, s);
+    if (d.q == 14 && d.nhi == 16) return launch_recode_fixed<14, 16>(d, sc, digits, colsum, s);
+    if (d.q == 13 && d.nhi == 7) return launch_recode_fixed<13, 7>(d, sc, digits, colsum, s);
+    if (d.q == 12 && d.nhi == 14) return launch_recode_fixed<12, 14>(d, sc, digits, colsum, s);
+  }
+  hipLaunchKernelGGL(k_recode_hist<uint16_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint16_t*>(digits),
+                     colsum);
+}
+bool is_recode_kernel(const void* f) {
+  const void* ks[] = {reinterpret_cast<const void*>(&k_recode_hist<uint32_t>),
+                      reinterpret_cast<const void*>(&k_recode_hist<uint16_t>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<15, 14, true>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<15, 14, false>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<14, 16, true>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<14, 16, false>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<13, 7, true>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<13, 7, false>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<12, 14, true>),
+                      reinterpret_cast<const void*>(&k_recode_fixed<12, 14, false>)};
+  for (const void* k : ks)
+    if (f == k) return true;
+  // the narrow recodes too: a replayed graph must not read the previous call's scalars
+  for (uint32_t sw = 1; sw <= 8; sw++)
+    if (f == recode_narrow_fn<uint16_t>(sw) || f == recode_narrow_fn<uint32_t>(sw)) return true;
+  return false;
+}
+
+// Enqueue parts of the device pipeline on `s`; the reduced per-window terms land in the slot's
+// h_out.  `pts` is the point-record buffer (the slot's own, or a shared base vector's).
+// With `acc_events` (eager launches only), k_accumulate runs between the slot's ev_acc0 / ev_acc1
+// (2), or is followed by ev_acc1 alone (1);
+// captured graphs get the same events as record nodes (add_acc_event_nodes).
+int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si,
+                hipStream_t s, int parts, uint32_t* pts, int acc_events = 0) {
+  const MsmDims& d = pl.d;
+  Slot& sl = c->slot[si];
+  Workspace& w = sl.ws;
+  const bool prof = c->profiling == 1;
+  auto mark = [&](int ph) {
+    if (prof) hipEventRecord(c->ev[ph], s);
+  };
+  const uint32_t* total = w.bin_base.as<uint32_t>() + d.nbins;
+  const unsigned rgrid = grid_for(pl.runs_max, ACC_THREADS);
+  // The preparation reads only the points and the sort only the scalars: with both in this
+  // sequence the preparation forks onto the slot's aux stream (a parallel branch of the captured
+  // graph) and rejoins before the accumulation, so a lone MSM's sort no longer waits behind it.
+  // (Profiling mode 1 keeps them in order, one event between every phase.)
+  const bool fork = (parts & PART_PREP) && (parts & PART_SORT) && !prof && slot_forks(sl);
+  auto prepare = [&](hipStream_t ps) {
+    hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(d.n, PP_THREADS), d.shared ? 1 : d.nm), dim3(PP_THREADS), 0, ps,
+                       d_points, pts, d.n, w.err.as<uint32_t>(), prep_nt((size_t)(d.shared ? 1 : d.nm) * d.n), pl.pfmt);
+  };
+  if (parts & PART_PREP) {
+    mark(PH_START);
+    hipStream_t ps = s;
+    if (fork) {
+      HIPCHECK(hipEventRecord(sl.ev_fork, s));
+      HIPCHECK(hipStreamWaitEvent(sl.aux, sl.ev_fork, 0));
+      ps = sl.aux;
+    }
+    prepare(ps);
+    if (fork) HIPCHECK(hipEventRecord(sl.ev_join, sl.aux));
+    mark(PH_PREPARE);
+  }
+  if (parts & PART_SORT) {
+    if (!(parts & PART_PREP)) {
+      mark(PH_START);
+      mark(PH_PREPARE);
+    }
+    launch_recode(d, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), w.err.as<uint32_t>(), s);
+    mark(PH_RECODE);
+    mark(PH_SCAN);
+    if (d.sub != MSM_SUB_NONE) {
+      // a subset launch on a handle's records: the scatter's record-mapping variants, reading the
+      // slot's own index buffer (a fixed address: the captured node never holds a caller's pointer)
+      auto scatter = [&](auto kern, auto* dig) {
+        hipLaunchKernelGGL(kern, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s, dig, d,
+                           w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(), w.bin_base.as<uint32_t>(),
+                           w.part_entry.as<uint32_t>(), w.part_fine.as<uint16_t>(),
+                           static_cast<const uint32_t*>(w.sub_idx.as<uint32_t>()));
+      };
+      const bool ix = d.sub == MSM_SUB_INDEXED;
+      if (d.c <= 16) {
+        const uint16_t* dig = w.digits.as<uint16_t>();
+        if (ix) scatter(k_part_scatter<uint16_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
+        else scatter(k_part_scatter<uint16_t, MSM_SUB_RANGE, const uint32_t*>, dig);
+      } else {
+        const uint32_t* dig = w.digits.as<uint32_t>();
+        if (ix) scatter(k_part_scatter<uint32_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
+        else scatter(k_part_scatter<uint32_t, MSM_SUB_RANGE, const uint32_t*>, dig);
+      }
+    } else if (d.c <= 16) {
+      hipLaunchKernelGGL(k_part_scatter<uint16_t>, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s,
+                         w.digits.as<uint16_t>(), d, w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(),
+                         w.bin_base.as<uint32_t>(), w.part_entry.as<uint32_t>(),
+                         w.part_fine.as<uint16_t>());
+    } else {
+      hipLaunchKernelGGL(k_part_scatter<uint32_t>, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s,
+                         w.digits.as<uint32_t>(), d, w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(),
+                         w.bin_base.as<uint32_t>(), w.part_entry.as<uint32_t>(),
+                         w.part_fine.as<uint16_t>());
+    }
+    mark(PH_SCATTER);
+    hipLaunchKernelGGL(k_fine_sort, dim3(d.nbins), dim3(FS_THREADS), 0, s, w.part_entry.as<uint32_t>(),
+                       w.part_fine.as<uint16_t>(), w.bin_base.as<uint32_t>(), d, pl.K, w.sorted_entry.as<uint32_t>(),
+                       w.bucket_start.as<uint32_t>(), w.run_key.as<uint32_t>(), w.colsum.as<uint32_t>(),
+                       w.bin_cur.as<uint32_t>());
+#ifdef MSM_GAP_KERNEL
+    hipLaunchKernelGGL(k_gap, dim3(MSM_GAP_KERNEL), dim3(64), 0, s, w.err.as<uint32_t>());
+#endif
+    mark(PH_FINE);
+  }
+  if (fork) HIPCHECK(hipStreamWaitEvent(s, sl.ev_join, 0));
+  if ((parts & PART_ACC) && acc_events == 2) HIPCHECK(hipEventRecord(sl.ev_acc0, s));
+  if (parts & PART_ACC) {
+    hipLaunchKernelGGL(k_accumulate, dim3(rgrid), dim3(ACC_THREADS), 0, s, pts, w.sorted_entry.as<uint32_t>(),
+                       w.bucket_start.as<uint32_t>(), w.run_key.as<uint32_t>(), total, pl.K, d.W * d.B,
+                       w.buckets.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.lead_open.as<uint32_t>(),
+                       w.cross_key.as<uint32_t>(), w.skew_list.as<uint32_t>(), w.g_head.as<uint32_t>(),
+                       w.g_hkey.as<uint32_t>(), w.g_tkey.as<uint32_t>());
+    mark(PH_ACCUM);
+  }
+  if ((parts & PART_ACC) && acc_events) HIPCHECK(hipEventRecord(sl.ev_acc1, s));
+  // profiling mode 1 keeps the joins in line (its per-phase timings include them)
+  const bool joins = (parts & PART_JOIN) || prof;
+  if ((parts & PART_POST) && joins) {
+    hipLaunchKernelGGL(k_chain_join, dim3(CJ_GRID), dim3(ACC_THREADS), 0, s, w.skew_list.as<uint32_t>(), total, pl.K,
+                       w.g_head.as<uint32_t>(), w.g_hkey.as<uint32_t>(), w.g_tkey.as<uint32_t>(),
+                       w.buckets.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.lead_open.as<uint32_t>(),
+                       w.lead_flag.as<uint32_t>());
+    hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(LS_THREADS), 0, s, w.lead_val.as<uint32_t>(),
+                       w.lead_open.as<uint32_t>(), w.lead_flag.as<uint32_t>(), total, pl.K);
+  }
+  if (parts & PART_POST) {
+    mark(PH_FIXUP);
+    const bool fold = red_fold() && red2_tree(pl);
+    if (fold) {
+      const uint32_t G = red2_groups(pl);
+      auto red1g = pl.L == 4    ? k_bucket_reduce_1g<4>
+                   : pl.L == 9  ? k_bucket_reduce_1g<9>
+                   : pl.L == 10 ? k_bucket_reduce_1g<10>
+                   : pl.L == 12 ? k_bucket_reduce_1g<12>
+                   : pl.L == 16 ? k_bucket_reduce_1g<16>
+                   : pl.L == 17 ? k_bucket_reduce_1g<17>
+                   : pl.L == 20 ? k_bucket_reduce_1g<20>
+                                : k_bucket_reduce_1g<8>;
+      hipLaunchKernelGGL(red1g, dim3(d.W * G), dim3(RG_CH), 0, s, w.buckets.as<uint32_t>(),
+                         w.bucket_start.as<uint32_t>(), d, pl.K, pl.nchunks, G, w.cross_key.as<uint32_t>(),
+                         w.lead_val.as<uint32_t>(), w.red_G.as<uint32_t>());
+    }
+    const bool pairs = red1_pairs();
+    auto red1 = pl.L == 4    ? (pairs ? k_bucket_reduce_1p<4> : k_bucket_reduce_1<4>)
+                : pl.L == 9  ? (pairs ? k_bucket_reduce_1p<9> : k_bucket_reduce_1<9>)
+                : pl.L == 10 ? (pairs ? k_bucket_reduce_1p<10> : k_bucket_reduce_1<10>)
+                : pl.L == 12 ? (pairs ? k_bucket_reduce_1p<12> : k_bucket_reduce_1<12>)
+                : pl.L == 16 ? (pairs ? k_bucket_reduce_1p<16> : k_bucket_reduce_1<16>)
+                : pl.L == 17 ? (pairs ? k_bucket_reduce_1p<17> : k_bucket_reduce_1<17>)
+                : pl.L == 20 ? (pairs ? k_bucket_reduce_1p<20> : k_bucket_reduce_1<20>)
+                             : (pairs ? k_bucket_reduce_1p<8> : k_bucket_reduce_1<8>);
+    if (!fold)
+    hipLaunchKernelGGL(red1, dim3(grid_for((size_t)d.W * pl.nchunks * (pairs ? 2 : 1), RED1_THREADS)), dim3(RED1_THREADS), 0, s,
+                       w.buckets.as<uint32_t>(), w.bucket_start.as<uint32_t>(), d, pl.K, pl.nchunks,
+                       w.cross_key.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.red_U.as<uint32_t>(),
+                       w.red_T.as<uint32_t>());
+    mark(PH_RED1);
+    if (red2_tree(pl)) {
+      const uint32_t G = red2_groups(pl);
+      if (!fold)
+        hipLaunchKernelGGL(k_red2_groups, dim3(d.W * G), dim3(4 * RG_CH), 0, s, w.red_U.as<uint32_t>(),
+                           w.red_T.as<uint32_t>(), pl.nchunks, G, w.bucket_start.as<uint32_t>(), d.B,
+                           w.red_G.as<uint32_t>());
+      // one lane quad per group point of the widest term (a wave at least): 2^16 pipelined
+      // 0.117-0.120 against 0.125-0.131 ms per MSM with 64 quads throughout
+      uint32_t gp = 16;
+      while (gp < G) gp <<= 1;
+      hipLaunchKernelGGL(k_red2_terms, dim3(d.W * pl.nterms), dim3(4 * gp), 0, s,
+                         w.red_G.as<uint32_t>(), G,
+                         pl.nv, pl.nterms, w.err.as<uint32_t>(), w.lead_flag.as<uint32_t>(),
+                         w.skew_list.as<uint32_t>(), total, joins ? 1u : 0u, w.bucket_start.as<uint32_t>(), d.B,
+                         reinterpret_cast<uint32_t*>(sl.h_out_dev));
+    } else {
+      hipLaunchKernelGGL(k_bucket_reduce_2, dim3(d.W * pl.nterms), dim3(RED2_THREADS), 0, s, w.red_U.as<uint32_t>(),
+                         w.red_T.as<uint32_t>(), pl.nchunks, pl.nv, pl.nterms, w.err.as<uint32_t>(),
+                         w.lead_flag.as<uint32_t>(), w.skew_list.as<uint32_t>(), total, joins ? 1u : 0u,
+                         w.bucket_start.as<uint32_t>(), d.B, reinterpret_cast<uint32_t*>(sl.h_out_dev));
+    }
+    mark(PH_RED2);
+    mark(PH_READBACK);
+  }
+  HIPCHECK(hipGetLastError());
+  return MSM_OK;
+}
+
+// Bracket the captured k_accumulate node with event-record nodes (the slot's ev_acc0 / ev_acc1):
+// every replay of the graph then times the accumulation, with no extra launches.
+int add_acc_event_nodes(hipGraph_t g, Slot& sl, bool both) {
+  size_t num = 0;
+  if (hipGraphGetNodes(g, nullptr, &num) != hipSuccess || num == 0) return MSM_ERR_HIP;
+  std::vector<hipGraphNode_t> nodes(num);
+  if (hipGraphGetNodes(g, nodes.data(), &num) != hipSuccess) return MSM_ERR_HIP;
+  const void* f_acc = reinterpret_cast<const void*>(&k_accumulate);
+  hipGraphNode_t acc = nullptr;
+  for (hipGraphNode_t nd : nodes) {
+    hipGraphNodeType ty;
+    hipKernelNodeParams kp{};
+    if (hipGraphNodeGetType(nd, &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
+        hipGraphKernelNodeGetParams(nd, &kp) == hipSuccess && kp.func == f_acc)
+      acc = nd;
+  }
+  if (!acc) return MSM_ERR_HIP;
+  size_t nd = 0, nx = 0;
+  if (hipGraphNodeGetDependencies(acc, nullptr, &nd) != hipSuccess ||
+      hipGraphNodeGetDependentNodes(acc, nullptr, &nx) != hipSuccess)
+    return MSM_ERR_HIP;
+  std::vector<hipGraphNode_t> deps(nd), outs(nx);
+  if ((nd && hipGraphNodeGetDependencies(acc, deps.data(), &nd) != hipSuccess) ||
+      (nx && hipGraphNodeGetDependentNodes(acc, outs.data(), &nx) != hipSuccess))
+    return MSM_ERR_HIP;
+  hipGraphNode_t r0 = nullptr, r1 = nullptr;
+  if (both) {
+    for (hipGraphNode_t d : deps)
+      if (hipGraphRemoveDependencies(g, &d, &acc, 1) != hipSuccess) return MSM_ERR_HIP;
+    if (hipGraphAddEventRecordNode(&r0, g, deps.data(), deps.size(), sl.ev_acc0) != hipSuccess ||
+        hipGraphAddDependencies(g, &r0, &acc, 1) != hipSuccess)
+      return MSM_ERR_HIP;
+  }
+  for (hipGraphNode_t o : outs)
+    if (hipGraphRemoveDependencies(g, &acc, &o, 1) != hipSuccess) return MSM_ERR_HIP;
+  if (hipGraphAddEventRecordNode(&r1, g, &acc, 1, sl.ev_acc1) != hipSuccess) return MSM_ERR_HIP;
+  for (hipGraphNode_t o : outs)
+    if (hipGraphAddDependencies(g, &r1, &o, 1) != hipSuccess) return MSM_ERR_HIP;
+  return MSM_OK;
+}
+
+int capture(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si, hipStream_t s,
+            int parts, uint32_t* pts, int acc_events, hipGraph_t* gout, hipGraphExec_t* out) {
+  hipGraph_t g = nullptr;
+  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return MSM_ERR_HIP;
+  int rc = enqueue_msm(c, pl, d_points, d_scalars, si, s, parts, pts);
+  hipError_t e = hipStreamEndCapture(s, &g);
+  if (rc != MSM_OK || e != hipSuccess || !g) {
+    if (g) hipGraphDestroy(g);
+    (void)hipGetLastError();
+    return MSM_ERR_HIP;
+  }
+  if (acc_events && (parts & PART_ACC) && add_acc_event_nodes(g, c->slot[si], acc_events == 2) != MSM_OK) {
+    hipGraphDestroy(g);
+    (void)hipGetLastError();
+    return MSM_ERR_HIP;
+  }
+  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  if (e != hipSuccess) {
+    hipGraphDestroy(g);
+    *out = nullptr;
+    (void)hipGetLastError();
+    return MSM_ERR_HIP;
+  }
+  *gout = g;
+  return MSM_OK;
+}
+
+// Find the input-reading kernel nodes of a segment so later launches can repoint them.
+int find_input_nodes(Segment& sg) {
+  size_t num = 0;
+  if (hipGraphGetNodes(sg.graph, nullptr, &num) != hipSuccess || num == 0) return MSM_ERR_HIP;
+  std::vector<hipGraphNode_t> nodes(num);
+  if (hipGraphGetNodes(sg.graph, nodes.data(), &num) != hipSuccess) return MSM_ERR_HIP;
+  const void* f_prep = reinterpret_cast<const void*>(&k_prepare_points);
+  for (hipGraphNode_t nd : nodes) {
+    hipGraphNodeType ty;
+    if (hipGraphNodeGetType(nd, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
+    hipKernelNodeParams kp{};
+    if (hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess) continue;
+    if (kp.func == f_prep) {
+      sg.n_prep = nd;
+      sg.p_prep = kp;
+    } else if (is_recode_kernel(kp.func)) {
+      sg.n_recode = nd;
+      sg.p_recode = kp;
+    }
+  }
+  const bool ok = (!(sg.parts & PART_PREP) || sg.n_prep) && (!(sg.parts & PART_SORT) || sg.n_recode);
+  return ok ? MSM_OK : MSM_ERR_HIP;
+}
+
+bool same_ptrs(const BatchPtrs& a, const BatchPtrs& b) { return memcmp(&a, &b, sizeof(BatchPtrs)) == 0; }
+
+// Point an instantiated segment at new input buffers (kernel-node argument update, no
+// re-capture).
+int repoint_inputs(const Plan& pl, Slot& sl, Segment& sg, const BatchPtrs& d_points, const BatchPtrs& d_scalars) {
+  const MsmDims& d = pl.d;
+  Workspace& w = sl.ws;
+  if (sg.n_prep && !same_ptrs(sg.in_pts, d_points)) {
+    BatchPtrs wire = d_points;
+    uint32_t* ptsb = const_cast<uint32_t*>(sg.pts_buf);
+    uint32_t n = d.n;
+    uint32_t* err = w.err.as<uint32_t>();
+    uint32_t nt = prep_nt((size_t)(d.shared ? 1 : d.nm) * d.n);
+    uint32_t fmt = pl.pfmt;
+    void* a_prep[] = {&wire, &ptsb, &n, &err, &nt, &fmt};
+    hipKernelNodeParams kp = sg.p_prep;
+    kp.kernelParams = a_prep;
+    kp.extra = nullptr;
+    if (hipGraphExecKernelNodeSetParams(sg.exec, sg.n_prep, &kp) != hipSuccess) return MSM_ERR_HIP;
+    sg.in_pts = d_points;
+  }
+  if (sg.n_recode && !same_ptrs(sg.in_sc, d_scalars)) {
+    BatchPtrs scal = d_scalars;
+    MsmDims dd = d;
+    void* digits = w.digits.p;
+    uint32_t* hist = w.colsum.as<uint32_t>();
+    // (k_recode_narrow takes two more arguments; the other recodes read the first four)
+    NarrowBias nb = d.sw ? narrow_bias(d) : NarrowBias{};
+    uint32_t* err = w.err.as<uint32_t>();
+    void* a_rc[] = {&scal, &dd, &digits, &hist, &nb, &err};
+    hipKernelNodeParams kr = sg.p_recode;
+    kr.kernelParams = a_rc;
+    kr.extra = nullptr;
+    if (hipGraphExecKernelNodeSetParams(sg.exec, sg.n_recode, &kr) != hipSuccess) return MSM_ERR_HIP;
+    sg.in_sc = d_scalars;
+  }
+  return MSM_OK;
+}
+
+// The cached graph of `parts` for this plan (captured on first use, least recently used segment
+// evicted), repointed at the launch's inputs; nullptr when graphs are unavailable.
+Segment* get_segment(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si,
+                     int parts, uint32_t* pts, int acc_events) {
+  Slot& sl = c->slot[si];
+  const uint64_t gen = g_alloc_gen.load();
+  Segment* hit = nullptr;
+  for (Segment& sg : sl.seg)
+    if (sg.exec && sg.parts == parts && sg.pts_buf == pts && sg.acc_events == acc_events && sg.gen == gen &&
+        sg.fork == slot_forks(sl) && plan_eq(sg.pl, pl))
+      hit = &sg;
+  if (!hit) {
+    Segment* victim = &sl.seg[0];
+    for (Segment& sg : sl.seg) {
+      if (!sg.exec || sg.gen != gen) {
+        victim = &sg;
+        break;
+      }
+      if (sg.used < victim->used) victim = &sg;
+    }
+    victim->drop();
+    victim->pl = pl;
+    victim->parts = parts;
+    victim->pts_buf = pts;
+    victim->acc_events = acc_events;
+    victim->fork = slot_forks(sl);
+    victim->gen = gen;
+    int rc = capture(c, pl, d_points, d_scalars, si, sl.stream, parts, pts, acc_events, &victim->graph,
+                     &victim->exec);
+    if (rc == MSM_OK) rc = find_input_nodes(*victim);
+    if (rc != MSM_OK) {
+      victim->drop();
+      // event-record nodes unsupported: time k_accumulate eagerly between graph segments;
+      // otherwise capture itself is unsupported here: stay eager
+      if (acc_events) c->graph_events_ok = false;
+      else c->graphs_ok = false;
+      return nullptr;
+    }
+    victim->in_pts = d_points;
+    victim->in_sc = d_scalars;
+    hit = victim;
+  }
+  if (repoint_inputs(pl, sl, *hit, d_points, d_scalars) != MSM_OK) {
+    hit->drop();
+    (void)hipGetLastError();
+    c->graphs_ok = false;
+    return nullptr;
+  }
+  hit->used = ++sl.seg_clock;
+  return hit;
+}
+
+// Enqueue `parts` of one launch in slot `si` (on the slot's stream) by replaying the captured
+// graph of those parts; k_accumulate runs between the slot's two timing events on every launch
+// (event-record nodes inside the graph), so the production path is the timed one.  Where the
+// runtime cannot capture event records, the accumulation is launched eagerly between a graph of
+// the parts before it and one of the parts after it.  Profiling mode 1 launches everything
+// eagerly with an event between every phase.
+int launch_on(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si, int parts,
+              uint32_t* pts, hipStream_t s) {
+  // k_accumulate's bracketing events only when profiling mode 2 reads them: each event-record
+  // node adds ~6 us to the launch sequence's critical path (profiles/r3/latency_timeline.txt)
+  // (a staggered slot's graphs also record ev_acc1 after k_accumulate: the next launch waits on it)
+  const int acc = (parts & PART_ACC) == 0 ? 0 : c->profiling == 2 ? 2 : c->slot[si].stagger ? 1 : 0;
+  if (parts & PART_ACC) c->slot[si].acc_timed = acc == 2;
+  if (c->profiling == 1) {
+    c->slot[si].acc_timed = false;
+    if (int rc = enqueue_msm(c, pl, d_points, d_scalars, si, s, parts, pts)) return rc;
+  } else if (c->graphs_ok && graphs_enabled()) {
+    Segment* sg = (!acc || c->graph_events_ok) ? get_segment(c, pl, d_points, d_scalars, si, parts, pts, acc) : nullptr;
+    if (sg) {
+      HIPCHECK(hipGraphLaunch(sg->exec, s));
+    } else {
+      auto run = [&](int p) -> int {
+        if (!p) return MSM_OK;
+        Segment* g = c->graphs_ok ? get_segment(c, pl, d_points, d_scalars, si, p, pts, false) : nullptr;
+        if (g) {
+          HIPCHECK(hipGraphLaunch(g->exec, s));
+          return MSM_OK;
+        }
+        return enqueue_msm(c, pl, d_points, d_scalars, si, s, p, pts);
+      };
+      if (int rc = run(parts & (PART_PREP | PART_SORT))) return rc;
+      if (parts & PART_ACC)
+        if (int rc = enqueue_msm(c, pl, d_points, d_scalars, si, s, PART_ACC, pts, acc)) return rc;
+      if (int rc = run(parts & (PART_POST | PART_JOIN))) return rc;
+    }
+  } else if (int rc = enqueue_msm(c, pl, d_points, d_scalars, si, s, parts, pts, acc)) {
+    return rc;
+  }
+  return MSM_OK;
+}
+
+int launch_parts(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si,
+                 int parts, uint32_t* pts) {
+  Slot& sl = c->slot[si];
+  hipStream_t s = sl.stream;
+  if (c->profiling && (parts & (PART_PREP | PART_SORT))) HIPCHECK(hipEventRecord(sl.ev_start, s));
+  if (int rc = launch_on(c, pl, d_points, d_scalars, si, parts, pts, s)) return rc;
+  if (parts & PART_POST) {
+    if (c->profiling) HIPCHECK(hipEventRecord(sl.ev_end, s));
+    HIPCHECK(hipEventRecord(sl.ev_done, s));
+  }
+  return MSM_OK;
+}
+
+// Wait for the launch in slot `si` (spinning briefly: the result is usually due within a couple of
+// milliseconds, and a blocking wait adds a wake-up latency) and check its flags; its window terms
+// are then in the slot's h_out.  Skewed scalars: the sequence ran without the bucket joins
+// (PART_JOIN), so they and the reduction run again here (the slot's stream is idle: its next launch
+// is enqueued afterwards).
+int wait_slot(DevCtx* c, int si, uint32_t* total_out = nullptr) {
+  Slot& sl = c->slot[si];
+  const Plan& pl = sl.pl;
+  const auto spin_until = clk::now() + std::chrono::milliseconds(50);
+  hipError_t q;
+  while ((q = hipEventQuery(sl.ev_done)) == hipErrorNotReady && clk::now() < spin_until) _mm_pause();
+  if (q == hipErrorNotReady) q = hipEventSynchronize(sl.ev_done);
+  HIPCHECK(q);
+  const size_t outb = (size_t)pl.d.W * pl.nterms * 32 * 4;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(sl.h_out.p);
+  const uint32_t err = h[outb / 4];
+  if (total_out) *total_out = h[outb / 4 + 1];
+  if (h[outb / 4 + 2]) {
+    // only the second k_bucket_reduce_2 clears the skew list and the lead flag: if the re-run
+    // cannot be enqueued or does not complete, clear them here, or the slot's next MSM would append
+    // to a stale skew list and rejoin stale workgroups without any error
+    int rc = enqueue_msm(c, pl, BatchPtrs{}, BatchPtrs{}, si, sl.stream, PART_JOIN | PART_POST, nullptr);
+    if (rc == MSM_OK && (hipEventRecord(sl.ev_done, sl.stream) != hipSuccess ||
+                         hipEventSynchronize(sl.ev_done) != hipSuccess))
+      rc = MSM_ERR_HIP;
+    if (rc != MSM_OK) {
+      (void)hipGetLastError();
+      hipMemsetAsync(sl.ws.skew_list.p, 0, 4, sl.stream);
+      hipMemsetAsync(sl.ws.lead_flag.p, 0, sl.ws.lead_flag.cap, sl.stream);
+      hipStreamSynchronize(sl.stream);
+      return rc;
+    }
+  }
+  if (err & MSM_DEV_ERR_COORD_RANGE) return MSM_ERR_COORD_RANGE;
+  if (err & MSM_DEV_ERR_BAD_POINT) return MSM_ERR_BAD_POINT;
+  if (err & MSM_DEV_ERR_BAD_INDEX) return MSM_ERR_INVALID_ARG;  // a device-entry subset's index >= n
+  if (err & MSM_DEV_ERR_SCALAR_RANGE) return MSM_ERR_INVALID_ARG;  // a narrow scalar's bit at or above scalar_bits
+  return MSM_OK;
+}
+
+int finish_msm(DevCtx* c, int si, Pt* result, std::vector<uint32_t>* terms = nullptr, TailCrew* crew = nullptr) {
+  Slot& sl = c->slot[si];
+  const Plan& pl = sl.pl;
+  uint32_t total = 0;
+  if (int rc = wait_slot(c, si, &total)) return rc;
+  const size_t outb = (size_t)pl.d.W * pl.nterms * 32 * 4;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(sl.h_out.p);
+  auto t0 = clk::now();
+  if (terms)
+    terms->assign(h, h + outb / 4);
+  else if (crew && crew->active())
+    *result = crew->run(pl, h);
+  else
+    *result = horner_tail(pl, h);
+  auto t1 = clk::now();
+  if (c->profiling == 1 || (c->profiling == 2 && sl.acc_timed)) {
+    float ms[PH_COUNT] = {};
+    msm_profile_t& P = c->last;
+    if (c->profiling == 1) {
+      for (int i = 1; i < PH_COUNT; i++) hipEventElapsedTime(&ms[i], c->ev[i - 1], c->ev[i]);
+      hipEventElapsedTime(&P.device_total, c->ev[PH_START], c->ev[PH_READBACK]);
+    } else {
+      hipEventElapsedTime(&ms[PH_ACCUM], sl.ev_acc0, sl.ev_acc1);
+      hipEventElapsedTime(&P.device_total, sl.ev_start, sl.ev_end);
+    }
+    P.prepare_points = ms[PH_PREPARE];
+    P.recode_count = ms[PH_RECODE];
+    P.coarse_scan = ms[PH_SCAN];
+    P.coarse_scatter = ms[PH_SCATTER];
+    P.fine_sort = ms[PH_FINE];
+    P.accumulate = ms[PH_ACCUM];
+    P.fixup = ms[PH_FIXUP];
+    P.bucket_reduce_1 = ms[PH_RED1];
+    P.bucket_reduce_2 = ms[PH_RED2];
+    P.readback = ms[PH_READBACK];
+    P.host_tail = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    P.entries = total;
+    P.window_bits = pl.d.c;
+    P.windows = pl.d.Wr;
+    P.run_length = pl.K;
+    P.chunk_len = pl.L;
+    P.msms_per_launch = pl.d.nm;
+    P.accumulate_sum += P.accumulate;
+    P.device_total_sum += P.device_total;
+    P.profiled++;
+    if (c->profiling == 2) {
+      float a = 0, b = 0;
+      if (hipEventElapsedTime(&a, c->ev_base, sl.ev_acc0) == hipSuccess &&
+          hipEventElapsedTime(&b, c->ev_base, sl.ev_acc1) == hipSuccess)
+        c->acc_ivals.emplace_back(a, b);
+    }
+  }
+  return MSM_OK;
+}
+
+BatchPtrs splat(const uint32_t* p) {
+  BatchPtrs b{};
+  for (uint32_t m = 0; m < MSM_MAX_BATCH; m++) b.p[m] = p;
+  return b;
+}
+
+// The caller's stream (if any) -> every slot stream about to be used waits for its work so far.
+int order_after_user(DevCtx* c, hipStream_t user, int nslot) {
+  if (!user) return MSM_OK;
+  HIPCHECK(hipEventRecord(c->ev_user, user == (hipStream_t)MSM_STREAM_NULL ? nullptr : user));
+  for (int si = 0; si < nslot; si++) HIPCHECK(hipStreamWaitEvent(c->slot[si].stream, c->ev_user, 0));
+  return MSM_OK;
+}
+
+// Before an error return once something is queued: wait for the copy stream and the streams of slots
+// [0, nslot), then hand back `code`.  The copies read the caller's arrays, which msm.h promises are
+// not read after the call returns.
+int drain_streams(DevCtx* c, int nslot, int code) {
+  hipStreamSynchronize(c->copy_stream);
+  for (int si = 0; si < nslot; si++) hipStreamSynchronize(c->slot[si].stream);
+  return code;
+}
+
+// The host tail of a lone MSM in slot `si`, over the device context's persistent helpers: armed
+// right after the launch (they spin while the device works), handed the terms when they land.
+int finish_lone(DevCtx* c, int si, Pt* result) {
+  TailCrew* crew = ctx_crew(c);
+  crew->arm();
+  const int rc = finish_msm(c, si, result, nullptr, crew);
+  if (rc != MSM_OK) crew->disarm();  // no terms will come
+  return rc;
+}

@@ -1,0 +1,496 @@
+// Layer 12, the msm_test_* hooks (not in msm.h) and their helpers.  Included last: it may use every layer,
+// and only msm_shutdown (stopping the hooks' pools) uses it.
+#pragma once
+namespace {
+
+// Pools the CPU test hooks start (msm_test_pack, msm_test_pools), stopped by msm_shutdown too.
+struct TestPools {
+  PackPool* packer = nullptr;
+  TailCrew* crew = nullptr;
+  HornerPool* pool = nullptr;
+  void stop() {
+    delete packer;
+    delete crew;
+    delete pool;
+    packer = nullptr;
+    crew = nullptr;
+    pool = nullptr;
+  }
+};
+std::mutex g_test_mu;
+TestPools g_test_pools;
+
+// ---- helpers of the device test hooks (msm_test_field_op .. msm_test_records) -------------------
+// A device buffer of one hook call: freed when the call returns, on its HIPCHECK exits too.
+struct TestBuf {
+  uint32_t* p = nullptr;
+  TestBuf() = default;
+  TestBuf(const TestBuf&) = delete;
+  TestBuf& operator=(const TestBuf&) = delete;
+  ~TestBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+
+// One k_test_limbs* instantiation per LimbOp (msm_kernels.hip), picked by the runtime op.
+template <int OP>
+void launch_limb_op(const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  const dim3 g(grid_for(n, 256)), t(256);
+  if constexpr (OP == LOP_PT_QUAD)
+    hipLaunchKernelGGL(k_test_limbs_quad, dim3(grid_for(4 * (size_t)n, 256)), t, 0, 0, a, b, out, n);
+  else if constexpr (OP >= LOP_PT_ADD)
+    hipLaunchKernelGGL(k_test_limbs_point<OP>, g, t, 0, 0, a, b, neg, out, n);
+  else
+    hipLaunchKernelGGL(k_test_limbs<OP>, g, t, 0, 0, a, b, out, n);
+}
+template <int... OPS>
+void dispatch_limb_op(int op, std::integer_sequence<int, OPS...>, const uint32_t* a, const uint32_t* b,
+                      const uint32_t* neg, uint32_t* out, uint32_t n) {
+  ((op == OPS ? launch_limb_op<OPS>(a, b, neg, out, n) : (void)0), ...);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- test hooks (not in msm.h) ----
+// The device-list shard split (tests/test_host_logic.py checks it against msm_amd.dist).
+int msm_test_shard_range(size_t n, size_t i, size_t D, size_t* lo, size_t* hi) {
+  if (!lo || !hi || D == 0 || i >= D) return MSM_ERR_INVALID_ARG;
+  shard_range(n, i, D, lo, hi);
+  return MSM_OK;
+}
+
+// The sharded paths with a list that may repeat a device (the one-GPU box has no second device):
+// mode 0 = msm_compute (host inputs), 1 = msm_compute_device; affine result.
+int msm_test_sharded(int mode, const uint32_t* points, const uint32_t* scalars, size_t n, const msm_opts* opts,
+                     const int32_t* devices, uint32_t n_devices, void* hip_stream, uint32_t out_xy_be[16]) {
+  if (!opts || !devices || !n_devices || n_devices > MSM_MAX_DEVICES || !out_xy_be) return MSM_ERR_INVALID_ARG;
+  std::vector<int> devs(devices, devices + n_devices);
+  for (int d : devs) {
+    DevCtx* c;
+    if (int rc = get_ctx(d, &c)) return rc;
+  }
+  Pt r;
+  const int rc = mode == 0 ? sharded_host(points, scalars, n, opts, devs, &r)
+                           : sharded_device(points, scalars, n, opts, hip_stream, devs, &r);
+  if (rc != MSM_OK) return rc;
+  pt_to_be_affine(r, out_xy_be);
+  return MSM_OK;
+}
+
+// Peer access of device `dev` to `owner` (enabled on first use, as peer_shard does): 1 enabled
+// (or dev == owner), 0 unavailable, MSM_ERR_INVALID_ARG for a non-gfx950 ordinal.
+int msm_test_peer_state(int dev, int owner) {
+  DevCtx *a, *b;
+  if (get_ctx(dev, &a) != MSM_OK || get_ctx(owner, &b) != MSM_OK) return MSM_ERR_INVALID_ARG;
+  DeviceGuard g(dev);
+  return enable_peer(dev, owner);
+}
+
+// The host tail of a lone MSM of n points (auto plan) on caller-supplied window terms (host
+// Montgomery X|Y|T|Z words, the layout k_bucket_reduce_2 writes): helpers = 0 runs horner_tail,
+// otherwise the TailCrew.  Affine result; *ms = the tail's wall time.
+// helpers < 0: one crew of -helpers threads over 40 rounds (the persistent crew of a device
+// context), every third round armed and disarmed without terms first (an error return); the
+// result of the last round, MSM_ERR_INVALID_ARG if any round disagrees with the first.
+int msm_test_tail(size_t n, const uint32_t* terms, int helpers, uint32_t out_xy_be[16], double* ms) {
+  Plan pl;
+  if (int rc = make_plan(n, nullptr, DevShape{}, &pl)) return rc;
+  const int rounds = helpers < 0 ? 40 : 1;
+  TailCrew crew(helpers < 0 ? -helpers : helpers);
+  Pt first{}, r{};
+  bool same = true;
+  const auto t0 = clk::now();
+  for (int k = 0; k < rounds; k++) {
+    if (helpers < 0 && k % 3 == 1) {
+      crew.arm();
+      crew.disarm();
+    }
+    crew.arm();
+    r = helpers ? crew.run(pl, terms) : horner_tail(pl, terms);
+    crew.disarm();
+    if (k == 0) first = r;
+    same = same && fq_eq(fq_mul(r.X, first.Z), fq_mul(first.X, r.Z)) && fq_eq(fq_mul(r.Y, first.Z), fq_mul(first.Y, r.Z));
+  }
+  *ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count() / rounds;
+  pt_to_be_affine(r, out_xy_be);
+  return same ? MSM_OK : MSM_ERR_INVALID_ARG;
+}
+
+// Host field / curve timings (ns per operation, dependent chains): what 0 = fq_mul, 1 = one
+// doubling of pt_dbl_n, 2 = pt_add, 3 = fq_inv.  For sizing the host tail.
+int msm_test_host_timing(int what, size_t iters, double* ns) {
+  if (!ns || iters == 0 || what < 0 || what > 4) return MSM_ERR_INVALID_ARG;
+  if (what == 4) {  // self-check: binary-Euclid fq_inv against a^(p-2) on iters pseudo-random a
+    uint64_t st = 0x9E3779B97F4A7C15ull, bad = 0;
+    for (size_t i = 0; i < iters; i++) {
+      uint64_t s[4];
+      for (int j = 0; j < 4; j++) {
+        st = st * 6364136223846793005ull + 1442695040888963407ull;
+        s[j] = st ^ (st >> 29);
+      }
+      s[3] &= (i & 1) ? 0x0fffffffffffffffull : 0x000000000000ffffull;  // full-width and short
+      if (i == 0) s[0] = 1, s[1] = s[2] = s[3] = 0;
+      if (i == 1) s[0] = P[0] - 1, s[1] = P[1], s[2] = P[2], s[3] = P[3];
+      const Fq a = fq_from_std(s);
+      const Fq x = fq_inv(a);
+      bad += !fq_eq(x, fq_inv_pow(a)) || !fq_eq(fq_mul(x, a), fq_one());
+    }
+    bad += !fq_is_zero(fq_inv(fq_zero()));
+    *ns = (double)bad;
+    return MSM_OK;
+  }
+  Pt p = pt_identity();
+  p.X = fq_one();
+  p.Y = fq_add(fq_one(), fq_one());
+  p.T = fq_add(p.Y, fq_one());
+  p.Z = fq_add(p.T, fq_one());
+  Fq a = p.Z;
+  const auto t0 = clk::now();
+  for (size_t i = 0; i < iters; i++) {
+    if (what == 0) a = fq_mul(a, a);
+    else if (what == 1) p = pt_dbl_n(p, 1);
+    else if (what == 2) p = pt_add(p, p);
+    else a = fq_inv(a);
+  }
+  *ns = std::chrono::duration<double, std::nano>(clk::now() - t0).count() / (double)iters;
+  volatile uint64_t sink = a.l[0] ^ p.X.l[0];
+  (void)sink;
+  return MSM_OK;
+}
+
+// The number of window-term words msm_test_tail reads for n points.
+// msm_test_tail over k MSMs' terms at once (k blocks of msm_test_tail_words(n) words), as the last
+// launch of a pipelined run finishes: helpers > 0 runs TailCrew::run_batch on a crew of that many
+// threads, helpers = 0 one horner_tail per MSM.  out_xy_be: k affine results (16 words each).
+int msm_test_tail_batch(size_t n, uint32_t k, const uint32_t* terms, int helpers, uint32_t* out_xy_be, double* ms) {
+  if (!terms || !out_xy_be || !ms || k < 1 || k > MSM_MAX_BATCH || helpers < 0) return MSM_ERR_INVALID_ARG;
+  Plan pl;
+  if (int rc = make_plan(n, nullptr, DevShape{}, &pl)) return rc;
+  TailCrew crew(helpers);
+  Pt r[MSM_MAX_BATCH];
+  const auto t0 = clk::now();
+  if (helpers) {
+    crew.arm();
+    crew.run_batch(pl, terms, k, r);
+  } else {
+    for (uint32_t m = 0; m < k; m++) r[m] = horner_tail(pl, terms, m);
+  }
+  *ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  for (uint32_t m = 0; m < k; m++) pt_to_be_affine(r[m], out_xy_be + 16 * m);
+  return MSM_OK;
+}
+
+// The launch plan make_plan builds for n points, nm MSMs per launch, pipelined or lone, with
+// `opts` (window width / range; may be null): out = {c (widest window), windows in the launch per
+// MSM (Wr), run length K, reduction chunk L, MSMs per launch, coarse bins per window, skew floor
+// of K}, for the default device shape (256 CUs, 4 accumulation waves per SIMD).
+int msm_test_plan(size_t n, uint32_t nm, int pipelined, const msm_opts* opts, uint32_t out[7]) {
+  if (!out || nm < 1 || nm > MSM_MAX_BATCH) return MSM_ERR_INVALID_ARG;
+  Plan pl;
+  if (int rc = make_plan(n, opts, DevShape{}, &pl, pipelined != 0, nm)) return rc;
+  const uint32_t v[7] = {pl.d.c, pl.d.Wr, pl.K, pl.L, pl.d.nm, pl.d.nbc, run_length_skew_floor(pl.d)};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// The host packing of the packed uploads (pack_records over a pool of MSM_HOST_PACK_THREADS):
+// n wire records -> out (16 words per point for fmt 1 = x|y, 24 for fmt 2 = x|y|z); *all_z_one =
+// whether every z is 1, *t_bad = whether some t >= p.  Host code only (no device needed).
+// The host thread pools a call over `ndev` devices runs per device context (CPU test hook,
+// no device needed): out[0] the CPU budget (host_threads: hardware threads capped by the cgroup
+// quota), out[1..3] packing threads (the caller included), lone-MSM tail helpers and pipelined-tail
+// threads per device, out[4] the threads the library adds for the whole call -- per device its
+// packing workers, helpers, tail threads and one uploader, plus a host thread per device but the
+// first.  With `run` the three pools are started at those sizes (replacing the previous set), given
+// one job each, and left parked until the next call or msm_shutdown.
+int msm_test_pools(int ndev, int run, int* out) {
+  if (ndev < 1 || ndev > 64 || !out) return MSM_ERR_INVALID_ARG;
+  const int own = t_call_devices;
+  t_call_devices = ndev;
+  const int pk = pack_threads(), th = tail_helpers(), hn = horner_threads();
+  t_call_devices = own;
+  out[0] = (int)host_threads();
+  out[1] = pk;
+  out[2] = th;
+  out[3] = hn;
+  out[4] = ndev * ((pk - 1) + th + hn + 1) + (ndev - 1);
+  if (!run) return MSM_OK;
+  std::lock_guard<std::mutex> lk(g_test_mu);
+  g_test_pools.stop();
+  g_test_pools.packer = new PackPool(pk);
+  g_test_pools.crew = new TailCrew(th);
+  g_test_pools.pool = hn ? new HornerPool(hn) : nullptr;
+  std::atomic<int> hits{0};
+  g_test_pools.packer->run([&](int, int) { hits.fetch_add(1); });
+  if (g_test_pools.pool) {
+    for (int i = 0; i < 2 * hn; i++) g_test_pools.pool->push([&] { hits.fetch_add(1); });
+    g_test_pools.pool->wait_all();
+  }
+  g_test_pools.crew->arm();  // the helpers wake and spin, then go back to sleep
+  g_test_pools.crew->disarm();
+  return hits.load() == pk + 2 * hn ? MSM_OK : MSM_ERR_HIP;
+}
+
+int msm_test_pack(const uint32_t* wire, size_t n, uint32_t fmt, uint32_t* out, int* all_z_one, int* t_bad) {
+  if ((!wire || !out) && n) return MSM_ERR_INVALID_ARG;
+  if (fmt != PT_FMT_XY && fmt != PT_FMT_XYZ) return MSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(g_test_mu);
+  PackPool*& pool = g_test_pools.packer;
+  if (!pool) pool = new PackPool(pack_threads());
+  const size_t bytes = n * pt_fmt_slots(fmt) * 16;
+  void* tmp = aligned_alloc(64, (bytes + 63) / 64 * 64 + 64);  // the nontemporal stores want 32-B alignment
+  if (!tmp) return MSM_ERR_OOM;
+  bool tb = false;
+  const bool z1 = pack_records(*pool, static_cast<uint32_t*>(tmp), wire, n, fmt, &tb);
+  memcpy(out, tmp, bytes);
+  free(tmp);
+  if (all_z_one) *all_z_one = z1 ? 1 : 0;
+  if (t_bad) *t_bad = tb ? 1 : 0;
+  return MSM_OK;
+}
+
+size_t msm_test_tail_words(size_t n) {
+  Plan pl;
+  if (make_plan(n, nullptr, DevShape{}, &pl)) return 0;
+  return (size_t)pl.d.W * pl.nterms * 32;
+}
+
+// Batch field / point ops on the device, canonical LE words.
+int msm_test_field_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf da, db, dout;  // freed on every return path
+  HIPCHECK(da.alloc(n * 32 + 32));
+  HIPCHECK(db.alloc(n * 32 + 32));
+  HIPCHECK(dout.alloc(n * 32 + 32));
+  HIPCHECK(hipMemcpy(da.p, a, n * 32, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(db.p, b, n * 32, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_field, dim3(grid_for(n, 256)), dim3(256), 0, 0, da.p, db.p, dout.p, (uint32_t)n, op);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+int msm_test_point_op(uint32_t op, const uint32_t* p, const uint32_t* q, uint32_t* out, size_t n) {
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf dp, dq, dout;
+  HIPCHECK(dp.alloc(n * 64 + 64));
+  HIPCHECK(dq.alloc(n * 64 + 64));
+  HIPCHECK(dout.alloc(n * 128 + 128));
+  HIPCHECK(hipMemcpy(dp.p, p, n * 64, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(dq.p, q, n * 64, hipMemcpyHostToDevice));
+  if (op == 3)
+    hipLaunchKernelGGL(k_test_quad, dim3(grid_for(4 * n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
+  else if (op == 0)
+    hipLaunchKernelGGL(k_test_point<0>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
+  else if (op == 1)
+    hipLaunchKernelGGL(k_test_point<1>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
+  else
+    hipLaunchKernelGGL(k_test_point<2>, dim3(grid_for(n, 256)), dim3(256), 0, 0, dp.p, dq.p, dout.p, (uint32_t)n);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, n * 128, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// ---- raw-limb hooks (msm_kernels.hip k_test_limbs*, tests/test_gpu_limbs.py) --------------------
+// The four WIDE_* masks this library was built with (fp29.cuh; all 0 under MSM_NARROW_DIGITS).
+int msm_test_wide_masks(uint32_t out[4]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  out[0] = WIDE_ALL;
+  out[1] = WIDE_GH;
+  out[2] = WIDE_EH;
+  out[3] = WIDE_EF;
+  return MSM_OK;
+}
+
+// out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
+// msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
+int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {
+  if (op >= (uint32_t)LOP_COUNT || n == 0 || n > (1u << 24) || !a || !out) return MSM_ERR_INVALID_ARG;
+  const size_t wa = limb_op_in_words((int)op), wb = limb_op_b_words((int)op), wo = limb_op_out_words((int)op);
+  if ((wb && !b) || (op == (uint32_t)LOP_PT_MADD && !neg)) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf da, db, dn, dout;
+  HIPCHECK(da.alloc(n * wa * 4));
+  HIPCHECK(db.alloc(n * (wb ? wb : 1) * 4));
+  HIPCHECK(dn.alloc(n * 4));
+  HIPCHECK(dout.alloc(n * wo * 4));
+  HIPCHECK(hipMemcpy(da.p, a, n * wa * 4, hipMemcpyHostToDevice));
+  if (wb) HIPCHECK(hipMemcpy(db.p, b, n * wb * 4, hipMemcpyHostToDevice));
+  if (op == (uint32_t)LOP_PT_MADD) HIPCHECK(hipMemcpy(dn.p, neg, n * 4, hipMemcpyHostToDevice));
+  dispatch_limb_op((int)op, std::make_integer_sequence<int, LOP_COUNT>{}, da.p, db.p, dn.p, dout.p, (uint32_t)n);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, n * wo * 4, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// k_prepare_points on n input points (fmt: PT_FMT_WIRE 32, PT_FMT_XY 16 or PT_FMT_XYZ 24 BE words
+// each) -> the n 32-word records and the device error word; then, for m > 0, the accumulation's
+// gather and add on them: out[j] = acc[j] + record(ents[j]), ents[j] = index << 1 | sign.
+int msm_test_records(uint32_t fmt, const uint32_t* in, size_t n, uint32_t* records, uint32_t* err,
+                     const uint32_t* ents, const uint32_t* acc, uint32_t* out, size_t m) {
+  if (fmt > PT_FMT_XYZ || !in || !records || !err || n == 0 || n > (1u << 24) || m > (1u << 24))
+    return MSM_ERR_INVALID_ARG;
+  if (m && (!ents || !acc || !out)) return MSM_ERR_INVALID_ARG;
+  for (size_t j = 0; j < m; j++)
+    if ((ents[j] >> 1) >= n) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t in_bytes = n * pt_fmt_slots(fmt) * 16;
+  TestBuf din, dpts, derr, dents, dacc, dout;
+  HIPCHECK(din.alloc(in_bytes));
+  HIPCHECK(dpts.alloc(n * PRE_WORDS * 4));
+  HIPCHECK(derr.alloc(4));
+  HIPCHECK(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemset(derr.p, 0, 4));
+  BatchPtrs bp{};
+  bp.p[0] = din.p;
+  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(n, PP_THREADS), 1), dim3(PP_THREADS), 0, 0, bp, dpts.p, (uint32_t)n,
+                     derr.p, 0u, fmt);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(records, dpts.p, n * PRE_WORDS * 4, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(err, derr.p, 4, hipMemcpyDeviceToHost));
+  if (!m) return MSM_OK;
+  HIPCHECK(dents.alloc(m * 4));
+  HIPCHECK(dacc.alloc(m * PT_WORDS * 4));
+  HIPCHECK(dout.alloc(m * PT_WORDS * 4));
+  HIPCHECK(hipMemcpy(dents.p, ents, m * 4, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(dacc.p, acc, m * PT_WORDS * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_limbs_gather, dim3(grid_for(m, 256)), dim3(256), 0, 0, dpts.p, dents.p, dacc.p, dout.p,
+                     (uint32_t)m);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, m * PT_WORDS * 4, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// The fold geometry a handle of `levels` levels gets at width window_bits (0: the auto width for n
+// points): out = {window_bits c, windows per folded MSM Wc, chunk bits S, points of the folded
+// problem levels * n}.  Host code only (no device needed).
+int msm_test_bases_plan(size_t n, uint32_t levels, uint32_t window_bits, uint32_t out[4]) {
+  if (!out || levels < 1 || levels > 8) return MSM_ERR_INVALID_ARG;
+  const uint32_t c = window_bits ? window_bits : levels > 1 ? bases_auto_window(n, levels) : msm_best_window(n);
+  BasesGeo g;
+  if (!bases_geometry(c, levels, &g)) return MSM_ERR_UNSUPPORTED_WINDOW;
+  out[0] = g.c;
+  out[1] = g.Wc;
+  out[2] = g.S;
+  out[3] = (uint32_t)(n * levels);
+  return MSM_OK;
+}
+
+// The geometry of one narrow-scalar MSM (MSM_FLAG_SCALAR_BITS) of n terms at width window_bits (0:
+// the lone launch's auto width for n): out = {widest window c, windows in the launch W', base width
+// q, windows of q + 1 bits nhi, words per wire scalar, d.packed}.  254 bits and more report the plain
+// launch (Wr counts its overflow window; 8 words).  Host code only.
+int msm_test_narrow_plan(size_t n, uint32_t scalar_bits, uint32_t window_bits, uint32_t out[6]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  msm_opts op{};
+  op.window_bits = window_bits;
+  op.flags = MSM_FLAG_SCALAR_BITS;
+  op.scalar_bits = scalar_bits;
+  Plan pl;
+  if (int rc = make_plan(n, &op, DevShape{}, &pl, false, 1, true)) return rc;
+  const uint32_t v[6] = {pl.d.c, pl.d.Wr, pl.d.q, pl.d.nhi, pl.d.sw ? pl.d.sw : 8u, pl.d.packed};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// The launch plan of one subset MSM (msm_bases_compute_subset*) of m terms on a handle of n_handle
+// points and `levels` levels at width window_bits (0: the width such a handle or launch gets):
+// out = {d.n, d.packed, the record stride d.rstride, d.fb, d.sub}.  The argument rules that need no
+// device apply (MSM_ERR_INVALID_ARG); the range [0, m) of a levels = 1 handle reports the plain
+// plan of m points (sub 0, stride 0).  Host code only.
+int msm_test_subset_plan(size_t n_handle, uint32_t levels, uint32_t window_bits, uint64_t first, uint64_t m,
+                         int indexed, uint32_t out[5]) {
+  if (!out || levels < 1 || levels > 8) return MSM_ERR_INVALID_ARG;
+  if ((uint64_t)levels * n_handle >= (1ull << 30)) return MSM_ERR_INVALID_ARG;  // no such handle
+  if (int rc = subset_check(n_handle, levels, first, m, indexed != 0)) return rc;
+  msm_opts op{};
+  op.window_bits = window_bits;
+  if (levels > 1) {
+    BasesGeo g;
+    op.window_bits = window_bits ? window_bits : bases_auto_window(n_handle, levels);
+    if (!bases_geometry(op.window_bits, levels, &g)) return MSM_ERR_UNSUPPORTED_WINDOW;
+    op.flags = MSM_FLAG_WINDOWS;
+    op.window_hi = g.Wc;
+  }
+  SubsetGeo sg;
+  sg.kind = subset_kind(levels, first, indexed != 0);
+  sg.levels = levels;
+  sg.rec_n = n_handle;
+  sg.first = (size_t)first;
+  Plan pl;
+  if (int rc = make_plan((size_t)m * levels, &op, DevShape{}, &pl, false, 1, true, &sg)) return rc;
+  out[0] = pl.d.n;
+  out[1] = pl.d.packed;
+  out[2] = pl.d.rstride;
+  out[3] = pl.d.fb;
+  out[4] = pl.d.sub;
+  return MSM_OK;
+}
+
+// The records of one level of a handle, copied to the host (n * 32 words).
+int msm_test_bases_records(const msm_bases* h, uint32_t level, uint32_t* records) {
+  if (!h || !records) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b || level >= b->levels) return MSM_ERR_INVALID_ARG;
+  msm_opts o{};
+  o.device = b->device;
+  return on_device(&o, [&](DevCtx*) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;
+    if (!b->n) return MSM_OK;
+    HIPCHECK(hipMemcpy(records, b->rec.as<uint32_t>() + (size_t)level * b->n * PRE_WORDS, b->n * PRE_WORDS * 4,
+                       hipMemcpyDeviceToHost));
+    return MSM_OK;
+  });
+}
+
+// k_split_scalars on n wire scalars: out = the k * n virtual scalars of S bits (8 words each,
+// element j n + i).
+int msm_test_split_scalars(const uint32_t* scalars, size_t n, uint32_t k, uint32_t S, uint32_t* out) {
+  if (!scalars || !out || n == 0 || n > (1u << 24) || k < 2 || k > 8 || S < 1 || S > 255)
+    return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  TestBuf din, dout;
+  HIPCHECK(din.alloc(n * 32));
+  HIPCHECK(dout.alloc((size_t)k * n * 32));
+  HIPCHECK(hipMemcpy(din.p, scalars, n * 32, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_split_scalars, dim3(grid_for(n, 256), k, 1), dim3(256), 0, 0, splat(din.p), dout.p, (uint32_t)n, k,
+                     S);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(out, dout.p, (size_t)k * n * 32, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+#ifdef MSM_PHASE_PROBE
+// Tuning builds only: writes the sort kernels' phase stamps of the last launch (g_probe) to `path`.
+int msm_test_probe_dump(const char* path) {
+  static std::vector<uint64_t> buf(sizeof(g_probe) / 8);
+  if (hipDeviceSynchronize() != hipSuccess) return MSM_ERR_HIP;
+  if (hipMemcpyFromSymbol(buf.data(), HIP_SYMBOL(g_probe), sizeof(g_probe), 0, hipMemcpyDeviceToHost) != hipSuccess)
+    return MSM_ERR_HIP;
+  FILE* f = fopen(path, "wb");
+  if (!f) return MSM_ERR_INVALID_ARG;
+  fwrite(buf.data(), 8, buf.size(), f);
+  fclose(f);
+  return MSM_OK;
+}
+#endif
+
+}  // extern "C"
