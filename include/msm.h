@@ -115,6 +115,14 @@ uint32_t msm_window_count(uint32_t window_bits);
  * lowest T mod W' of them one bit wider -- 5 windows for b = 64 at c = 16 against the 17 of a 256-bit
  * scalar.  For b >= 254 the call is the 8-word one as it is.
  *
+ * Dense buckets: a narrow launch of n terms whose widest window has 2^(c' - 1) buckets of n >> (c' - 1)
+ * >= 128 entries each, with at most 8,192 buckets over all its windows and MSMs, accumulates by
+ * bucket segment -- a wave per 256..4,096 entries of one bucket, then a fold -- instead of by runs of
+ * the sorted list.  So b <= 8 needs no special care: booleans and bytes at any n are
+ * faster than the same scalars zero-extended to 8 words.  Results are bit-identical either way; with
+ * profiling on, msm_profile_t.accumulate covers the path's three kernels and run_length reports its
+ * entries per lane.
+ *
  * Honoured by the eight msm_bases_compute* entries (the subset forms included: a subset picks the
  * records, the width the digits; neither knows of the other).  Every other entry that takes msm_opts,
  * msm_bases_create* included, returns MSM_ERR_INVALID_ARG when the flag is set, before any device work.

@@ -37,6 +37,14 @@ computing the MSM of n random b-bit scalars:
 
 with the same four timings and the per-phase times of one profiled awaited call.
 
+With --dense the pass is the dense-bucket sweep of DESIGN.md §9 (the narrow launches whose buckets
+hold DENSE_MIN entries or more, host_plan.h): the narrow pass at the auto width for b = 1, 4, 8, 12,
+for b = 16 at the explicit width 16, and (at 2^20) for all-equal bytes, once as the library plans
+it and once with the path turned off (MSM_DENSE_MIN, read once per process: each way is a child
+process of its own; every line carries "dense_min", the variable's value, and "dense" / "E", the
+lone launch's plan); then the threshold rows with the path forced on (MSM_DENSE_MIN=1) and off:
+b = 8 at 2^13..2^16, b = 12 at 2^17..2^19, and b = 13 at 2^20.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -274,7 +282,8 @@ def narrow_pass(a):
             p = M.last_profile()
         finally:
             M.set_profiling(0)
-        return {**{k: round(float(p[k]), 4) for k in phases}, "windows": int(p["windows"]), "c": int(p["window_bits"])}
+        return {**{k: round(float(p[k]), 4) for k in phases}, "windows": int(p["windows"]), "c": int(p["window_bits"]),
+                "run_length": int(p["run_length"])}
 
     def measure(row, exp, host1, dev1, host_many, dev_many):
         ok = True
@@ -295,10 +304,19 @@ def narrow_pass(a):
     pts = M.gen_points(n, k0=k0, step=step)
     d_pts = dev(pts)
     rnd = np.random.RandomState(29)
+    # (bits, widths, scalars): the sweep's uniform scalars at the auto and the explicit widths, then
+    # --narrow-extra's b:c rows, then --narrow-equal's all-equal bytes
+    cases = [(bits, [0] + list(a.narrow_widths), "uniform") for bits in a.narrow_bits]
+    cases += [(bits, [c], "uniform") for bits, c in a.narrow_extra]
+    cases += [(8, [0], "equal")] if a.narrow_equal else []
+    dense_min = os.environ.get("MSM_DENSE_MIN")
     with M.Bases.from_device(d_pts, n, levels=1) as b:
-        for bits in a.narrow_bits:
+        for bits, widths, kind in cases:
             words = (bits + 31) // 32
-            if bits == 253:
+            if kind == "equal":
+                sc8 = np.zeros((n, 8), np.uint32)
+                sc8[:, 7] = 0xA5
+            elif bits == 253:
                 sc8 = M.gen_scalars(n, seed=700)  # canonical field elements: below 2^253
             else:
                 sc8 = np.zeros((n, 8), np.uint32)
@@ -309,16 +327,56 @@ def narrow_pass(a):
             exp = closed_form(k0, step, sc8)
             d_sc8, d_sc = dev(sc8), dev(sc)
             base = {"entry": "narrow", "bits": bits, "words": words, "count": count}
-            measure({**base, "form": "extended"}, exp,
-                    lambda: b.compute(sc8), lambda: b.compute_device(d_sc8),
-                    lambda: b.compute_many([sc8] * count), lambda: b.compute_many_device([d_sc8] * count))
-            for c in [0] + list(a.narrow_widths):
+            if kind != "uniform":
+                base["scalars"] = kind
+            base["dense_min"] = dense_min
+            if not a.no_extended:
+                measure({**base, "form": "extended"}, exp,
+                        lambda: b.compute(sc8), lambda: b.compute_device(d_sc8),
+                        lambda: b.compute_many([sc8] * count), lambda: b.compute_many_device([d_sc8] * count))
+            for c in widths:
                 kw = {"window_size": c or None, "scalar_bits": bits}
-                measure({**base, "form": "narrow", "c": c}, exp,
+                # (a library from before the dense accumulation, loaded for an A/B run, has no such plan)
+                plan = (M._test_dense_plan(n, 1, False, bits, c) if hasattr(M.load(), "msm_test_dense_plan")
+                        else {"dense": 0, "E": 0})
+                measure({**base, "form": "narrow", "c": c, "dense": plan["dense"], "E": plan["E"]}, exp,
                         lambda: b.compute(sc, **kw), lambda: b.compute_device(d_sc, **kw),
                         lambda: b.compute_many([sc] * count, **kw),
                         lambda: b.compute_many_device([d_sc] * count, **kw))
     return 1 if bad else 0
+
+
+def dense_sweep(a):
+    """The children of --dense, one after the other; stops at the first that fails."""
+    def child(lg, bits, extra, equal, dense_min, extended):
+        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n", str(1 << lg),
+               "--narrow", "--narrow-bits", bits, "--narrow-widths", "", "--narrow-extra", extra, "--count", str(a.count),
+               "--runs", str(a.runs)]
+        cmd += (["--narrow-equal"] if equal else []) + ([] if extended else ["--no-extended"])
+        cmd += ["--out", a.out] if a.out else []
+        env = dict(os.environ)
+        env.pop("MSM_DENSE_MIN", None)
+        if dense_min:
+            env["MSM_DENSE_MIN"] = str(dense_min)
+        rc = subprocess.run(cmd, env=env).returncode
+        if rc != 0:
+            print(f"bases_probe: size 2^{lg} (MSM_DENSE_MIN={dense_min}) ended with status {rc}; stopping", file=sys.stderr)
+        return rc
+
+    off = 1 << 30
+    for lg in (int(x) for x in a.sizes.split(",")):
+        for dense_min in (None, off):  # as planned (with the 8-word rows), then the path off
+            if rc := child(lg, "1,4,8,12", "16:16", lg == 20, dense_min, dense_min is None):
+                return rc
+    # the threshold rows, path forced on and off: bytes (256 keys) at 32..256 entries per bucket, 12 bits
+    # (4,096 keys) at 32..128, and 13 bits at 2^20 (8,192 keys at 128 per bucket; its two-MSM launches
+    # are past DENSE_MAX_KEYS, as any launch of 14 and 15 bits is: the committed rows of those were
+    # taken with the cap lifted)
+    for lg, bits in ((13, 8), (14, 8), (15, 8), (16, 8), (17, 12), (18, 12), (19, 12), (20, 13)):
+        for dense_min in (1, off):
+            if rc := child(lg, str(bits), "", False, dense_min, False):
+                return rc
+    return 0
 
 
 def main():
@@ -335,9 +393,16 @@ def main():
     ap.add_argument("--narrow", action="store_true", help="the narrow-scalar sweep (MSM_FLAG_SCALAR_BITS) instead")
     ap.add_argument("--narrow-bits", default="8,16,32,64,128,253", help="scalar widths b of the narrow sweep")
     ap.add_argument("--narrow-widths", default="13,14,15,16,17,19", help="explicit window widths of the narrow sweep")
+    ap.add_argument("--narrow-extra", default="", help="more narrow rows at explicit widths, as b:c,b:c")
+    ap.add_argument("--narrow-equal", action="store_true", help="a narrow row of all-equal bytes as well")
+    ap.add_argument("--no-extended", action="store_true", help="the narrow pass without its 8-word rows")
+    ap.add_argument("--dense", action="store_true", help="the dense-bucket sweep (DENSE_MIN, MSM_DENSE_MIN) instead")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
+    a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
+    if a.dense:
+        return dense_sweep(a)
     if a.subset:
         a.subset_sizes = [int(x) for x in str(a.subset_sizes).split(",")]
         if a.n:

@@ -93,6 +93,9 @@ struct Plan {
   size_t Mmax;      // W * n upper bound on sorted entries
   size_t runs_max;
   uint32_t pfmt;    // input point format of k_prepare_points (PT_FMT_*: wire records or a compact upload)
+  // The dense-bucket accumulation (finish_plan; k_dense_* in the place of k_accumulate): entries per
+  // unit lane E (a unit's segment is 64 E entries) and the unit kernel's grid bound.  Zero otherwise.
+  uint32_t dense, dense_E, dense_units;
 };
 
 // Every field that shapes a launch (grids, buffer offsets, the h_out layout): a captured graph is
@@ -106,7 +109,8 @@ bool plan_eq(const Plan& a, const Plan& b) {
          x.packed == y.packed && x.shared == y.shared && x.sub == y.sub && x.rstride == y.rstride &&
          x.first == y.first && x.sm == y.sm && x.sw == y.sw && x.sbits == y.sbits && a.K == b.K && a.L == b.L &&
          a.nchunks == b.nchunks && a.nv == b.nv && a.nterms == b.nterms && a.Mmax == b.Mmax &&
-         a.runs_max == b.runs_max && a.pfmt == b.pfmt;
+         a.runs_max == b.runs_max && a.pfmt == b.pfmt && a.dense == b.dense && a.dense_E == b.dense_E &&
+         a.dense_units == b.dense_units;
 }
 
 // Device workspace of one MSM (all sizes from Plan; grown on demand, never shrunk).
@@ -118,6 +122,7 @@ struct Workspace {
   Buf red_G;               // k_red2_groups' points per (window, group of RG_CH chunks)
   Buf split_sc;            // k_split_scalars' virtual scalars of a folded launch (msm_bases_*, levels > 1)
   Buf sub_idx;             // base indices [nm][m] of an indexed subset launch (msm_bases_compute_subset*)
+  Buf seg_base, unit_key, partials;  // the dense-bucket accumulation's segment map and per-unit sums (Plan::dense)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
@@ -125,7 +130,7 @@ struct Workspace {
     Buf* bufs[] = {&pts, &err, &digits, &colsum, &bin_base, &bin_cur, &part_entry, &part_fine,
                    &sorted_entry, &bucket_start, &run_key, &buckets, &lead_val, &lead_open, &cross_key,
                    &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G, &split_sc,
-                   &sub_idx};
+                   &sub_idx, &seg_base, &unit_key, &partials};
     for (Buf* b : bufs) b->release();
   }
 };
@@ -212,12 +217,14 @@ struct PinRing {
   bool used[NPIN] = {};
 };
 
-// What the launch plans take from the device: compute units, and k_accumulate's waves per SIMD
-// (the occupancy query at context creation; run_length_for fills whole rounds of them).  The test
-// hooks plan for the defaults, so their plans do not depend on which device was used first.
+// What the launch plans take from the device: compute units, and k_accumulate's and k_dense_units'
+// waves per SIMD (the occupancy queries at context creation; run_length_for and dense_entries fill
+// whole rounds of them).  The test hooks plan for the defaults, so their plans do not depend on
+// which device was used first.
 struct DevShape {
   int n_cu = 256;
   int acc_waves = 4;
+  int dense_waves = 4;
 };
 
 struct DevCtx {
@@ -293,6 +300,11 @@ struct DevCtx {
                                                            ACC_THREADS, 0) == hipSuccess &&
         acc_blocks > 0)
       shape.acc_waves = std::max(1, acc_blocks * (int)(ACC_THREADS / 64) / 4);
+    int du_blocks = 0;
+    if (ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&du_blocks, reinterpret_cast<const void*>(&k_dense_units),
+                                                           DU_THREADS, 0) == hipSuccess &&
+        du_blocks > 0)
+      shape.dense_waves = std::max(1, du_blocks * (int)(DU_THREADS / 64) / 4);
     hipSetDevice(prev);
     return ok ? MSM_OK : MSM_ERR_HIP;
   }

@@ -73,6 +73,11 @@ size_t pin_max_bytes() {  // MSM_PIN_MAX_MB overrides (tests force the fallback 
   return v;
 }
 
+// MSM_DENSE_MIN overrides DENSE_MIN, the entries per bucket from which a narrow launch takes the
+// dense-bucket accumulation (host_plan.h; 0: unset).  1 forces the path wherever it applies, a huge
+// value turns it off: for A/B runs.
+uint32_t knob_dense_min() { static const uint32_t v = (uint32_t)std::max(0, env_int("MSM_DENSE_MIN", 0)); return v; }
+
 // MSM_NO_GRAPH (set to anything): every launch sequence is enqueued eagerly, none captured.
 bool graphs_enabled() { static const bool on = !getenv("MSM_NO_GRAPH"); return on; }
 

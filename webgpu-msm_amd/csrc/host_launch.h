@@ -39,6 +39,11 @@ int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
   ENS(red_U, (size_t)d.W * pl.nchunks * PT_WORDS * 4);
   ENS(red_T, (size_t)d.W * pl.nchunks * PT_WORDS * 4);
   if (red2_tree(pl)) ENS(red_G, (size_t)d.W * red2_groups(pl) * RG_OUT * PT_WORDS * 4);
+  if (pl.dense) {
+    ENS(seg_base, (nb + 1) * 4);
+    ENS(unit_key, (size_t)pl.dense_units * 4);
+    ENS(partials, (size_t)pl.dense_units * PT_WORDS * 4);
+  }
 #undef ENS
   if (g_alloc_gen.load() != gen0) {
     // err, lead_flag, colsum and bin_cur are kept all-zero between MSMs by the kernels themselves
@@ -174,7 +179,8 @@ bool is_recode_kernel(const void* f) {
 
 // Enqueue parts of the device pipeline on `s`; the reduced per-window terms land in the slot's
 // h_out.  `pts` is the point-record buffer (the slot's own, or a shared base vector's).
-// With `acc_events` (eager launches only), k_accumulate runs between the slot's ev_acc0 / ev_acc1
+// With `acc_events` (eager launches only), the accumulation -- k_accumulate, or a dense plan's
+// k_dense_segments, k_dense_units and k_dense_fold -- runs between the slot's ev_acc0 / ev_acc1
 // (2), or is followed by ev_acc1 alone (1);
 // captured graphs get the same events as record nodes (add_acc_event_nodes).
 int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si,
@@ -259,7 +265,22 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
   }
   if (fork) HIPCHECK(hipStreamWaitEvent(s, sl.ev_join, 0));
   if ((parts & PART_ACC) && acc_events == 2) HIPCHECK(hipEventRecord(sl.ev_acc0, s));
-  if (parts & PART_ACC) {
+  if ((parts & PART_ACC) && pl.dense) {
+    // The segment map is data: k_dense_segments rebuilds it from this launch's bucket_start, so a
+    // replayed graph holds nothing of any launch's bucket sizes, only the plan's grid bound.
+    const uint32_t nkeys = d.W * d.B;
+    const uint32_t ncross = (uint32_t)(pl.runs_max / ACC_THREADS + 2);  // ensure_workspace's cross_key words
+    hipLaunchKernelGGL(k_dense_segments, dim3(1), dim3(DS_THREADS), 0, s, w.bucket_start.as<uint32_t>(), nkeys,
+                       64u * pl.dense_E, w.seg_base.as<uint32_t>(), w.unit_key.as<uint32_t>(), pl.dense_units,
+                       w.cross_key.as<uint32_t>(), pl.K * ACC_THREADS, ncross);
+    hipLaunchKernelGGL(k_dense_units, dim3(grid_for(pl.dense_units, DU_THREADS / 64)), dim3(DU_THREADS), 0, s, pts,
+                       w.sorted_entry.as<uint32_t>(), w.bucket_start.as<uint32_t>(), w.seg_base.as<uint32_t>(),
+                       w.unit_key.as<uint32_t>(), pl.dense_E, nkeys, pl.dense_units, w.buckets.as<uint32_t>(),
+                       w.partials.as<uint32_t>());
+    hipLaunchKernelGGL(k_dense_fold, dim3(nkeys), dim3(DF_THREADS), 0, s, w.seg_base.as<uint32_t>(),
+                       w.partials.as<uint32_t>(), pl.dense_units, w.buckets.as<uint32_t>());
+    mark(PH_ACCUM);
+  } else if (parts & PART_ACC) {
     hipLaunchKernelGGL(k_accumulate, dim3(rgrid), dim3(ACC_THREADS), 0, s, pts, w.sorted_entry.as<uint32_t>(),
                        w.bucket_start.as<uint32_t>(), w.run_key.as<uint32_t>(), total, pl.K, d.W * d.B,
                        w.buckets.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.lead_open.as<uint32_t>(),
@@ -269,7 +290,8 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
   }
   if ((parts & PART_ACC) && acc_events) HIPCHECK(hipEventRecord(sl.ev_acc1, s));
   // profiling mode 1 keeps the joins in line (its per-phase timings include them)
-  const bool joins = (parts & PART_JOIN) || prof;
+  // (a dense launch has none: no bucket continues in another lane's run, skew_list and lead_flag stay clear)
+  const bool joins = ((parts & PART_JOIN) || prof) && !pl.dense;
   if ((parts & PART_POST) && joins) {
     hipLaunchKernelGGL(k_chain_join, dim3(CJ_GRID), dim3(ACC_THREADS), 0, s, w.skew_list.as<uint32_t>(), total, pl.K,
                        w.g_head.as<uint32_t>(), w.g_hkey.as<uint32_t>(), w.g_tkey.as<uint32_t>(),
@@ -338,30 +360,37 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
   return MSM_OK;
 }
 
-// Bracket the captured k_accumulate node with event-record nodes (the slot's ev_acc0 / ev_acc1):
-// every replay of the graph then times the accumulation, with no extra launches.
+// Bracket the captured accumulation with event-record nodes (the slot's ev_acc0 / ev_acc1): every
+// replay of the graph then times the accumulation, with no extra launches.  The accumulation is the
+// k_accumulate node, or a dense plan's chain k_dense_segments -> k_dense_units -> k_dense_fold:
+// ev_acc0 goes before the first of them, ev_acc1 after the last.
 int add_acc_event_nodes(hipGraph_t g, Slot& sl, bool both) {
   size_t num = 0;
   if (hipGraphGetNodes(g, nullptr, &num) != hipSuccess || num == 0) return MSM_ERR_HIP;
   std::vector<hipGraphNode_t> nodes(num);
   if (hipGraphGetNodes(g, nodes.data(), &num) != hipSuccess) return MSM_ERR_HIP;
   const void* f_acc = reinterpret_cast<const void*>(&k_accumulate);
-  hipGraphNode_t acc = nullptr;
+  const void* f_seg = reinterpret_cast<const void*>(&k_dense_segments);
+  const void* f_fold = reinterpret_cast<const void*>(&k_dense_fold);
+  hipGraphNode_t acc = nullptr, acc_end = nullptr;  // the accumulation's first and last node
   for (hipGraphNode_t nd : nodes) {
     hipGraphNodeType ty;
     hipKernelNodeParams kp{};
-    if (hipGraphNodeGetType(nd, &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
-        hipGraphKernelNodeGetParams(nd, &kp) == hipSuccess && kp.func == f_acc)
-      acc = nd;
+    if (hipGraphNodeGetType(nd, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel ||
+        hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess)
+      continue;
+    if (kp.func == f_acc) acc = acc_end = nd;
+    if (kp.func == f_seg) acc = nd;
+    if (kp.func == f_fold) acc_end = nd;
   }
-  if (!acc) return MSM_ERR_HIP;
+  if (!acc || !acc_end) return MSM_ERR_HIP;
   size_t nd = 0, nx = 0;
   if (hipGraphNodeGetDependencies(acc, nullptr, &nd) != hipSuccess ||
-      hipGraphNodeGetDependentNodes(acc, nullptr, &nx) != hipSuccess)
+      hipGraphNodeGetDependentNodes(acc_end, nullptr, &nx) != hipSuccess)
     return MSM_ERR_HIP;
   std::vector<hipGraphNode_t> deps(nd), outs(nx);
   if ((nd && hipGraphNodeGetDependencies(acc, deps.data(), &nd) != hipSuccess) ||
-      (nx && hipGraphNodeGetDependentNodes(acc, outs.data(), &nx) != hipSuccess))
+      (nx && hipGraphNodeGetDependentNodes(acc_end, outs.data(), &nx) != hipSuccess))
     return MSM_ERR_HIP;
   hipGraphNode_t r0 = nullptr, r1 = nullptr;
   if (both) {
@@ -372,8 +401,8 @@ int add_acc_event_nodes(hipGraph_t g, Slot& sl, bool both) {
       return MSM_ERR_HIP;
   }
   for (hipGraphNode_t o : outs)
-    if (hipGraphRemoveDependencies(g, &acc, &o, 1) != hipSuccess) return MSM_ERR_HIP;
-  if (hipGraphAddEventRecordNode(&r1, g, &acc, 1, sl.ev_acc1) != hipSuccess) return MSM_ERR_HIP;
+    if (hipGraphRemoveDependencies(g, &acc_end, &o, 1) != hipSuccess) return MSM_ERR_HIP;
+  if (hipGraphAddEventRecordNode(&r1, g, &acc_end, 1, sl.ev_acc1) != hipSuccess) return MSM_ERR_HIP;
   for (hipGraphNode_t o : outs)
     if (hipGraphAddDependencies(g, &r1, &o, 1) != hipSuccess) return MSM_ERR_HIP;
   return MSM_OK;
@@ -654,7 +683,7 @@ int finish_msm(DevCtx* c, int si, Pt* result, std::vector<uint32_t>* terms = nul
     P.entries = total;
     P.window_bits = pl.d.c;
     P.windows = pl.d.Wr;
-    P.run_length = pl.K;
+    P.run_length = pl.dense ? pl.dense_E : pl.K;  // a dense launch: entries per unit lane
     P.chunk_len = pl.L;
     P.msms_per_launch = pl.d.nm;
     P.accumulate_sum += P.accumulate;

@@ -220,12 +220,69 @@ int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pi
   return finish_plan(d, o, sh, pl, pipelined);
 }
 
+// ---- the dense-bucket accumulation (k_dense_segments / k_dense_units / k_dense_fold) -------------
+// A narrow launch whose buckets hold DENSE_MIN entries or more (n over the buckets of its widest
+// window) and whose key space is at most DENSE_MAX_KEYS takes the dense accumulation in the place of
+// k_accumulate.  There k_accumulate is short of lanes: run_length_skew_floor keeps K above a third
+// of the largest bucket, so the launch has ~3 lanes per bucket whatever n is (2^20 bytes in one
+// 9-bit window: ~710 lanes of ~1,476 dependent adds, 4.964 of the launch's 5.111 ms).  A dense unit
+// pays a six-level tree (~8 adds of a whole wave) per segment instead, whatever the segment holds, so
+// the path wins where buckets are large and few, and loses where the keys alone fill the machine.
+// profiles/bases_dense_sweep.jsonl (tools/bases_probe.py --dense), ms awaited device-resident /
+// ms per MSM pipelined, path on against off (MSM_DENSE_MIN=1 / 2^30):
+//   b = 8, 256 keys (x 4 pipelined), 32 / 64 / 128 / 256 per bucket (2^13..2^16):
+//     0.212 / 0.214 / 0.218 / 0.220 against 0.247 / 0.288 / 0.377 / 0.580 awaited,
+//     0.024 / 0.025 / 0.026 / 0.033 against 0.026 / 0.033 / 0.048 / 0.077 pipelined: on wins from 32
+//   b = 12, 4,096 keys (x 4, x 2 at 2^19), 32 / 64 / 128 per bucket (2^17..2^19):
+//     0.278 / 0.283 / 0.295 against 0.260 / 0.321 / 0.419 awaited,
+//     0.126 / 0.133 / 0.162 against 0.048 / 0.061 / 0.163 pipelined: on loses below 128, level at 128
+//     (and wins at 256, 2^20: 0.393 against 0.605, 0.185 against 0.254)
+//   b = 13, 8,192 keys (x 2: 16,384), 128 per bucket (2^20): 0.418 against 0.422 awaited,
+//     0.284 against 0.170 pipelined; b = 14 / 15 (16,384 / 32,768 keys, 64 / 32 per bucket): 0.608 /
+//     1.001 against 0.332 / 0.282 awaited.
+// So DENSE_MIN stays at 128 -- also where the skew floor first pushes K past its usual 64 (lambda =
+// 128: K = 64; 192: K = 88) -- since below it only the launches of few keys gain, and DENSE_MAX_KEYS
+// is 8,192, the most keys a measured row wins or draws with (the two-MSM 2^20 launch of 12-bit
+// scalars; 16,384 keys at 128 per bucket lose by two thirds).  k_dense_segments, one workgroup, then
+// walks 8 keys per thread.  MSM_DENSE_MIN overrides the threshold.
+constexpr uint32_t DENSE_MIN = 128;
+constexpr uint32_t DENSE_MAX_KEYS = 1u << 13;
+constexpr uint32_t DENSE_K = 4096;  // a dense plan's run length: it sizes run_key and the cross_key index only
+
+bool dense_launch(const MsmDims& d) {
+  const uint32_t dmin = knob_dense_min() ? knob_dense_min() : DENSE_MIN;
+  return d.sw != 0 && (d.n >> (d.c - 1)) >= dmin && (uint64_t)d.W * d.B <= DENSE_MAX_KEYS;
+}
+// The unit kernel's grid for segments of 64 E entries: sum_k ceil(s_k / S) <= floor(M / S) + #nonempty
+// for any bucket sizes s_k of sum M <= Mmax over nkeys buckets.
+uint64_t dense_unit_bound(uint64_t Mmax, uint32_t nkeys, uint32_t E) { return Mmax / (64ull * E) + nkeys; }
+// Entries per unit lane: the smallest multiple of 4 in 4..64 whose grid is one round of resident
+// waves (sh.dense_waves per SIMD, the runtime's occupancy query for k_dense_units) -- a unit pays a
+// six-level tree whatever E is, so no more units than the machine holds at once -- and past one
+// round at E = 64, the smallest E of that many whole rounds.
+uint32_t dense_entries(uint64_t Mmax, uint32_t nkeys, const DevShape& sh) {
+#ifdef MSM_DENSE_E
+  return MSM_DENSE_E;  // tuning builds: one E for every launch (make variant NAME=e16 DEFS=-DMSM_DENSE_E=16)
+#endif
+  const uint64_t round = (uint64_t)std::max(1, sh.dense_waves) * 4 * (uint64_t)(sh.n_cu > 0 ? sh.n_cu : 256);
+  const uint64_t rounds = std::max<uint64_t>(1, (dense_unit_bound(Mmax, nkeys, 64) + round - 1) / round);
+  for (uint32_t E = 4; E < 64; E += 4)
+    if (dense_unit_bound(Mmax, nkeys, E) <= rounds * round) return E;
+  return 64;
+}
+
 // The launch-shape fields that follow from the geometry d.
 int finish_plan(const MsmDims& d, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined) {
   const size_t n = d.n;
   pl->d = d;
-  pl->K = (o && o->run_length) ? o->run_length : run_length_for(d, sh, pipelined);
+  pl->dense = dense_launch(d) ? 1u : 0u;
+  // (a dense plan's K is not governed by the skew floor: no lane walks a run)
+  pl->K = (o && o->run_length) ? o->run_length : pl->dense ? DENSE_K : run_length_for(d, sh, pipelined);
   if (pl->K < 1 || pl->K > 4096) return MSM_ERR_INVALID_ARG;
+  if (pl->dense) {
+    pl->dense_E = dense_entries((uint64_t)d.W * n, d.W * d.B, sh);
+    pl->dense_units = (uint32_t)dense_unit_bound((uint64_t)d.W * n, d.W * d.B, pl->dense_E);
+  }
   pl->L = bucket_reduce_L(d, sh);
   pl->nchunks = (d.B + pl->L - 1) / pl->L;
   // every k_bucket_reduce_2 workgroup sums at most pow2ceil(nchunks)/2 points (the R_k terms' size)

@@ -408,6 +408,56 @@ int msm_test_narrow_plan(size_t n, uint32_t scalar_bits, uint32_t window_bits, u
   return MSM_OK;
 }
 
+// The dense-bucket part of the plan of a narrow launch (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
+// of nm MSMs of n terms at width window_bits (0: auto), pipelined or lone: out = {dense (0 / 1),
+// entries per unit lane E, keys W * B, the unit kernel's grid bound, run length K}, for the default
+// device shape.  E and the bound are 0 for a launch that is not dense.  Host code only.
+int msm_test_dense_plan(size_t n, uint32_t nm, int pipelined, uint32_t scalar_bits, uint32_t window_bits,
+                        uint32_t out[5]) {
+  if (!out || nm < 1 || nm > MSM_MAX_BATCH) return MSM_ERR_INVALID_ARG;
+  msm_opts op{};
+  op.window_bits = window_bits;
+  op.flags = MSM_FLAG_SCALAR_BITS;
+  op.scalar_bits = scalar_bits;
+  Plan pl;
+  if (int rc = make_plan(n, &op, DevShape{}, &pl, pipelined != 0, nm, true)) return rc;
+  const uint32_t v[5] = {pl.dense, pl.dense_E, pl.d.W * pl.d.B, pl.dense_units, pl.K};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// k_dense_segments alone, on the device: bucket_start[0..nkeys] (non-decreasing) and the segment
+// length S (a multiple of 64) -> seg_base[0..nkeys] and unit_key[0..bound), bound =
+// bucket_start[nkeys] / S + nkeys, the grid bound a plan would hold; the words of unit_key past the
+// live units come back as 0xffffffff (unwritten).
+int msm_test_dense_segments(const uint32_t* bucket_start, uint32_t nkeys, uint32_t S, uint32_t* seg_base,
+                            uint32_t* unit_key) {
+  if (!bucket_start || !seg_base || !unit_key || nkeys < 1 || nkeys > DENSE_MAX_KEYS || S < 64 || (S & 63u))
+    return MSM_ERR_INVALID_ARG;
+  for (uint32_t k = 0; k < nkeys; k++)
+    if (bucket_start[k + 1] < bucket_start[k]) return MSM_ERR_INVALID_ARG;
+  if (bucket_start[nkeys] >= (1u << 31)) return MSM_ERR_INVALID_ARG;
+  const uint32_t bound = bucket_start[nkeys] / S + nkeys;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const uint32_t KA = DENSE_K * ACC_THREADS, ncross = bucket_start[nkeys] / KA + 2;
+  TestBuf dbs, dseg, dunit, dcross;
+  HIPCHECK(dbs.alloc(((size_t)nkeys + 1) * 4));
+  HIPCHECK(dseg.alloc(((size_t)nkeys + 1) * 4));
+  HIPCHECK(dunit.alloc((size_t)bound * 4));
+  HIPCHECK(dcross.alloc((size_t)ncross * 4));
+  HIPCHECK(hipMemcpy(dbs.p, bucket_start, ((size_t)nkeys + 1) * 4, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemset(dunit.p, 0xff, (size_t)bound * 4));
+  hipLaunchKernelGGL(k_dense_segments, dim3(1), dim3(DS_THREADS), 0, 0, dbs.p, nkeys, S, dseg.p, dunit.p, bound,
+                     dcross.p, KA, ncross);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(seg_base, dseg.p, ((size_t)nkeys + 1) * 4, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(unit_key, dunit.p, (size_t)bound * 4, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
 // The launch plan of one subset MSM (msm_bases_compute_subset*) of m terms on a handle of n_handle
 // points and `levels` levels at width window_bits (0: the width such a handle or launch gets):
 // out = {d.n, d.packed, the record stride d.rstride, d.fb, d.sub}.  The argument rules that need no

@@ -1727,6 +1727,196 @@ extern "C" __global__ void __launch_bounds__(LS_THREADS) k_lead_scan(uint32_t* _
 }
 
 // ---------------------------------------------------------------------------------------------
+// dense-bucket accumulation (narrow scalars whose buckets hold hundreds of entries: Plan::dense)
+// ---------------------------------------------------------------------------------------------
+// k_accumulate hands a lane a run of K sorted entries and must keep K above a third of the largest
+// bucket (run_length_skew_floor), so a launch of few, large buckets has ~3 lanes per bucket whatever
+// its size: 2^20 bytes in one 9-bit window are ~710 lanes of ~1,476 dependent adds each.  Here the
+// work goes out by bucket and by position inside the bucket instead.  A unit is one wave; it owns
+// one segment of S = 64 E consecutive entries of ONE bucket, lane l the entries l + 64 j (coalesced
+// 4-byte loads), added from the identity with no boundary test, and the 64 lane sums join in a
+// six-level tree through LDS.  A bucket of one segment is stored straight to the bucket table; the
+// segments of a larger one go to partials[unit] and k_dense_fold adds them.  Which unit owns which
+// segment is data (k_dense_segments builds the map from bucket_start on every launch), so the grid
+// is a bound the host knows without the bucket sizes: sum_k ceil(s_k / S) <= floor(M / S) + #nonempty.
+constexpr uint32_t DS_THREADS = 1024;  // k_dense_segments: one workgroup
+constexpr uint32_t DU_THREADS = 256;   // k_dense_units: four units
+constexpr uint32_t DF_THREADS = 256;   // k_dense_fold: one bucket
+
+// Inclusive running maximum over the wave's lanes.
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t x) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
+    if (lane >= d) x = max(x, y);
+  }
+  return x;
+}
+
+// The segment map.  seg_base[k] = segments of the buckets before k (seg_base[nkeys]: the live
+// units), unit_key[u] = the bucket of unit u: every thread counts a stretch of consecutive buckets,
+// one workgroup scan places them, each non-empty bucket marks its first unit and a running maximum
+// over the units fills in the rest (keys only grow with the unit).  The same pass invalidates every
+// cross_key word the bucket reduction may probe -- bucket_start[k] / (K ACC_THREADS) = KA, at most
+// M / KA -- since no bucket of a dense launch continues in a lead.  Nothing is written at or past
+// `ubound` units (the host's bound, which the sizes cannot exceed) or `ncross` words.
+extern "C" __global__ void __launch_bounds__(DS_THREADS) k_dense_segments(const uint32_t* __restrict__ bucket_start,
+                                                                          uint32_t nkeys, uint32_t S,
+                                                                          uint32_t* __restrict__ seg_base,
+                                                                          uint32_t* __restrict__ unit_key,
+                                                                          uint32_t ubound,
+                                                                          uint32_t* __restrict__ cross_key,
+                                                                          uint32_t KA, uint32_t ncross) {
+  __shared__ uint32_t sh_w[DS_THREADS / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t kp = (nkeys + DS_THREADS - 1) / DS_THREADS;
+  const uint32_t k0 = min(tid * kp, nkeys), k1 = min(k0 + kp, nkeys);
+  uint32_t mine = 0;
+  for (uint32_t k = k0; k < k1; k++) mine += (bucket_start[k + 1] - bucket_start[k] + S - 1) / S;
+  uint32_t wtot;
+  uint32_t base = wave_excl_scan(mine, wtot);
+  if (lane == 63) sh_w[wv] = wtot;
+  __syncthreads();
+  uint32_t total = 0;
+  for (uint32_t w = 0; w < DS_THREADS / 64; w++) {
+    if (w == wv) base += total;
+    total += sh_w[w];
+  }
+  __syncthreads();  // sh_w is reused below
+  for (uint32_t k = k0, run = base; k < k1; k++) {
+    seg_base[k] = run;
+    run += (bucket_start[k + 1] - bucket_start[k] + S - 1) / S;
+  }
+  if (tid == 0) seg_base[nkeys] = total;
+  const uint32_t live = min(total, ubound);
+  for (uint32_t u = tid; u < live; u += DS_THREADS) unit_key[u] = 0u;
+  const uint32_t M = bucket_start[nkeys];
+  for (uint32_t g = tid; g <= M / KA + 1u && g < ncross; g += DS_THREADS) cross_key[g] = KEY_INVALID;
+  __syncthreads();
+  for (uint32_t k = k0, run = base; k < k1; k++) {
+    const uint32_t segs = (bucket_start[k + 1] - bucket_start[k] + S - 1) / S;
+    if (segs && run < live) unit_key[run] = k;
+    run += segs;
+  }
+  __syncthreads();
+  const uint32_t up = (live + DS_THREADS - 1) / DS_THREADS;
+  const uint32_t u0 = min(tid * up, live), u1 = min(u0 + up, live);
+  uint32_t m = 0;
+  for (uint32_t u = u0; u < u1; u++) m = max(m, unit_key[u]);
+  const uint32_t incl = wave_incl_max(m);
+  if (lane == 63) sh_w[wv] = incl;
+  uint32_t carry = (uint32_t)__shfl_up((int)incl, 1, 64);
+  if (lane == 0) carry = 0;
+  __syncthreads();
+  for (uint32_t w = 0; w < wv; w++) carry = max(carry, sh_w[w]);
+  for (uint32_t u = u0; u < u1; u++) {
+    carry = max(carry, unit_key[u]);
+    unit_key[u] = carry;
+  }
+}
+
+// One tree level of a lane group through `x` ([word][lane], so a level's reads and writes walk
+// consecutive banks): lanes [d, 2 d) hand their points to lanes [0, d).  `sync` orders the writes
+// before the reads, and the reads before the next level's writes.
+template <uint32_t LANES, typename SYNC>
+__device__ __forceinline__ void dense_tree_level(uint32_t (*x)[LANES], uint32_t l, uint32_t d, xyzt& acc, SYNC&& sync) {
+  if (l >= d && l < 2 * d) {
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+      x[k][l - d] = acc.X.v[k];
+      x[NL + k][l - d] = acc.Y.v[k];
+      x[2 * NL + k][l - d] = acc.T.v[k];
+      x[3 * NL + k][l - d] = acc.Z.v[k];
+    }
+  }
+  sync();
+  if (l < d) {
+    xyzt o;
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+      o.X.v[k] = x[k][l];
+      o.Y.v[k] = x[NL + k][l];
+      o.T.v[k] = x[2 * NL + k][l];
+      o.Z.v[k] = x[3 * NL + k][l];
+    }
+    acc = pt_add(acc, o);
+  }
+  sync();
+}
+
+// (four waves per SIMD asked of the compiler, k_accumulate's occupancy: 132 VGPRs without the bound)
+extern "C" __global__ void __launch_bounds__(DU_THREADS, 4) k_dense_units(const uint32_t* __restrict__ pts,
+                                                                       const uint32_t* __restrict__ sorted_entry,
+                                                                       const uint32_t* __restrict__ bucket_start,
+                                                                       const uint32_t* __restrict__ seg_base,
+                                                                       const uint32_t* __restrict__ unit_key,
+                                                                       uint32_t E, uint32_t nkeys, uint32_t ubound,
+                                                                       uint32_t* __restrict__ buckets,
+                                                                       uint32_t* __restrict__ partials) {
+  __shared__ uint32_t sh_x[DU_THREADS / 64][PT_WORDS][32];
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+  const uint32_t u = blockIdx.x * (DU_THREADS / 64) + wv;
+  // (no workgroup barrier below: a wave past the live units just leaves)
+  if (u >= ubound || u >= seg_base[nkeys]) return;
+  const uint32_t key = min((uint32_t)__builtin_amdgcn_readfirstlane((int)unit_key[u]), nkeys - 1);
+  const uint32_t sb = seg_base[key], nseg = seg_base[key + 1] - sb;
+  const uint32_t S = 64u * E;
+  const uint32_t bend = bucket_start[key + 1];
+  const uint32_t beg = min(bucket_start[key] + (u - sb) * S, bend), end = min(beg + S, bend);
+  xyzt acc = pt_identity();
+  if (end - beg == S) {
+    // a whole segment: E entries per lane, nothing to test
+    const uint32_t* ep = sorted_entry + beg + lane;
+    uint32_t ent = ep[0];
+#pragma unroll 1
+    for (uint32_t j = 1; j <= E; j++) {
+      const pre q = load_pre_signed(pts, ent);
+      if (j < E) ent = ep[64u * j];  // the next entry's load beside this one's add
+      acc = pt_madd(acc, q);
+    }
+  } else {
+    // the bucket's last segment: lanes past its end keep the identity
+#pragma unroll 1
+    for (uint32_t pos = beg + lane; pos < end; pos += 64u) acc = pt_madd(acc, load_pre_signed(pts, sorted_entry[pos]));
+  }
+  // wave-synchronous: the exchange is private to the wave, so its LDS writes and reads need only
+  // keep their program order (the fences hold the compiler to it, the hardware runs a wave's LDS
+  // operations in order)
+  auto sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+#pragma unroll 1
+  for (uint32_t d = 32; d >= 1; d >>= 1) dense_tree_level<32>(sh_x[wv], lane, d, acc, sync);
+  if (lane == 0) store_pt(nseg == 1 ? buckets + (size_t)key * PT_WORDS : partials + (size_t)u * PT_WORDS, acc);
+}
+
+// The buckets of more than one segment: one workgroup per bucket adds its partials, lane l those
+// at l, l + 256, ... (one bucket may hold the whole list: all-equal scalars), then a tree of as
+// many levels as the bucket has live lanes.
+extern "C" __global__ void __launch_bounds__(DF_THREADS) k_dense_fold(const uint32_t* __restrict__ seg_base,
+                                                                      const uint32_t* __restrict__ partials,
+                                                                      uint32_t ubound,
+                                                                      uint32_t* __restrict__ buckets) {
+  __shared__ uint32_t sh_x[PT_WORDS][DF_THREADS / 2];
+  const uint32_t key = blockIdx.x, lt = threadIdx.x;
+  const uint32_t sb = seg_base[key];
+  const uint32_t ns = min(seg_base[key + 1], ubound) - min(sb, ubound);
+  if (ns < 2) return;  // uniform: the bucket is empty, or its one unit stored it
+  xyzt acc = pt_identity();
+  if (lt < ns) acc = load_pt(partials + (size_t)(sb + lt) * PT_WORDS);
+  for (uint32_t i = lt + DF_THREADS; i < ns; i += DF_THREADS)
+    acc = pt_add(acc, load_pt(partials + (size_t)(sb + i) * PT_WORDS));
+  uint32_t top = DF_THREADS / 2;
+  while (top >= ns) top >>= 1;  // the first level that still moves a live lane: top < ns <= 2 top
+#pragma unroll 1
+  for (uint32_t d = top; d >= 1; d >>= 1) dense_tree_level<DF_THREADS / 2>(sh_x, lt, d, acc, [] { __syncthreads(); });
+  if (lt == 0) store_pt(buckets + (size_t)key * PT_WORDS, acc);
+}
+
+// ---------------------------------------------------------------------------------------------
 // bucket reduction:  G_w = sum_{b} (b+1) B_{w,b}
 //   chunk c (L buckets): U_c = sum_i (i+1) B_{cL+i}, T_c = sum_i B_{cL+i}   (running sums)
 //   G_w = sum_c U_c + L * sum_c c T_c = R_{w,V} + sum_k L 2^k R_{w,k},  R_{w,k} = sum_{c: bit k} T_c

@@ -159,6 +159,9 @@ def load() -> ctypes.CDLL:
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_narrow_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_dense_plan": ([sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, u32p],
+                                ctypes.c_int),
+        "msm_test_dense_segments": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
         "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
@@ -976,6 +979,31 @@ def _test_narrow_plan(n: int, scalar_bits: int, window_size: int = 0) -> dict:
     _check(load().msm_test_narrow_plan(n, int(scalar_bits), int(window_size),
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_narrow_plan")
     return dict(zip(("c", "windows", "q", "nhi", "words", "packed"), (int(v) for v in out)))
+
+
+def _test_dense_plan(n: int, nm: int = 1, pipelined: bool = False, scalar_bits: int = 8, window_size: int = 0) -> dict:
+    """The dense-bucket part of a narrow launch's plan (msm_test_dense_plan; no GPU needed): whether
+    the launch takes the dense accumulation, the entries per unit lane E, the keys W * B, the unit
+    kernel's grid bound and the run length K, for the default device shape (256 CUs, 4 waves per
+    SIMD).  E and the bound are 0 for a launch that is not dense."""
+    o, op_ = _out(5)
+    _check(load().msm_test_dense_plan(n, int(nm), 1 if pipelined else 0, int(scalar_bits), int(window_size), op_),
+           "msm_test_dense_plan")
+    return dict(zip(("dense", "E", "nkeys", "units", "K"), (int(v) for v in o)))
+
+
+def _test_dense_segments(bucket_start, S: int) -> Tuple[np.ndarray, np.ndarray]:
+    """k_dense_segments alone on the device (test hook): bucket_start [nkeys + 1] (non-decreasing)
+    and the segment length S -> (seg_base [nkeys + 1], unit_key [bucket_start[-1] // S + nkeys]);
+    unit_key's words past the live units come back as 0xffffffff."""
+    bs = np.ascontiguousarray(_u32(bucket_start).reshape(-1))
+    nkeys = bs.shape[0] - 1
+    if nkeys < 1:
+        raise ValueError("bucket_start holds nkeys + 1 words")
+    seg, seg_ = _out(nkeys + 1)
+    unit, unit_ = _out(int(bs[-1]) // int(S) + nkeys)
+    _check(load().msm_test_dense_segments(_ptr(bs), nkeys, int(S), seg_, unit_), "msm_test_dense_segments")
+    return seg, unit
 
 
 def _test_subset_plan(n_handle: int, levels: int, window_size: int, first: int, m: int, indexed: bool) -> dict:
