@@ -15,7 +15,8 @@
  *                   (Aleo's msm over affine points) does, so an inconsistent t does not change it
  *   scalar        : 8 x uint32 big-endian = full 256-bit integer (not reduced mod r); the
  *                   msm_bases_compute* entries also take narrow scalars of ceil(b / 32) words
- *                   (MSM_FLAG_SCALAR_BITS below)
+ *                   (MSM_FLAG_SCALAR_BITS below) and native integer arrays, signed ones included
+ *                   (MSM_FLAG_SCALAR_TYPE below)
  *   result        : x | y affine = 16 x uint32; identity = (0, 1)
  */
 #ifndef MSM_MI355X_H
@@ -48,6 +49,7 @@ extern "C" {
 #define MSM_FLAG_WINDOWS 4u /* the window-range fields (window_lo, window_hi) are set: see below  */
 #define MSM_FLAG_HALF_WINDOWS 8u /* with MSM_FLAG_WINDOWS: window_lo / window_hi count half windows */
 #define MSM_FLAG_SCALAR_BITS 16u /* scalar_bits is set: narrow scalars (msm_bases_compute* only, below) */
+#define MSM_FLAG_SCALAR_TYPE 32u /* the options are a msm_opts_typed: native integer scalars (msm_bases_compute* only) */
 
 #define MSM_MAX_DEVICES 16
 
@@ -143,6 +145,58 @@ uint32_t msm_window_count(uint32_t window_bits);
  * aligned -- the kernels read scalars with 16-byte vector loads.  The narrow recode reads a vector
  * that is only 4-byte aligned (a slice of a larger tensor at b <= 32, say) word by word instead, at
  * a lower rate; host arrays need only their natural 4-byte alignment. */
+
+/* Native scalar types (MSM_FLAG_SCALAR_TYPE): a column that already is an array of int8 / uint8 / ..
+ * / int64 / uint64 elements, or a bitmap, goes to the msm_bases_compute* entries as it is -- no
+ * rewrite into big-endian words, and an upload of ceil(m e / 8) bytes per vector of m scalars.
+ *
+ *   MSM_SCALAR_BIT                e = 1: scalar i is bit (i & 7) of byte (i >> 3), value 0 or 1
+ *                                 (numpy's packbits(bitorder="little")); a vector of m scalars is
+ *                                 ceil(m / 8) bytes and the pad bits of its last byte are ignored
+ *   MSM_SCALAR_U8 / U16 / U32 / U64   e = 8 / 16 / 32 / 64 bits, contiguous, the host's (little-
+ *                                 endian) byte order, unsigned
+ *   MSM_SCALAR_I8 / I16 / I32 / I64   the same, two's complement
+ *
+ * The field is appended to the options: the caller fills a msm_opts_typed (a msm_opts followed by
+ * scalar_type, so the bytes of every shorter struct in use keep their meaning), sets the flag and
+ * passes &typed.opts; the library reads scalar_type only when the flag is set.
+ *
+ * Result: sum v_i P_i over the integers v_i; a negative v contributes |v| (-P_i).  It is the group
+ * element the narrow call gives for the magnitudes |v_i| on bases with P_i negated where v_i < 0.
+ * The signed-digit recode flips the digit's sign per scalar; nothing after it knows of the type.
+ *
+ * Width: with MSM_FLAG_SCALAR_BITS also set, scalar_bits = b bounds the magnitude, |v| < 2^b with
+ * 1 <= b <= e; without it b = e (which covers -2^(e-1)).  For MSM_SCALAR_BIT b must be 1 or unset.
+ * b = 0, b > e or an unknown scalar_type give MSM_ERR_INVALID_ARG.  The launch geometry is exactly the
+ * narrow geometry of b -- the same windows, the same auto width, the same dense-bucket rule.
+ *
+ * A magnitude of 2^b or more (possible only when b < e) gives MSM_ERR_INVALID_ARG by the rule of the
+ * narrow scalars: the host entries check every vector before anything is uploaded or enqueued; the
+ * device entries mask the magnitude in the recode kernel, so the launch runs to its end, and then
+ * return the error with their results unspecified.
+ *
+ * Honoured by the eight msm_bases_compute* entries (subsets compose unchanged); every other entry that
+ * takes msm_opts, msm_bases_create* included, returns MSM_ERR_INVALID_ARG when the flag is set, before
+ * any device work.  The pointer parameters keep their const uint32_t* type: callers cast.  On a
+ * handle of levels > 1 a typed call runs unfolded on the level-0 records, as a narrow call does.
+ *
+ * Alignment: host vectors need their element's natural alignment; device vectors must be 4-byte
+ * aligned (MSM_ERR_INVALID_ARG otherwise, checked on the host from the pointer value before anything
+ * is enqueued).  16-byte alignment gets the 32- and 64-bit types their vector loads; a vector that is
+ * only 4-byte aligned is read word by word at a lower rate, as in the narrow recode. */
+#define MSM_SCALAR_BIT 1u
+#define MSM_SCALAR_U8 2u
+#define MSM_SCALAR_U16 3u
+#define MSM_SCALAR_U32 4u
+#define MSM_SCALAR_U64 5u
+#define MSM_SCALAR_I8 6u
+#define MSM_SCALAR_I16 7u
+#define MSM_SCALAR_I32 8u
+#define MSM_SCALAR_I64 9u
+typedef struct msm_opts_typed {
+  msm_opts opts;        /* flags has MSM_FLAG_SCALAR_TYPE                                          */
+  uint32_t scalar_type; /* MSM_SCALAR_*: read only when opts.flags & MSM_FLAG_SCALAR_TYPE          */
+} msm_opts_typed;
 
 /* Per-phase device times (ms) of the most recent MSM on the calling thread's device when
  * profiling is enabled (hipEvents on the library's stream). */

@@ -45,6 +45,18 @@ process of its own; every line carries "dense_min", the variable's value, and "d
 lone launch's plan); then the threshold rows with the path forced on (MSM_DENSE_MIN=1) and off:
 b = 8 at 2^13..2^16, b = 12 at 2^17..2^19, and b = 13 at 2^20.
 
+With --native the pass is the native-type sweep of DESIGN.md §9 (MSM_FLAG_SCALAR_TYPE): on a levels-1
+handle of each size, for the types bit, u8, i8, u16, i16, i32, i64 and u64, one line per way of
+computing the MSM of n random values of the type:
+
+  {"entry": "native", "type", "form": "narrow"}  (a) the existing narrow call on the magnitudes as big-endian
+                                                 words (the points of negative values negated in a handle of
+                                                 its own), with "convert_ms": the numpy conversion its
+                                                 caller pays (magnitudes to [n, ceil(b / 32)] big-endian u32)
+  {"entry": "native", "type", "form": "typed"}   (b) Bases.compute*(scalar_type=type) on the array as it is
+
+with the narrow sweep's four timings and the per-phase times of one profiled awaited call.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -346,6 +358,120 @@ def narrow_pass(a):
     return 1 if bad else 0
 
 
+def native_pass(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import as_xy, scalar_dot
+    from oracle import oracle as O
+
+    n, count, k0, step = a.n, a.count, 3, 5
+    bad = []
+
+    def emit(d):
+        d = {"n": n, **d}
+        if not d.get("correct", True):
+            bad.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()
+
+    phases = ("recode_count", "coarse_scatter", "fine_sort", "accumulate", "bucket_reduce_1", "bucket_reduce_2",
+              "device_total")
+
+    def profile(fn):
+        M.set_profiling(1)
+        try:
+            fn()
+            p = M.last_profile()
+        finally:
+            M.set_profiling(0)
+        return {**{k: round(float(p[k]), 4) for k in phases}, "windows": int(p["windows"]), "c": int(p["window_bits"]),
+                "run_length": int(p["run_length"])}
+
+    def measure(row, exp, host1, dev1, host_many, dev_many):
+        ok = True
+        for key, fn, many in (("single_host", host1, False), ("single_device", dev1, False),
+                              ("pipelined_host", host_many, True), ("pipelined_device", dev_many, True)):
+            ms, runs, res = timed(fn, a.runs)
+            if many:
+                row[key + "_ms_per_msm"] = round(ms / count, 4)
+                ok = ok and [as_xy(r) for r in res] == [exp] * count
+            else:
+                row[key + "_ms"] = round(ms, 4)
+                ok = ok and res == exp
+            row[key + "_runs_ms"] = runs
+        row["phases_ms"] = profile(dev1)
+        row["correct"] = ok
+        emit(row)
+
+    def to_words(mag, words):
+        """Magnitudes (uint64) as [n, words] big-endian u32: the rewrite the narrow call's caller pays."""
+        out = np.empty((n, words), np.uint32)
+        out[:, words - 1] = mag & np.uint64(0xffffffff)
+        if words == 2:
+            out[:, 0] = mag >> np.uint64(32)
+        return out
+
+    pts = M.gen_points(n, k0=k0, step=step)
+    neg_pts = pts.copy()  # every point negated: x -> -x mod p, t -> -t mod p (multi-word, in numpy)
+    pw = np.array(O.int_to_be_words(O.P), dtype=np.int64)
+    for j in (0, 2):
+        d = pw[None, :] - pts[:, 8 * j:8 * j + 8].astype(np.int64)
+        for k in range(7, 0, -1):  # borrows
+            borrow = d[:, k] < 0
+            d[:, k] += borrow.astype(np.int64) << 32
+            d[:, k - 1] -= borrow
+        zero = ~pts[:, 8 * j:8 * j + 8].any(axis=1)
+        d[zero] = 0
+        neg_pts[:, 8 * j:8 * j + 8] = d.astype(np.uint32)
+    ks = k0 + step * np.arange(n, dtype=np.uint64)
+    rnd = np.random.RandomState(31)
+    with M.Bases.from_wire(pts, levels=1) as plain:
+        for ty in a.native_types:
+            _, dt, e = M.SCALAR_TYPES[ty]
+            signed = ty[0] == "i"
+            if ty == "bit":
+                vals = rnd.randint(0, 2, size=n).astype(np.int64)
+                arr = np.packbits(vals.astype(np.uint8), bitorder="little")
+            else:
+                raw = rnd.randint(0, 1 << 32, size=n, dtype=np.uint64) | rnd.randint(0, 1 << 32, size=n, dtype=np.uint64) << np.uint64(32)
+                arr = raw.astype(np.uint64).view(np.uint64).astype(dt) if not signed else raw.view(np.int64).astype(dt)
+                vals = arr
+            t0 = time.perf_counter()
+            isneg = (vals < 0) if signed else np.zeros(n, bool)
+            mag = np.where(isneg, (0 - vals.astype(np.int64)).astype(np.uint64) if signed else 0,
+                           vals.astype(np.uint64)).astype(np.uint64)
+            words = (e + 31) // 32
+            sc = to_words(mag, words)
+            convert_ms = (time.perf_counter() - t0) * 1e3
+            sc8p, sc8n = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
+            sc8p[~isneg, 8 - words:] = sc[~isneg]
+            sc8n[isneg, 8 - words:] = sc[isneg]
+            exp = O.scalar_mul(O.G, (scalar_dot(ks, sc8p) - scalar_dot(ks, sc8n)) % O.R_ORDER)
+            base = {"entry": "native", "type": ty, "bits": e, "count": count, "vector_bytes": int(arr.nbytes)}
+            d_sc, d_arr = torch.from_numpy(sc.view(np.int32)).cuda(), dev(arr)
+            kw = {"scalar_bits": e}
+            # (a) the narrow call on the magnitudes, over a handle whose points carry the signs
+            with M.Bases.from_wire(np.where(isneg[:, None], neg_pts, pts), levels=1) as signed_bases:
+                measure({**base, "form": "narrow", "convert_ms": round(convert_ms, 4)}, exp,
+                        lambda: signed_bases.compute(sc, **kw), lambda: signed_bases.compute_device(d_sc, **kw),
+                        lambda: signed_bases.compute_many([sc] * count, **kw),
+                        lambda: signed_bases.compute_many_device([d_sc] * count, **kw))
+            # (b) the typed call on the array as it is
+            tk = {"scalar_type": ty}
+            measure({**base, "form": "typed"}, exp,
+                    lambda: plain.compute(arr, **tk), lambda: plain.compute_device(d_arr, **tk),
+                    lambda: plain.compute_many([arr] * count, **tk),
+                    lambda: plain.compute_many_device([d_arr] * count, **tk))
+    return 1 if bad else 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -397,6 +523,8 @@ def main():
     ap.add_argument("--narrow-equal", action="store_true", help="a narrow row of all-equal bytes as well")
     ap.add_argument("--no-extended", action="store_true", help="the narrow pass without its 8-word rows")
     ap.add_argument("--dense", action="store_true", help="the dense-bucket sweep (DENSE_MIN, MSM_DENSE_MIN) instead")
+    ap.add_argument("--native", action="store_true", help="the native-type sweep (MSM_FLAG_SCALAR_TYPE) instead")
+    ap.add_argument("--native-types", default="bit,u8,i8,u16,i16,i32,i64,u64", help="types of the native sweep")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
@@ -412,6 +540,19 @@ def main():
                "--subset", "--subset-sizes", ",".join(map(str, a.subset_sizes)), "--count", str(a.count),
                "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
         return subprocess.run(cmd).returncode
+    if a.native:
+        a.native_types = [x for x in str(a.native_types).split(",") if x]
+        if a.n:
+            return native_pass(a)
+        for lg in (int(x) for x in a.sizes.split(",")):
+            cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n",
+                   str(1 << lg), "--native", "--native-types", ",".join(a.native_types), "--count", str(a.count),
+                   "--runs", str(a.runs)]
+            rc = subprocess.run(cmd + (["--out", a.out] if a.out else [])).returncode
+            if rc != 0:
+                print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)
+                return rc
+        return 0
     if a.narrow:
         a.narrow_bits = [int(x) for x in str(a.narrow_bits).split(",")]
         a.narrow_widths = [int(x) for x in str(a.narrow_widths).split(",") if x]

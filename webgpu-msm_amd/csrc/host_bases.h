@@ -134,7 +134,14 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   // Narrow scalars (MSM_FLAG_SCALAR_BITS): below 254 bits the call runs unfolded on the level-0
   // records, whatever the handle's levels -- they are plain prepared records -- over the scalars'
   // own geometry (make_plan); 254 bits and more are the 8-word call as it is.
-  const uint32_t sbits = narrow_flagged(opts) ? opts->scalar_bits : 256;
+  // Native scalar types (MSM_FLAG_SCALAR_TYPE): the narrow call of b = scalar_bits, or of the element's
+  // own width where that is unset, on the caller's own integer array.
+  const bool bits_set = opts && (opts->flags & MSM_FLAG_SCALAR_BITS);
+  const uint32_t stype = opts_scalar_type(opts);
+  if (typed_flagged(opts) && !typed_width(stype, bits_set, bits_set ? opts->scalar_bits : 0)) return MSM_ERR_INVALID_ARG;
+  const uint32_t ebits = scalar_type_bits(stype);
+  const uint32_t sbits = stype ? typed_width(stype, bits_set, bits_set ? opts->scalar_bits : 0)
+                               : bits_set ? opts->scalar_bits : 256;
   if (sbits < 1 || sbits > 256) return MSM_ERR_INVALID_ARG;
   const bool narrow = sbits < MAIN_BITS;
   const uint32_t levels = narrow ? 1u : b->levels;
@@ -151,7 +158,8 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
     }
   }
   if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
-  msm_opts o{};
+  msm_opts_typed ot{};
+  msm_opts& o = ot.opts;
   o.run_length = opts ? opts->run_length : 0;
   o.flags = opts ? (opts->flags & MSM_FLAG_SERIAL) : 0;
   o.device = b->device;
@@ -159,6 +167,10 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   if (narrow) {
     o.flags |= MSM_FLAG_SCALAR_BITS;
     o.scalar_bits = sbits;
+  }
+  if (stype) {
+    o.flags |= MSM_FLAG_SCALAR_TYPE;
+    ot.scalar_type = stype;
   }
   if (levels > 1) {
     if (o.window_bits && o.window_bits != b->window_bits) return MSM_ERR_INVALID_ARG;
@@ -168,13 +180,54 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
     o.window_hi = b->geo.Wc;
   }
   if (count == 0) return MSM_OK;
-  for (size_t k = 0; k < count; k++)
+  for (size_t k = 0; k < count; k++) {
     if (!scalars[k] && terms) return MSM_ERR_INVALID_ARG;
+    // a native vector's alignment, from the pointer value: the element's own on the host, 4 bytes on
+    // the device (the recode reads whole words)
+    if (stype && (reinterpret_cast<uintptr_t>(scalars[k]) & (host ? std::max(ebits / 8, 1u) - 1u : 3u)))
+      return MSM_ERR_INVALID_ARG;
+  }
   // A bit at or above scalar_bits: host vectors are checked on the host, before anything is uploaded
   // or enqueued (the device entries' by k_recode_narrow); only the most significant word can hold
   // one.  Large vectors go over the device context's parked packing threads (the strided read of
   // 2^20 8-word scalars is ~0.5 ms on one thread); a vector given again is checked once.
+  // A native type's magnitude of 2^sbits or more (possible only below the element's width): the OR of
+  // the vector's magnitudes, formed as the recode forms them, has a bit at or above sbits.
+  auto native_scan = [&](const uint32_t* vec, size_t i0, size_t i1) -> uint64_t {
+    uint64_t a = 0;
+    auto mags = [&](auto* p, auto zero) {
+      using U = decltype(zero);
+      for (size_t i = i0; i < i1; i++) {
+        const U u = (U)p[i];
+        a |= p[i] < 0 ? (U)((U)0 - u) : u;
+      }
+    };
+    switch (stype) {
+      case MSM_SCALAR_U8: mags(reinterpret_cast<const uint8_t*>(vec), (uint8_t)0); break;
+      case MSM_SCALAR_I8: mags(reinterpret_cast<const int8_t*>(vec), (uint8_t)0); break;
+      case MSM_SCALAR_U16: mags(reinterpret_cast<const uint16_t*>(vec), (uint16_t)0); break;
+      case MSM_SCALAR_I16: mags(reinterpret_cast<const int16_t*>(vec), (uint16_t)0); break;
+      case MSM_SCALAR_U32: mags(reinterpret_cast<const uint32_t*>(vec), (uint32_t)0); break;
+      case MSM_SCALAR_I32: mags(reinterpret_cast<const int32_t*>(vec), (uint32_t)0); break;
+      case MSM_SCALAR_U64: mags(reinterpret_cast<const uint64_t*>(vec), (uint64_t)0); break;
+      case MSM_SCALAR_I64: mags(reinterpret_cast<const int64_t*>(vec), (uint64_t)0); break;
+      default: break;  // MSM_SCALAR_BIT: b = e = 1
+    }
+    return a;
+  };
   auto host_scalars_ok = [&](DevCtx* c) -> bool {
+    if (stype) {
+      if (!host || sbits >= ebits) return true;
+      for (size_t k = 0; k < count; k++) {
+        if (k && scalars[k] == scalars[k - 1]) continue;
+        std::atomic<uint64_t> any{0};
+        auto scan = [&](int t, int nt) { any.fetch_or(native_scan(scalars[k], terms * t / nt, terms * (t + 1) / nt)); };
+        if (terms >= (1u << 17)) ctx_packer(c)->run(scan);
+        else scan(0, 1);
+        if (any.load() >> sbits) return false;
+      }
+      return true;
+    }
     if (!host || sbits == 256 || !(sbits & 31u)) return true;
     const size_t sw = (sbits + 31) / 32;
     const uint32_t excess = ~((1u << (sbits & 31u)) - 1u);

@@ -96,6 +96,11 @@ struct Plan {
   // The dense-bucket accumulation (finish_plan; k_dense_* in the place of k_accumulate): entries per
   // unit lane E (a unit's segment is 64 E entries) and the unit kernel's grid bound.  Zero otherwise.
   uint32_t dense, dense_E, dense_units;
+  // Native scalar types (msm_opts_typed): MSM_SCALAR_* of the launch's vectors, 0 for word formats, and
+  // the bytes of one vector, ceil(n e / 8).  The geometry in `d` is the narrow one of d.sbits and knows
+  // nothing of the type: only the recode kernel's choice and the upload's length follow it.
+  uint32_t stype;
+  size_t sc_bytes;
 };
 
 // Every field that shapes a launch (grids, buffer offsets, the h_out layout): a captured graph is
@@ -110,7 +115,7 @@ bool plan_eq(const Plan& a, const Plan& b) {
          x.first == y.first && x.sm == y.sm && x.sw == y.sw && x.sbits == y.sbits && a.K == b.K && a.L == b.L &&
          a.nchunks == b.nchunks && a.nv == b.nv && a.nterms == b.nterms && a.Mmax == b.Mmax &&
          a.runs_max == b.runs_max && a.pfmt == b.pfmt && a.dense == b.dense && a.dense_E == b.dense_E &&
-         a.dense_units == b.dense_units;
+         a.dense_units == b.dense_units && a.stype == b.stype && a.sc_bytes == b.sc_bytes;
 }
 
 // Device workspace of one MSM (all sizes from Plan; grown on demand, never shrunk).

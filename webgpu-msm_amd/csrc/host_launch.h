@@ -132,8 +132,33 @@ NarrowBias narrow_bias(const MsmDims& d) {
   return nb;
 }
 
-void launch_recode(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
+// The native recode (Plan::stype): one k_recode_native instantiation per element width, signedness
+// and code width.  MSM_SCALAR_U32 has the bytes of the one-word narrow format: k_recode_narrow<T, 1>.
+template <typename T>
+const void* recode_native_fn(uint32_t stype) {
+  switch (stype) {
+    case MSM_SCALAR_BIT: return reinterpret_cast<const void*>(&k_recode_native<T, 1, false>);
+    case MSM_SCALAR_U8: return reinterpret_cast<const void*>(&k_recode_native<T, 8, false>);
+    case MSM_SCALAR_I8: return reinterpret_cast<const void*>(&k_recode_native<T, 8, true>);
+    case MSM_SCALAR_U16: return reinterpret_cast<const void*>(&k_recode_native<T, 16, false>);
+    case MSM_SCALAR_I16: return reinterpret_cast<const void*>(&k_recode_native<T, 16, true>);
+    case MSM_SCALAR_I32: return reinterpret_cast<const void*>(&k_recode_native<T, 32, true>);
+    case MSM_SCALAR_U64: return reinterpret_cast<const void*>(&k_recode_native<T, 64, false>);
+    case MSM_SCALAR_I64: return reinterpret_cast<const void*>(&k_recode_native<T, 64, true>);
+    default: return reinterpret_cast<const void*>(&k_recode_narrow<T, 1>);  // MSM_SCALAR_U32
+  }
+}
+constexpr uint32_t NATIVE_TYPES[] = {MSM_SCALAR_BIT, MSM_SCALAR_U8,  MSM_SCALAR_U16, MSM_SCALAR_U32, MSM_SCALAR_U64,
+                                     MSM_SCALAR_I8,  MSM_SCALAR_I16, MSM_SCALAR_I32, MSM_SCALAR_I64};
+// The recode kernel of a narrow or native plan (both take k_recode_narrow's six arguments).
+const void* recode_kernel(const Plan& pl) {
+  if (!pl.stype) return recode_narrow_kernel(pl.d);
+  return pl.d.c > 16 ? recode_native_fn<uint32_t>(pl.stype) : recode_native_fn<uint16_t>(pl.stype);
+}
+
+void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
                    hipStream_t s) {
+  const MsmDims& d = pl.d;
   const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
   const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;  // histogram + window totals
   if (d.sw) {
@@ -141,7 +166,7 @@ void launch_recode(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t
     MsmDims dd = d;
     NarrowBias nb = narrow_bias(d);
     void* args[] = {&scal, &dd, &digits, &colsum, &nb, &err};
-    (void)hipLaunchKernel(recode_narrow_kernel(d), grid, dim3(RC_THREADS), args, lds, s);
+    (void)hipLaunchKernel(recode_kernel(pl), grid, dim3(RC_THREADS), args, lds, s);
     return;
   }
   if (d.c > 16) {
@@ -174,6 +199,9 @@ bool is_recode_kernel(const void* f) {
   // the narrow recodes too: a replayed graph must not read the previous call's scalars
   for (uint32_t sw = 1; sw <= 8; sw++)
     if (f == recode_narrow_fn<uint16_t>(sw) || f == recode_narrow_fn<uint32_t>(sw)) return true;
+  // and every native one: the same trap
+  for (uint32_t ty : NATIVE_TYPES)
+    if (f == recode_native_fn<uint16_t>(ty) || f == recode_native_fn<uint32_t>(ty)) return true;
   return false;
 }
 
@@ -220,7 +248,7 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
       mark(PH_START);
       mark(PH_PREPARE);
     }
-    launch_recode(d, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), w.err.as<uint32_t>(), s);
+    launch_recode(pl, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), w.err.as<uint32_t>(), s);
     mark(PH_RECODE);
     mark(PH_SCAN);
     if (d.sub != MSM_SUB_NONE) {

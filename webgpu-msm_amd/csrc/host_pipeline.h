@@ -61,6 +61,7 @@ struct ManyRun {
   uint32_t kf = 1, nm = 1;    // levels of a folded launch; MSMs per launch
   size_t np = 0, nbatch = 0;  // points the plan sees per MSM; launches
   size_t sw = 8, scs = 0;     // words per wire scalar, and between the MSMs' scalars in a slot's wire buffer
+  size_t sc_bytes = 0;        // bytes of one MSM's scalar vector: n sw words, or ceil(n e / 8) of a native type
   int nslot = 1;
   Plan pl;
   uint32_t* pts_shared = nullptr;
@@ -118,9 +119,11 @@ struct ManyRun {
     // Words per wire scalar (a narrow launch on a handle: pl.d.sw, else 8) and the words between the
     // MSMs' scalars in a slot's wire buffer: a narrow MSM's vector is padded to whole 16-B units so
     // that every MSM's scalars start aligned for k_recode_narrow's vector loads.
+    // A native type's vector (pl.stype) is counted in bytes, ceil(n e / 8), and padded the same way.
     narrow = pl.d.sw != 0;
     sw = narrow ? pl.d.sw : 8;
-    scs = narrow ? (n * sw + 3) & ~(size_t)3 : n * 8;
+    sc_bytes = pl.stype ? pl.sc_bytes : n * sw * 4;
+    scs = pl.stype ? typed_region_bytes(n, pl.stype) / 4 : narrow ? (n * sw + 3) & ~(size_t)3 : n * 8;
     // host inputs: one more launch in flight, so its upload queues behind the running ones
     // (2^20 msm_compute 4.21 -> 4.05 ms with three, profiles/r2t_*; device inputs are best with two)
     const int want = pipeline_slots(n, o) + (host && !(o && (o->flags & MSM_FLAG_SERIAL)) && !knob_slots_set() ? 1 : 0);
@@ -278,7 +281,16 @@ struct ManyRun {
           c, nreal, n, per, [&](uint32_t m) { return src[j * nm + m]; }, [&](uint32_t m) { return len_of(j * nm + m); },
           [&](uint32_t m) { return const_cast<uint32_t*>(dst.p[m]); });
     };
-    if (!in.dev_scalars && !up(in.scalars, bs, sw)) return MSM_ERR_HIP;
+    if (pl.stype) {
+      // a native type's vectors are bytes, not whole words per scalar: one copy each (the padding
+      // MSMs of a short last launch read the last real MSM's region, launch_inputs)
+      for (uint32_t m = 0; m < nreal; m++)
+        if (hipMemcpyAsync(const_cast<uint32_t*>(bs.p[m]), in.scalars[j * nm + m], sc_bytes, hipMemcpyHostToDevice,
+                           c->copy_stream) != hipSuccess)
+          return MSM_ERR_HIP;
+    } else if (!in.dev_scalars && !up(in.scalars, bs, sw)) {
+      return MSM_ERR_HIP;
+    }
     if (indexed) {
       // the launch's index vectors into the slot's own buffer (validated by the entry: no kernel);
       // the padding MSMs of a short last launch repeat the last real MSM's, as they do its scalars

@@ -131,6 +131,36 @@ struct SubsetGeo {
 
 constexpr uint32_t NARROW_WIDE_C = 17, NARROW_DENSE = 64;  // the narrow launches' auto width (make_plan)
 
+// Native scalar types (include/msm.h MSM_FLAG_SCALAR_TYPE): element bits e and signedness of a
+// MSM_SCALAR_* value (e = 0: unknown), and the type an options struct carries (0: none).
+uint32_t scalar_type_bits(uint32_t type) {
+  switch (type) {
+    case MSM_SCALAR_BIT: return 1;
+    case MSM_SCALAR_U8: case MSM_SCALAR_I8: return 8;
+    case MSM_SCALAR_U16: case MSM_SCALAR_I16: return 16;
+    case MSM_SCALAR_U32: case MSM_SCALAR_I32: return 32;
+    case MSM_SCALAR_U64: case MSM_SCALAR_I64: return 64;
+    default: return 0;
+  }
+}
+bool scalar_type_signed(uint32_t type) { return type >= MSM_SCALAR_I8 && type <= MSM_SCALAR_I64; }
+bool typed_flagged(const msm_opts* o) { return o && (o->flags & MSM_FLAG_SCALAR_TYPE); }
+uint32_t opts_scalar_type(const msm_opts* o) {
+  return typed_flagged(o) ? reinterpret_cast<const msm_opts_typed*>(o)->scalar_type : 0u;
+}
+// The magnitude bits b of a typed call: scalar_bits where MSM_FLAG_SCALAR_BITS is set (1..e; a bit
+// vector's must be 1), else e.  0: an argument error.
+uint32_t typed_width(uint32_t type, bool has_bits, uint32_t bits) {
+  const uint32_t e = scalar_type_bits(type);
+  if (!e) return 0;
+  if (!has_bits) return e;
+  return bits >= 1 && bits <= e ? bits : 0;
+}
+// Bytes of a vector of n elements, and of its region in a slot's wire buffer (whole 16-B units, so
+// that every MSM's vector starts aligned for the recode's vector loads).
+size_t typed_vector_bytes(size_t n, uint32_t type) { return (n * scalar_type_bits(type) + 7) / 8; }
+size_t typed_region_bytes(size_t n, uint32_t type) { return (typed_vector_bytes(n, type) + 15) & ~(size_t)15; }
+
 int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined = false, uint32_t nm = 1,
               bool shared = false, const SubsetGeo* sub = nullptr) {
   *pl = Plan{};
@@ -179,7 +209,17 @@ int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pi
       d.Wr = wn;
       d.sw = (b + 31) / 32;
       d.sbits = b;
+      // a native type: the narrow geometry of b as it is; the plan only remembers the type
+      if (const uint32_t ty = opts_scalar_type(o)) {
+        if (typed_width(ty, true, b) != b) return MSM_ERR_INVALID_ARG;
+        pl->stype = ty;
+        pl->sc_bytes = typed_vector_bytes(n, ty);
+      }
+    } else if (typed_flagged(o)) {
+      return MSM_ERR_INVALID_ARG;
     }
+  } else if (typed_flagged(o)) {
+    return MSM_ERR_INVALID_ARG;  // (the entry resolves an unset width to the element's before it plans)
   }
   if (o && (o->flags & MSM_FLAG_WINDOWS)) {
     // a window range needs an explicit width, so that every caller's ranges cut the same windows

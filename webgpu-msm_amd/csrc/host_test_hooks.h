@@ -408,6 +408,27 @@ int msm_test_narrow_plan(size_t n, uint32_t scalar_bits, uint32_t window_bits, u
   return MSM_OK;
 }
 
+// The plan of one native-type MSM (MSM_FLAG_SCALAR_TYPE with MSM_FLAG_SCALAR_BITS) of n terms:
+// out = msm_test_narrow_plan's six fields for scalar_bits, then the bytes of one vector and of its
+// region in a slot's wire buffer.  The entry's argument rules apply (unknown type, scalar_bits 0 or
+// past the element's width, a bit vector wider than 1: MSM_ERR_INVALID_ARG).  Host code only.
+int msm_test_native_plan(size_t n, uint32_t scalar_type, uint32_t scalar_bits, uint32_t window_bits, uint32_t out[8]) {
+  if (!out || !typed_width(scalar_type, true, scalar_bits)) return MSM_ERR_INVALID_ARG;
+  msm_opts_typed op{};
+  op.opts.window_bits = window_bits;
+  op.opts.flags = MSM_FLAG_SCALAR_BITS | MSM_FLAG_SCALAR_TYPE;
+  op.opts.scalar_bits = scalar_bits;
+  op.scalar_type = scalar_type;
+  Plan pl;
+  if (int rc = make_plan(n, &op.opts, DevShape{}, &pl, false, 1, true)) return rc;
+  if (pl.stype != scalar_type) return MSM_ERR_INVALID_ARG;
+  const uint32_t v[8] = {pl.d.c,  pl.d.Wr,     pl.d.q,
+                         pl.d.nhi, pl.d.sw,    pl.d.packed,
+                         (uint32_t)pl.sc_bytes, (uint32_t)typed_region_bytes(n, scalar_type)};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
 // The dense-bucket part of the plan of a narrow launch (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
 // of nm MSMs of n terms at width window_bits (0: auto), pipelined or lone: out = {dense (0 / 1),
 // entries per unit lane E, keys W * B, the unit kernel's grid bound, run length K}, for the default

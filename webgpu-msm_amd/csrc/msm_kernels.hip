@@ -9,7 +9,9 @@
 //                      written window-major (= first sort level: one contiguous array per window),
 //                      with the coarse-bin totals (LDS histogram, flushed with global atomics);
 //                      k_recode_narrow is the same for scalars of 1..8 words over the windows of
-//                      their own bits (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
+//                      their own bits (msm_bases_compute* with MSM_FLAG_SCALAR_BITS), and
+//                      k_recode_native for the caller's own integer arrays (bit / 8 / 16 / 32 / 64-bit
+//                      elements, signed ones included: MSM_FLAG_SCALAR_TYPE)
 //   k_part_scatter     digits -> coarse bins (each chunk reserves and writes one contiguous slice
 //                      per bin); its range / indexed variants map a subset launch's positions to
 //                      a handle's records (k_stage_indices checks a device caller's indices first)
@@ -864,6 +866,128 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_narrow(BatchPtrs scalar_s
       }
       row += d.n;
       h += d.nbc;
+    }
+  }
+  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  __syncthreads();
+  flush_hist(lds_hist, d, w0, colsum);
+}
+
+// Native integer scalars (msm_opts_typed, MSM_FLAG_SCALAR_TYPE): the vector is the caller's own array
+// of E-bit elements -- E = 1: bit (i & 7) of byte (i >> 3); 8 / 16 / 32 / 64: little-endian integers,
+// two's complement when SIGNED -- over the narrow geometry of d.sbits = b <= E magnitude bits.
+// k_recode_narrow's bias-add and per-window shift on SW + 1 words (SW = 2 at 64 bits, else 1) of the
+// magnitude |v|, formed in unsigned arithmetic so that -2^(E-1) is 2^(E-1); the scalar's sign is one
+// XOR into the digit's: code sign = (digit < 0) != (v < 0).  The histogram counts by magnitude as ever.
+// A lane takes one 32-bit word of bit / 8 / 16-bit elements (32 / 4 / 2 scalars) or 16 B of 32 /
+// 64-bit ones (4 / 2 scalars; word by word where the vector is only 4-B aligned), so a wave reads
+// whole cache lines, and recodes them four at a time.  The lanes that hold the tail of the workgroup's
+// span or of the vector read element by element: nothing past byte ceil(n E / 8) is touched.
+// Magnitude bits at or above b are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE).
+template <uint32_t E>
+__device__ __forceinline__ uint64_t native_elem(const uint32_t* __restrict__ scalars, uint32_t i) {
+  if (E == 1) return (reinterpret_cast<const uint8_t*>(scalars)[i >> 3] >> (i & 7u)) & 1u;
+  if (E == 8) return reinterpret_cast<const uint8_t*>(scalars)[i];
+  if (E == 16) return reinterpret_cast<const uint16_t*>(scalars)[i];
+  if (E == 32) return scalars[i];
+  return (uint64_t)scalars[2 * (size_t)i] | (uint64_t)scalars[2 * (size_t)i + 1] << 32;
+}
+template <typename T, uint32_t E, bool SIGNED>
+__global__ void __launch_bounds__(RC_THREADS) k_recode_native(BatchPtrs scalar_sets, MsmDims d,
+                                                              T* __restrict__ digits, uint32_t* __restrict__ colsum,
+                                                              NarrowBias bias, uint32_t* __restrict__ err) {
+  using DC = DigitCode<T>;
+  constexpr uint32_t SW = E == 64 ? 2 : 1;                     // words of a magnitude
+  constexpr uint32_t R = E <= 16 ? 32 / E : E == 32 ? 4 : 2;   // scalars per lane
+  constexpr uint32_t LW = E <= 16 ? 1 : 4;                     // words per lane
+  constexpr uint32_t CH = R < 4 ? R : 4;                       // scalars recoded together
+  static_assert(E == 1 || E == 8 || E == 16 || E == 32 || E == 64, "element bits");
+  static_assert(!(SIGNED && E == 1), "a bit has no sign");
+  extern __shared__ uint32_t lds_hist[];  // [Wr][nbc]
+  const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
+  const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
+  const uint32_t w0 = blockIdx.y * d.Wr;
+  const uint32_t nh = d.Wr * d.nbc;
+  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
+  const uint64_t mag_mask = d.sbits >= 64 ? ~0ull : (1ull << d.sbits) - 1ull;
+  const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
+  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
+  bool bad = false;
+  __syncthreads();
+  for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
+    const uint32_t cnt = min(R, hi - i);
+    uint32_t raw[LW] = {};
+    if (cnt == R) {  // (i is a multiple of R: the lane's words start at word i E / 32)
+      const uint32_t* p = scalars + ((size_t)i * E >> 5);
+      if (LW == 4 && vec) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        raw[0] = v.x, raw[1 % LW] = v.y, raw[2 % LW] = v.z, raw[3 % LW] = v.w;
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < LW; k++) raw[k] = p[k];
+      }
+    }
+    for (uint32_t g = 0; g < R; g += CH) {
+      if (g >= cnt) break;
+      uint32_t t[CH][SW + 1];
+      bool neg[CH];
+#pragma unroll
+      for (uint32_t r = 0; r < CH; r++) {
+        uint64_t v;
+        if (cnt != R) {
+          v = g + r < cnt ? native_elem<E>(scalars, i + g + r) : 0ull;
+        } else if constexpr (E == 64) {
+          v = (uint64_t)raw[2 * r] | (uint64_t)raw[2 * r + 1] << 32;
+        } else if constexpr (E == 32) {
+          v = raw[r];
+        } else {
+          v = (raw[0] >> ((g + r) * E)) & (0xffffffffu >> (32 - E));
+        }
+        // the magnitude, in E-bit unsigned arithmetic
+        neg[r] = SIGNED && ((v >> (E - 1)) & 1u);
+        if (neg[r]) v = (0ull - v) & (~0ull >> (64 - E));
+        bad = bad || (v & ~mag_mask) != 0;
+        v &= mag_mask;
+        uint32_t cy = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < SW; k++) {
+          const uint64_t x = (uint64_t)(uint32_t)(v >> (32 * k)) + bias.v[k] + cy;
+          t[r][k] = (uint32_t)x;
+          cy = (uint32_t)(x >> 32);
+        }
+        t[r][SW] = cy;
+      }
+      T* row = digits + (size_t)w0 * d.n + i + g;
+      uint32_t* h = lds_hist;
+      for (uint32_t w = 0; w < d.Wr; w++) {
+        const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
+        const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
+        const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
+        uint32_t code[CH];
+#pragma unroll
+        for (uint32_t r = 0; r < CH; r++) {
+          const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
+#pragma unroll
+          for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
+          t[r][SW] >>= b;
+          const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+          const bool live = digit != 0 && g + r < cnt;
+          // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
+          atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
+          code[r] = live ? mag | ((digit < 0) != neg[r] ? DC::SIGN : 0u) : DC::ZERO;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < CH; r += 2) {
+          if (CH > 1 && pair_store && g + r + 1 < cnt) {
+            *reinterpret_cast<uint32_t*>(row + r) = code[r] | code[(r + 1) % CH] << 16;
+          } else {
+            if (g + r < cnt) row[r] = (T)code[r];
+            if (CH > 1 && g + r + 1 < cnt) row[r + 1] = (T)code[(r + 1) % CH];
+          }
+        }
+        row += d.n;
+        h += d.nbc;
+      }
     }
   }
   if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);

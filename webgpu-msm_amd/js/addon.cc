@@ -125,6 +125,7 @@ struct Job {
   uint64_t first = 0;
   std::vector<uint32_t> indices;
   uint32_t scalar_bits = 0;  // computeMsmPrepared: narrow scalars (MSM_FLAG_SCALAR_BITS); 0 = the 8-word format
+  uint32_t scalar_type = 0;  // computeMsmPrepared: a native integer array (MSM_FLAG_SCALAR_TYPE); 0 = a word format
   uint32_t out[16] = {0};
   int rc = 0;
 };
@@ -142,12 +143,17 @@ void execute(napi_env, void* data) {
   }
   const uint32_t* pts = j->p_points ? j->p_points : j->stage ? j->stage->points.data() : j->points.data();
   const uint32_t* sc = j->p_scalars ? j->p_scalars : j->stage ? j->stage->scalars.data() : j->scalars.data();
-  msm_opts ob;  // the handle entries' options: the scalars' width only
-  memset(&ob, 0, sizeof(ob));
+  msm_opts_typed obt;  // the handle entries' options: the scalars' width and type only
+  memset(&obt, 0, sizeof(obt));
+  msm_opts& ob = obt.opts;
   ob.device = -1;
   if (j->scalar_bits) {
     ob.flags = MSM_FLAG_SCALAR_BITS;
     ob.scalar_bits = j->scalar_bits;
+  }
+  if (j->scalar_type) {
+    ob.flags |= MSM_FLAG_SCALAR_TYPE;
+    obt.scalar_type = j->scalar_type;
   }
   if (j->bases && j->subset) {
     const uint32_t* ix = j->indices.data();
@@ -214,6 +220,44 @@ bool get_u32_array(napi_env env, napi_value v, const uint32_t** data, size_t* le
     if (napi_is_arraybuffer(env, ab, &plain) != napi_ok) return false;
     *shared = !plain;
   }
+  return true;
+}
+
+// computeMsmPrepared's `scalarType`: the MSM_SCALAR_* value of a name, the typed-array class that
+// holds such a vector and its element bits.
+struct NativeType {
+  const char* name;
+  uint32_t type;
+  napi_typedarray_type cls;
+  uint32_t bits;
+};
+const NativeType NATIVE_TYPES[] = {
+    {"bit", MSM_SCALAR_BIT, napi_uint8_array, 1},        {"u8", MSM_SCALAR_U8, napi_uint8_array, 8},
+    {"i8", MSM_SCALAR_I8, napi_int8_array, 8},           {"u16", MSM_SCALAR_U16, napi_uint16_array, 16},
+    {"i16", MSM_SCALAR_I16, napi_int16_array, 16},       {"u32", MSM_SCALAR_U32, napi_uint32_array, 32},
+    {"i32", MSM_SCALAR_I32, napi_int32_array, 32},       {"u64", MSM_SCALAR_U64, napi_biguint64_array, 64},
+    {"i64", MSM_SCALAR_I64, napi_bigint64_array, 64}};
+const NativeType* native_type(napi_env env, napi_value v) {
+  char name[8] = {0};
+  size_t len = 0;
+  if (napi_get_value_string_utf8(env, v, name, sizeof(name), &len) != napi_ok) return nullptr;
+  for (const NativeType& t : NATIVE_TYPES)
+    if (!strcmp(name, t.name)) return &t;
+  return nullptr;
+}
+// A typed array of exactly the class `cls`: its bytes and element count.
+bool get_typed_array(napi_env env, napi_value v, napi_typedarray_type cls, const void** data, size_t* len, bool* shared) {
+  bool is_ta = false;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return false;
+  napi_typedarray_type t;
+  void* d;
+  napi_value ab;
+  size_t off;
+  if (napi_get_typedarray_info(env, v, &t, len, &d, &ab, &off) != napi_ok || t != cls) return false;
+  *data = d;
+  bool plain = true;  // napi_is_arraybuffer is false for a SharedArrayBuffer
+  if (napi_is_arraybuffer(env, ab, &plain) != napi_ok) return false;
+  *shared = !plain;
   return true;
 }
 
@@ -554,10 +598,19 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
 // Uint32Array) the MSM runs over a subset of the handle's bases and the scalar array gives its
 // length (msm_bases_compute_subset); with neither (absent or undefined) over all of them.  With
 // `scalarBits` = b (1..256) the scalars are narrow: ceil(b / 32) words each (MSM_FLAG_SCALAR_BITS).
+// With `scalarType` (a name of NATIVE_TYPES) the scalars are a typed array of that integer type as it is
+// (MSM_FLAG_SCALAR_TYPE): its class must be the type's, scalarBits then bounds the magnitude, and a
+// bitmap's term count is `count`, else the index list's length, the handle's n, or 8 per byte.
+napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv);
 napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  {
+    napi_valuetype vt = napi_undefined;
+    if (argc > 5 && napi_typeof(env, argv[5], &vt) == napi_ok && vt != napi_undefined && vt != napi_null)
+      return ComputeMsmPreparedTyped(env, argc, argv);
+  }
   const uint32_t* sc;
   size_t slen;
   bool sshared = false;
@@ -612,6 +665,71 @@ napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
   } else {  // detachable memory: the worker reads a copy
     j->scalars.resize(j->n * sw);
     copy_words(j->scalars.data(), sc, j->n * sw);
+  }
+  return start_job(env, j);
+}
+
+napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv) {
+  const msm_bases* h = get_handle(env, argv[0]);
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  const bool has_first = given(2), has_idx = given(3), has_bits = given(4), has_count = given(6);
+  const NativeType* ty = native_type(env, argv[5]);
+  double first = 0, bits = 0, count = 0;
+  const void* sc = nullptr;
+  const uint32_t* ix = nullptr;
+  size_t slen = 0, ilen = 0;
+  bool sshared = false;
+  if (!h || !ty || !get_typed_array(env, argv[1], ty->cls, &sc, &slen, &sshared) ||
+      (has_first && (napi_get_value_double(env, argv[2], &first) != napi_ok || !(first >= 0) ||
+                     first > 9007199254740992.0 || first != (double)(uint64_t)first)) ||
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen)) ||
+      (has_bits && (napi_get_value_double(env, argv[4], &bits) != napi_ok || bits != (double)(uint32_t)bits)) ||
+      (has_count && (napi_get_value_double(env, argv[6], &count) != napi_ok || !(count >= 0) ||
+                     count > 1073741824.0 || count != (double)(uint64_t)count))) {
+    napi_throw_type_error(env, nullptr,
+                          "computeMsmPrepared(id, scalars, first?, indices?, scalarBits?, scalarType, count?): scalars "
+                          "must be the typed array of scalarType (Uint8Array for bit and u8, Int8Array .. "
+                          "BigInt64Array / BigUint64Array for the rest)");
+    return nullptr;
+  }
+  if (has_bits && (bits < 1 || bits > ty->bits)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  msm_bases_info_t inf;
+  int rc = msm_bases_info(h, &inf);
+  if (rc != MSM_OK) return throw_rc(env, rc);  // released, or never a handle
+  const bool subset = has_first || has_idx;
+  const size_t held = ty->bits == 1 ? slen * 8 : slen;  // scalars the array can hold
+  const size_t m = has_count ? (size_t)count : has_idx ? ilen : subset ? held : (size_t)inf.n;
+  if (m > held || (!subset && m < inf.n)) {
+    napi_throw_range_error(env, nullptr, "fewer scalars than the call has terms");
+    return nullptr;
+  }
+  if (has_idx && ilen != m) {
+    napi_throw_range_error(env, nullptr, "one index per scalar");
+    return nullptr;
+  }
+  Job* j = new Job();
+  j->bases = h;
+  j->n = m;
+  j->scalar_bits = has_bits ? (uint32_t)bits : 0;
+  j->scalar_type = ty->type;
+  j->subset = subset;
+  j->indexed = has_idx;
+  j->first = (uint64_t)first;
+  if (has_idx) j->indices.assign(ix, ix + ilen);
+  if (sshared) {
+    j->p_scalars = static_cast<const uint32_t*>(sc);
+    if (napi_create_reference(env, argv[1], 1, &j->ref_scalars) != napi_ok) {
+      delete j;
+      napi_throw_error(env, nullptr, "cannot reference the input array");
+      return nullptr;
+    }
+  } else {  // detachable memory: the worker reads a copy (the vector's storage is aligned for any element)
+    const size_t bytes = (m * ty->bits + 7) / 8;
+    j->scalars.resize((bytes + 3) / 4 + 1);
+    memcpy(j->scalars.data(), sc, bytes);
   }
   return start_job(env, j);
 }

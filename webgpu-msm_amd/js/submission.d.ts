@@ -26,10 +26,19 @@ export declare function prepare_bases(
 // `scalarBits` = b (1..256), alone or beside either: narrow scalars -- a flat Uint32Array holds
 // ceil(b / 32) big-endian words per scalar, bigints are packed to that many words (one at or above
 // 2^b rejects) -- and the MSM runs the windows of a b-bit scalar only.
-export type BasesSubset = { first?: number; indices?: Uint32Array; scalarBits?: number };
+// `scalarType`: native integer scalars -- `scalars` is the typed array of that type as it is, negative
+// values included (Int8Array for "i8", Uint8Array for "u8" and for a "bit" bitmap, .. BigInt64Array for
+// "i64", BigUint64Array for "u64"; another class throws TypeError); scalarBits then bounds the
+// magnitude (|v| < 2^b, b up to the element's width) and `m` counts a bitmap's terms.
+export type ScalarType = "bit" | "u8" | "i8" | "u16" | "i16" | "u32" | "i32" | "u64" | "i64";
+export type NativeScalars =
+  | Uint8Array | Int8Array | Uint16Array | Int16Array | Uint32Array | Int32Array | BigUint64Array | BigInt64Array;
+export type BasesSubset = {
+  first?: number; indices?: Uint32Array; scalarBits?: number; scalarType?: ScalarType; m?: number;
+};
 export declare const compute_msm_prepared: (
   handle: BasesHandle,
-  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  scalars: bigint[] | Uint32Array[] | Uint32Array | NativeScalars,
   subset?: BasesSubset
 ) => Promise<{ x: bigint; y: bigint }>;
 export declare function release_bases(handle: BasesHandle): number;

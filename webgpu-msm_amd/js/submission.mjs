@@ -224,14 +224,35 @@ export function prepare_bases(baseAffinePoints, options) {
 // MSM_FLAG_SCALAR_BITS): a flat Uint32Array then holds ceil(b / 32) big-endian words per scalar,
 // bigints are packed to that many words (one at or above 2^b rejects), and the MSM runs the windows
 // of a b-bit scalar only -- 5 instead of 17 for 64-bit limbs.
+// { scalarType } (beside any of them) declares native integer scalars (msm_opts_typed,
+// MSM_FLAG_SCALAR_TYPE): `scalars` is then the typed array of that type as it is, negative values
+// included -- "i8" Int8Array, "u8" Uint8Array, "i16" / "u16", "i32" / "u32", "i64" BigInt64Array,
+// "u64" BigUint64Array, and "bit" a Uint8Array bitmap (scalar i is bit i & 7 of byte i >> 3) whose term
+// count is { m }, else indices.length, the handle's n, or 8 per byte.  Another class throws TypeError.
+// scalarBits = b then bounds the magnitude, |v| < 2^b with b up to the element's width.
+const NATIVE_CLASS = {
+  bit: Uint8Array, u8: Uint8Array, i8: Int8Array, u16: Uint16Array, i16: Int16Array, u32: Uint32Array, i32: Int32Array,
+  u64: BigUint64Array, i64: BigInt64Array,
+};
 export const compute_msm_prepared = async (handle, scalars, subset) => {
   if (!handle || typeof handle.id !== "number") throw new TypeError("compute_msm_prepared(handle, scalars): not a handle");
   if (subset !== undefined && subset !== null) {
-    const { first, indices, scalarBits } = subset;
+    const { first, indices, scalarBits, scalarType, m } = subset;
     if (scalarBits !== undefined && !(Number.isInteger(scalarBits) && scalarBits >= 1 && scalarBits <= 256))
       throw new RangeError("subset.scalarBits: an integer in 1..256");
     if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("subset.indices: a Uint32Array");
     if (first !== undefined && !(Number.isSafeInteger(first) && first >= 0)) throw new RangeError("subset.first: a non-negative integer");
+    if (scalarType !== undefined) {
+      const cls = NATIVE_CLASS[scalarType];
+      if (!cls) throw new TypeError("subset.scalarType: one of " + Object.keys(NATIVE_CLASS).join(", "));
+      if (!(scalars instanceof cls)) throw new TypeError(`subset.scalarType ${scalarType}: scalars must be a ${cls.name}`);
+      if (m !== undefined && !(Number.isSafeInteger(m) && m >= 0)) throw new RangeError("subset.m: a non-negative integer");
+      // (an options object is a subset call, as above: the prefix of as many bases as scalars)
+      const result = await addon.computeMsmPrepared(handle.id, scalars, first === undefined ? 0 : first, indices,
+                                                    scalarBits, scalarType, m);
+      const [x, y] = u32ArrayToBigInts(result);
+      return { x, y };
+    }
     // an empty options object is still a subset call: the prefix of as many bases as scalars
     const result = await addon.computeMsmPrepared(handle.id, scalarWords(scalars, scalarBits),
                                                   first === undefined ? 0 : first, indices, scalarBits);

@@ -28,6 +28,7 @@ __all__ = [
     "MSM_FLAG_DEVICES", "MSM_FLAG_WINDOWS", "MSM_FLAG_HALF_WINDOWS", "MSM_FLAG_SCALAR_BITS", "MSM_MAX_DEVICES",
     "window_count",
     "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P", "Bases", "BasesInfo",
+    "MsmOptsTyped", "MSM_FLAG_SCALAR_TYPE", "SCALAR_TYPES", "scalars_to_native",
 ]
 
 P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
@@ -52,6 +53,12 @@ class MsmOpts(ctypes.Structure):
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("devices", ctypes.POINTER(ctypes.c_int32)), ("n_devices", ctypes.c_uint32),
                 ("scalar_bits", ctypes.c_uint32), ("window_lo", ctypes.c_uint32), ("window_hi", ctypes.c_uint32)]
+
+
+class MsmOptsTyped(MsmOpts):
+    """include/msm.h msm_opts_typed: a msm_opts followed by scalar_type (MSM_SCALAR_*), read by libmsm
+    only when flags has MSM_FLAG_SCALAR_TYPE -- the shorter MsmOpts keeps its 40 bytes."""
+    _fields_ = [("scalar_type", ctypes.c_uint32)]
 
 
 class MsmProfile(ctypes.Structure):
@@ -80,7 +87,15 @@ MSM_FLAG_DEVICES = 2  # msm_opts carries a device list (include/msm.h)
 MSM_FLAG_WINDOWS = 4  # msm_opts carries a window range
 MSM_FLAG_HALF_WINDOWS = 8  # with MSM_FLAG_WINDOWS: the range counts half windows
 MSM_FLAG_SCALAR_BITS = 16  # msm_opts carries the scalars' width (narrow scalars, Bases.compute* only)
+MSM_FLAG_SCALAR_TYPE = 32  # the options are a MsmOptsTyped: native integer scalars (Bases.compute* only)
 MSM_MAX_DEVICES = 16
+# include/msm.h MSM_SCALAR_*: name -> (value, numpy dtype of the array, element bits e)
+SCALAR_TYPES = {
+    "bit": (1, np.dtype(np.uint8), 1),  # np.packbits(..., bitorder="little")
+    "u8": (2, np.dtype(np.uint8), 8), "u16": (3, np.dtype(np.uint16), 16), "u32": (4, np.dtype(np.uint32), 32),
+    "u64": (5, np.dtype(np.uint64), 64), "i8": (6, np.dtype(np.int8), 8), "i16": (7, np.dtype(np.int16), 16),
+    "i32": (8, np.dtype(np.int32), 32), "i64": (9, np.dtype(np.int64), 64),
+}
 MSM_STREAM_NULL = 1  # hip_stream value: order after the null (legacy default) stream
 
 
@@ -159,6 +174,7 @@ def load() -> ctypes.CDLL:
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_narrow_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_native_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_dense_plan": ([sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, u32p],
                                 ctypes.c_int),
         "msm_test_dense_segments": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
@@ -228,14 +244,20 @@ def _out(n: int) -> Tuple[np.ndarray, ctypes.POINTER(ctypes.c_uint32)]:
 
 def _opts(window_size: Optional[int], run_length: Optional[int] = None, device: int = -1, flags: int = 0,
           devices: Optional[Sequence[int]] = None, windows: Optional[Tuple[int, int]] = None,
-          scalar_bits: Optional[int] = None):
+          scalar_bits: Optional[int] = None, scalar_type=None):
     """A msm_opts by reference.  `devices` (a list of HIP ordinals) runs the call on several
     devices (MSM_FLAG_DEVICES); the array is kept alive by the returned object.  `windows` =
     (lo, hi) restricts the MSM to those signed-digit windows (MSM_FLAG_WINDOWS; needs an explicit
     window_size); (lo, hi, 2) counts the range in half windows (MSM_FLAG_HALF_WINDOWS: half window
     2w is window w's lower-half buckets, 2w + 1 its upper half).  `scalar_bits` = b declares narrow
-    scalars of ceil(b / 32) words (MSM_FLAG_SCALAR_BITS; the Bases.compute* calls only)."""
-    o = MsmOpts(int(window_size or 0), int(run_length or 0), int(device), int(flags))
+    scalars of ceil(b / 32) words (MSM_FLAG_SCALAR_BITS; the Bases.compute* calls only).
+    `scalar_type` (a SCALAR_TYPES name, or a raw MSM_SCALAR_* value) declares native integer scalars
+    (MSM_FLAG_SCALAR_TYPE; the same calls only): the options are then a MsmOptsTyped."""
+    if scalar_type is None:
+        o = MsmOpts(int(window_size or 0), int(run_length or 0), int(device), int(flags))
+    else:
+        o = MsmOptsTyped(int(window_size or 0), int(run_length or 0), int(device), int(flags) | MSM_FLAG_SCALAR_TYPE)
+        o.scalar_type = SCALAR_TYPES[scalar_type][0] if isinstance(scalar_type, str) else int(scalar_type)
     if scalar_bits is not None:
         if not 0 <= int(scalar_bits) < 1 << 32:
             raise ValueError("scalar_bits out of range")
@@ -330,6 +352,76 @@ def scalars_to_wire(scalars, scalar_bits: Optional[int] = None) -> np.ndarray:
             buf = b"".join(int(s).to_bytes(4 * words, "big") for s in sc)
         return np.frombuffer(buf, dtype=">u4").astype(np.uint32).reshape(-1, words)
     return np.stack([np.asarray(s, dtype=np.uint32).reshape(words) for s in sc])
+
+
+def scalars_to_native(values, scalar_type: str) -> np.ndarray:
+    """Python ints -> the array a Bases.compute*(scalar_type=...) call takes: the type's numpy dtype, or
+    for "bit" the little-order bitmap np.packbits(bits, bitorder="little").  A value the type cannot
+    hold raises ValueError."""
+    if scalar_type not in SCALAR_TYPES:
+        raise ValueError(f"unknown scalar type {scalar_type!r}")
+    _, dt, e = SCALAR_TYPES[scalar_type]
+    vals = [int(v) for v in values]
+    lo, hi = (-(1 << (e - 1)), 1 << (e - 1)) if scalar_type[0] == "i" else (0, 1 << e)
+    if any(not lo <= v < hi for v in vals):
+        raise ValueError(f"a scalar does not fit {scalar_type}")
+    if scalar_type == "bit":
+        return np.packbits(np.array(vals, dtype=np.uint8), bitorder="little")
+    return np.array(vals, dtype=dt).reshape(-1)
+
+
+_TORCH_NATIVE = {"torch.bool": "bool", "torch.uint8": "u8", "torch.int8": "i8", "torch.int16": "i16",
+                 "torch.int32": "i32", "torch.int64": "i64", "torch.uint16": "u16", "torch.uint32": "u32",
+                 "torch.uint64": "u64"}
+
+
+def _native_type(scalars, scalar_type, scalar_bits):
+    """Resolve `scalar_type` for one array (or the first of a list): "native" becomes the name of the
+    numpy or torch dtype -- bool is "u8" with scalar_bits = 1 unless a width is given.  Returns
+    (name or None, scalar_bits)."""
+    if scalar_type is None:
+        return None, scalar_bits
+    if scalar_type != "native":
+        if scalar_type not in SCALAR_TYPES:
+            raise ValueError(f"unknown scalar type {scalar_type!r}")
+        return scalar_type, scalar_bits
+    dt = getattr(scalars, "dtype", None)
+    if isinstance(dt, np.dtype):
+        name = "bool" if dt == np.bool_ else next((k for k, (_, d, _) in SCALAR_TYPES.items()
+                                                    if k != "bit" and d == dt), None)
+    else:
+        name = _TORCH_NATIVE.get(str(dt))
+    if name is None:
+        raise TypeError(f"no native scalar type for dtype {dt!r}")
+    if name == "bool":
+        return "u8", 1 if scalar_bits is None else scalar_bits
+    return name, scalar_bits
+
+
+def _native_host(scalars, name: str) -> np.ndarray:
+    """A host vector of a native type as a flat contiguous numpy array of the type's dtype: typed
+    arrays (and CPU torch tensors) pass through uncopied when contiguous; ints are packed."""
+    dt = SCALAR_TYPES[name][1]
+    if hasattr(scalars, "numpy") and not isinstance(scalars, np.ndarray):
+        scalars = scalars.numpy()  # a CPU tensor: shares its memory
+    if isinstance(scalars, np.ndarray):
+        if scalars.dtype == np.bool_ and dt == np.uint8:
+            scalars = scalars.view(np.uint8)
+        if scalars.dtype != dt:
+            raise TypeError(f"scalar_type {name!r} takes {dt} arrays, not {scalars.dtype}")
+        return np.ascontiguousarray(scalars).reshape(-1)
+    return scalars_to_native(scalars, name)
+
+
+def _native_len(arr: np.ndarray, name: str, m: Optional[int]) -> int:
+    """Scalars a host vector holds: its elements, or for a bitmap `m` (at most 8 per byte)."""
+    if name != "bit":
+        return arr.shape[0]
+    if m is None:
+        raise ValueError("a bit vector's length is not its byte count: pass m")
+    if (int(m) + 7) // 8 > arr.shape[0]:
+        raise ValueError("fewer bits than m")
+    return int(m)
 
 
 def _xy(o: np.ndarray) -> Tuple[int, int]:
@@ -519,6 +611,12 @@ def _host_list(arrs, words: int):
     return keep, ptrs
 
 
+def _native_list(arrs, name: str):
+    keep = [_native_host(a, name) for a in arrs]
+    ptrs = (ctypes.c_void_p * max(len(keep), 1))(*[a.ctypes.data for a in keep])
+    return keep, ptrs
+
+
 class Bases:
     """A base vector prepared once and kept on one device (include/msm.h msm_bases_*): every
     compute call then brings scalars only.  `levels` > 1 also keeps the shifted copies
@@ -560,50 +658,73 @@ class Bases:
     # Every compute call takes `scalar_bits` = b (include/msm.h MSM_FLAG_SCALAR_BITS): the scalars are
     # then narrow -- [n, ceil(b / 32)] words each, big-endian words, below 2^b (scalars_to_wire(...,
     # scalar_bits=b) packs ints) -- and the MSM runs the windows of a b-bit scalar only.
+    # And `scalar_type` (include/msm.h MSM_FLAG_SCALAR_TYPE): None (the word formats above), a
+    # SCALAR_TYPES name -- the vector is then a flat array of that integer type, negative values
+    # included, or for "bit" a little-order bitmap -- or "native", the type of the array's own numpy /
+    # torch dtype (bool: "u8" with scalar_bits = 1).  scalar_bits then bounds the magnitude, |v| < 2^b.
 
     def compute(self, scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                scalar_bits: Optional[int] = None) -> Tuple[int, int]:
+                scalar_bits: Optional[int] = None, scalar_type=None) -> Tuple[int, int]:
         """One MSM of host scalars ([n, 8] wire words, or anything scalars_to_wire takes)."""
         n = self.info["n"]
-        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
-        if sc.shape[0] < n:
+        ty, scalar_bits = _native_type(scalars, scalar_type, scalar_bits)
+        if ty:
+            sc = _native_host(scalars, ty)
+            short = _native_len(sc, ty, n) < n
+        else:
+            sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
+            short = sc.shape[0] < n
+        if short:
             raise ValueError("fewer scalars than the handle has points")
         o, op = _out(16)
-        _check(load().msm_bases_compute(self._h, _ptr(sc), _opts(window_size, run_length, scalar_bits=scalar_bits), op),
+        _check(load().msm_bases_compute(self._h, _ptr(sc),
+                                        _opts(window_size, run_length, scalar_bits=scalar_bits, scalar_type=ty), op),
                "msm_bases_compute")
         return _xy(o)
 
     def compute_device(self, d_scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                       stream: int = 0, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
+                       stream: int = 0, scalar_bits: Optional[int] = None, scalar_type=None) -> Tuple[int, int]:
         """One MSM of device-resident scalars (a torch tensor or a raw device pointer, n x 8 words)."""
+        ty, scalar_bits = _native_type(d_scalars, scalar_type, scalar_bits)
         o, op = _out(16)
         _check(load().msm_bases_compute_device(self._h or None, _dev_ptr(d_scalars),
-                                               _opts(window_size, run_length, scalar_bits=scalar_bits),
+                                               _opts(window_size, run_length, scalar_bits=scalar_bits,
+                                                     scalar_type=ty),
                                                _stream(stream, d_scalars), op), "msm_bases_compute_device")
         return _xy(o)
 
     def compute_many(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                     flags: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
+                     flags: int = 0, scalar_bits: Optional[int] = None, scalar_type=None) -> np.ndarray:
         """len(scalars_list) pipelined MSMs of host scalar vectors.  [count][16] BE words."""
         n = self.info["n"]
-        ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
-        if any(b.shape[0] < n for b in ks):
+        ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
+        if ty:
+            ks, ss = _native_list(scalars_list, ty)
+            short = any(_native_len(b, ty, n) < n for b in ks)
+        else:
+            ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
+            short = any(b.shape[0] < n for b in ks)
+        if short:
             raise ValueError("fewer scalars than the handle has points")
         count = len(ks)
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_many(self._h, ctypes.cast(ss, ctypes.c_void_p), count,
-                                             _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits), op),
+                                             _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits,
+                                                   scalar_type=ty), op),
                "msm_bases_compute_many")
         return o[:16 * count].reshape(count, 16)
 
     def compute_many_device(self, scalars_list, window_size: Optional[int] = None, run_length: Optional[int] = None,
-                            flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
+                            flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None,
+                            scalar_type=None) -> np.ndarray:
         """The same with device-resident scalar vectors."""
         count = len(scalars_list)
+        ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
         ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_many_device(self._h or None, ctypes.cast(ss, ctypes.c_void_p), count,
-                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits),
+                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits,
+                                                          scalar_type=ty),
                                                     _stream(stream, _first(scalars_list)), op),
                "msm_bases_compute_many_device")
         return o[:16 * count].reshape(count, 16)
@@ -652,59 +773,83 @@ class Bases:
         return [_dev_ptr(t) for t in vecs]
 
     def compute_subset(self, scalars, first: int = 0, indices=None, window_size: Optional[int] = None,
-                       run_length: Optional[int] = None, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
+                       run_length: Optional[int] = None, scalar_bits: Optional[int] = None, scalar_type=None,
+                       m: Optional[int] = None) -> Tuple[int, int]:
         """One MSM of the m = len(scalars) host scalars over bases [first, first + m), or over
-        bases indices[0..m) (a uint32 array)."""
-        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
-        m = sc.shape[0]
+        bases indices[0..m) (a uint32 array).  A "bit" vector's m is given (or is len(indices))."""
+        ty, scalar_bits = _native_type(scalars, scalar_type, scalar_bits)
+        if ty:
+            sc = _native_host(scalars, ty)
+            m = _native_len(sc, ty, len(indices) if m is None and indices is not None else m)
+        else:
+            sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
+            m = sc.shape[0]
         keep, ptrs = self._host_indices(indices, m, 1)
         sub = self._subset(first, m, ptrs)
         o, op = _out(16)
         _check(load().msm_bases_compute_subset(self._h or None, ctypes.byref(sub), _ptr(sc),
-                                               _opts(window_size, run_length, scalar_bits=scalar_bits), op),
+                                               _opts(window_size, run_length, scalar_bits=scalar_bits,
+                                                     scalar_type=ty), op),
                "msm_bases_compute_subset")
         return _xy(o)
 
     def compute_subset_device(self, d_scalars, first: int = 0, indices=None, m: Optional[int] = None,
                               window_size: Optional[int] = None, run_length: Optional[int] = None,
-                              stream: int = 0, scalar_bits: Optional[int] = None) -> Tuple[int, int]:
+                              stream: int = 0, scalar_bits: Optional[int] = None,
+                              scalar_type=None) -> Tuple[int, int]:
         """The same with device-resident scalars (a torch tensor [m, 8], or a raw device pointer with
         `m`) and, in indexed form, a device-resident int32/uint32 index tensor (or pointer)."""
+        ty, scalar_bits = _native_type(d_scalars, scalar_type, scalar_bits)
+        if ty == "bit" and m is None:
+            raise ValueError("a bit vector's length is not its byte count: pass m")
         m = len(d_scalars) if m is None else int(m)
         sub = self._subset(first, m, self._device_indices(indices, 1))
         o, op = _out(16)
         _check(load().msm_bases_compute_subset_device(self._h or None, ctypes.byref(sub), _dev_ptr(d_scalars),
-                                                      _opts(window_size, run_length, scalar_bits=scalar_bits),
+                                                      _opts(window_size, run_length, scalar_bits=scalar_bits,
+                                                            scalar_type=ty),
                                                       _stream(stream, d_scalars, indices), op),
                "msm_bases_compute_subset_device")
         return _xy(o)
 
     def compute_subset_many(self, scalars_list, first: int = 0, indices=None, window_size: Optional[int] = None,
                             run_length: Optional[int] = None, flags: int = 0,
-                            scalar_bits: Optional[int] = None) -> np.ndarray:
+                            scalar_bits: Optional[int] = None, scalar_type=None,
+                            m: Optional[int] = None) -> np.ndarray:
         """len(scalars_list) pipelined MSMs of host scalar vectors of one length m, over one range
         or over each MSM's own index vector (`indices`: a list of arrays, or one array for all).
-        [count][16] BE words."""
-        ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
+        [count][16] BE words.  "bit" vectors need `m`."""
+        ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
+        if ty:
+            ks, ss = _native_list(scalars_list, ty)
+            lens = [_native_len(b, ty, m) for b in ks]
+        else:
+            ks, ss = _host_list(scalars_list, _scalar_words(scalar_bits))
+            lens = [b.shape[0] for b in ks]
         count = len(ks)
-        m = ks[0].shape[0] if count else 0
-        if any(b.shape[0] != m for b in ks):
+        m = lens[0] if count else 0
+        if any(k != m for k in lens):
             raise ValueError("the scalar vectors of one call share their length")
         keep, ptrs = self._host_indices(indices, m, count)
         sub = self._subset(first, m, ptrs)
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_subset_many(self._h or None, ctypes.byref(sub), ctypes.cast(ss, ctypes.c_void_p),
                                                     count,
-                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits),
+                                                    _opts(window_size, run_length, -1, flags, scalar_bits=scalar_bits,
+                                                          scalar_type=ty),
                                                     op),
                "msm_bases_compute_subset_many")
         return o[:16 * count].reshape(count, 16)
 
     def compute_subset_many_device(self, scalars_list, first: int = 0, indices=None, m: Optional[int] = None,
                                    window_size: Optional[int] = None, run_length: Optional[int] = None,
-                                   flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None) -> np.ndarray:
+                                   flags: int = 0, stream: int = 0, scalar_bits: Optional[int] = None,
+                                   scalar_type=None) -> np.ndarray:
         """The same with device-resident scalar (and index) vectors."""
         count = len(scalars_list)
+        ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
+        if ty == "bit" and m is None:
+            raise ValueError("a bit vector's length is not its byte count: pass m")
         if m is None:
             m = len(scalars_list[0]) if count else 0
         ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
@@ -714,7 +859,7 @@ class Bases:
         _check(load().msm_bases_compute_subset_many_device(self._h or None, ctypes.byref(sub),
                                                            ctypes.cast(ss, ctypes.c_void_p), count,
                                                            _opts(window_size, run_length, -1, flags,
-                                                                 scalar_bits=scalar_bits),
+                                                                 scalar_bits=scalar_bits, scalar_type=ty),
                                                            _stream(stream, *tensors), op),
                "msm_bases_compute_subset_many_device")
         return o[:16 * count].reshape(count, 16)
@@ -979,6 +1124,17 @@ def _test_narrow_plan(n: int, scalar_bits: int, window_size: int = 0) -> dict:
     _check(load().msm_test_narrow_plan(n, int(scalar_bits), int(window_size),
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_narrow_plan")
     return dict(zip(("c", "windows", "q", "nhi", "words", "packed"), (int(v) for v in out)))
+
+
+def _test_native_plan(n: int, scalar_type, scalar_bits: int, window_size: int = 0) -> dict:
+    """The plan of a native-type launch (msm_test_native_plan; no GPU needed): _test_narrow_plan's
+    fields for scalar_bits, then the bytes of one vector and of its region in a launch's upload buffer."""
+    out = np.zeros(8, dtype=np.uint32)
+    ty = SCALAR_TYPES[scalar_type][0] if isinstance(scalar_type, str) else int(scalar_type)
+    _check(load().msm_test_native_plan(n, ty, int(scalar_bits), int(window_size),
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_native_plan")
+    return dict(zip(("c", "windows", "q", "nhi", "words", "packed", "vector_bytes", "region_bytes"),
+                    (int(v) for v in out)))
 
 
 def _test_dense_plan(n: int, nm: int = 1, pipelined: bool = False, scalar_bits: int = 8, window_size: int = 0) -> dict:
