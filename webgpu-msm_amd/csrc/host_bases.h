@@ -13,6 +13,10 @@ struct Bases {
   BasesGeo geo{};            // levels > 1
   Buf rec;                   // levels * n records, level j at [j n, (j + 1) n)
   bool alive = false;
+  template <typename F>
+  void each_buf(F&& f) {  // as Workspace::each_buf
+    f("bases_rec", rec);
+  }
 };
 std::map<uintptr_t, std::shared_ptr<Bases>> g_bases;  // under g_mu
 uintptr_t g_bases_next = 1;
@@ -29,7 +33,7 @@ void release_bases_on(int device) {
   for (auto& kv : g_bases)
     if (kv.second->device == device) {
       kv.second->alive = false;
-      kv.second->rec.release();
+      kv.second->each_buf([](const char*, Buf& b) { b.release(); });
     }
 }
 
@@ -78,6 +82,10 @@ int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* op
     }
     auto done = [&](int code) {  // every exit past the allocations: a failure leaves nothing allocated
       drain_streams(c, 1, code);
+      if (errb.base) {  // guarded (host_guard.h): the word does not outlive the call, so it is looked at here
+        std::lock_guard<std::mutex> gl(g_guard_mu);
+        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+      }
       errb.release();
       if (code != MSM_OK) b->rec.release();
       return code;

@@ -29,15 +29,26 @@ enum Phase {
 // replayed only while the generation it was captured under is current.
 std::atomic<uint64_t> g_alloc_gen{0};
 
+// Guarded workspaces, a test mode (msm_test_guard, host_guard.h; off in production, no environment
+// knob): every allocation made while the switch is on is front guard | payload | back guard, with
+// `cap` the requested bytes exactly -- no 256-B floor, so nothing hides in slack --, the guards filled
+// with GUARD_FILL and the payload with zero bytes (a defined value: read as an index it stays in
+// range).  The back guard is one whole partition chunk of 32-bit entries, the largest unit any one
+// lane group writes; the front guard keeps `p` 256-B aligned.  msm_test_guard_check reads the guards
+// back.  The switch changes only while nothing is allocated, so one process never mixes the layouts.
+std::atomic<bool> g_guard{false};
+constexpr size_t GUARD_FRONT = 4096, GUARD_BACK = 65536;
+constexpr int GUARD_FILL = 0xA5;
+
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
+  void* base = nullptr;  // a guarded allocation's own start (p = base + GUARD_FRONT), null otherwise
   int ensure(size_t bytes) {
     if (bytes <= cap) return MSM_OK;
     g_alloc_gen.fetch_add(1);
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
+    if (g_guard.load(std::memory_order_relaxed)) return ensure_guarded(bytes);
     size_t want = std::max<size_t>(bytes, 256);
     if (hipMalloc(&p, want) != hipSuccess) {
       p = nullptr;
@@ -46,13 +57,32 @@ struct Buf {
     cap = want;
     return MSM_OK;
   }
+  int ensure_guarded(size_t bytes) {
+    if (hipMalloc(&base, GUARD_FRONT + bytes + GUARD_BACK) != hipSuccess) {
+      base = nullptr;
+      return MSM_ERR_OOM;
+    }
+    char* b = static_cast<char*>(base);
+    // (the fills are complete before any of the library's streams, which do not wait for the null
+    // stream, can touch the buffer)
+    if (hipMemset(b, GUARD_FILL, GUARD_FRONT) != hipSuccess || hipMemset(b + GUARD_FRONT, 0, bytes) != hipSuccess ||
+        hipMemset(b + GUARD_FRONT + bytes, GUARD_FILL, GUARD_BACK) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+      hipFree(base);
+      base = nullptr;
+      return MSM_ERR_HIP;
+    }
+    p = b + GUARD_FRONT;
+    cap = bytes;
+    return MSM_OK;
+  }
   template <typename T>
   T* as() const {
     return reinterpret_cast<T*>(p);
   }
   void release() {
-    if (p) hipFree(p);
-    p = nullptr;
+    if (p) hipFree(base ? base : p);
+    p = base = nullptr;
     cap = 0;
   }
 };
@@ -60,12 +90,14 @@ struct Buf {
 struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
-  int ensure(size_t bytes) {
+  void* base = nullptr;  // as Buf::base
+  // `guardable`: a buffer kernels write into (a slot's h_out) takes the guarded layout in the test
+  // mode; the pinned upload ring, which only the host writes, never does.
+  int ensure(size_t bytes, bool guardable = false) {
     if (bytes <= cap) return MSM_OK;
     g_alloc_gen.fetch_add(1);
-    if (p) hipHostFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
+    if (guardable && g_guard.load(std::memory_order_relaxed)) return ensure_guarded(bytes);
     // pinned, host-cacheable memory; k_red2_terms (or k_bucket_reduce_2) writes its results
     // straight into it, visible to the host once the launch's event completes (a coherent /
     // uncached mapping would make the host Horner's reads ~4x slower)
@@ -76,9 +108,22 @@ struct HostBuf {
     cap = bytes;
     return MSM_OK;
   }
+  int ensure_guarded(size_t bytes) {
+    if (hipHostMalloc(&base, GUARD_FRONT + bytes + GUARD_BACK, hipHostMallocDefault) != hipSuccess) {
+      base = nullptr;
+      return MSM_ERR_OOM;
+    }
+    char* b = static_cast<char*>(base);
+    memset(b, GUARD_FILL, GUARD_FRONT);
+    memset(b + GUARD_FRONT, 0, bytes);
+    memset(b + GUARD_FRONT + bytes, GUARD_FILL, GUARD_BACK);
+    p = b + GUARD_FRONT;
+    cap = bytes;
+    return MSM_OK;
+  }
   void release() {
-    if (p) hipHostFree(p);
-    p = nullptr;
+    if (p) hipHostFree(base ? base : p);
+    p = base = nullptr;
     cap = 0;
   }
 };
@@ -131,12 +176,24 @@ struct Workspace {
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
+  // Every buffer with its name: release() and the guard check (host_guard.h) both go through this, so
+  // neither can miss one.
+  template <typename F>
+  void each_buf(F&& f) {
+#define WS_BUF(b) f(#b, b)
+    WS_BUF(pts), WS_BUF(err), WS_BUF(digits), WS_BUF(colsum), WS_BUF(bin_base), WS_BUF(bin_cur);
+    WS_BUF(part_entry), WS_BUF(part_fine), WS_BUF(sorted_entry), WS_BUF(bucket_start), WS_BUF(run_key), WS_BUF(buckets);
+    WS_BUF(lead_val), WS_BUF(lead_open), WS_BUF(cross_key), WS_BUF(lead_flag), WS_BUF(skew_list);
+    WS_BUF(g_head), WS_BUF(g_hkey), WS_BUF(g_tkey), WS_BUF(red_U), WS_BUF(red_T);
+    WS_BUF(wire_pts), WS_BUF(wire_sc), WS_BUF(red_G), WS_BUF(split_sc), WS_BUF(sub_idx);
+    WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials);
+#ifdef MSM_DUMMY_ALLOC
+    WS_BUF(dummy_tiles), WS_BUF(dummy_cursor);
+#endif
+#undef WS_BUF
+  }
   void release() {
-    Buf* bufs[] = {&pts, &err, &digits, &colsum, &bin_base, &bin_cur, &part_entry, &part_fine,
-                   &sorted_entry, &bucket_start, &run_key, &buckets, &lead_val, &lead_open, &cross_key,
-                   &lead_flag, &skew_list, &g_head, &g_hkey, &g_tkey, &red_U, &red_T, &wire_pts, &wire_sc, &red_G, &split_sc,
-                   &sub_idx, &seg_base, &unit_key, &partials};
-    for (Buf* b : bufs) b->release();
+    each_buf([](const char*, Buf& b) { b.release(); });
   }
 };
 
@@ -281,6 +338,13 @@ struct DevCtx {
       for (hipEvent_t* e : {&sl.ev_done, &sl.ev_in, &sl.ev_sc, &sl.ev_fork, &sl.ev_join}) f(e, false);
     }
   }
+  // The context's own device buffers with their names (the slots' are Workspace::each_buf's).
+  template <typename F>
+  void each_buf(F&& f) {
+    f("shared_pts", shared_pts);
+    f("host_sc", host_sc);
+    f("host_pts", host_pts);
+  }
   // No context without its streams and events (a null event would fail every call later): on an error
   // the caller destroys what was made.
   int create(int dev) {
@@ -320,9 +384,7 @@ struct DevCtx {
     hipSetDevice(device);
     hipStreamSynchronize(copy_stream);
     for (Slot& sl : slot) hipStreamSynchronize(sl.stream);
-    shared_pts.release();
-    host_sc.release();
-    host_pts.release();
+    each_buf([](const char*, Buf& b) { b.release(); });
     release_bases_on(device);
     for (Slot& sl : slot) {
       sl.ws.release();

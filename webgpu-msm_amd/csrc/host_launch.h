@@ -59,7 +59,7 @@ int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
   }
   const size_t hbytes = (size_t)d.W * pl.nterms * 32 * 4 + 64;
   if (hbytes > sl0.h_out.cap || !sl0.h_out_dev) {
-    if ((rc = sl0.h_out.ensure(hbytes)) != MSM_OK) return rc;
+    if ((rc = sl0.h_out.ensure(hbytes, true)) != MSM_OK) return rc;
     if (hipHostGetDevicePointer(&sl0.h_out_dev, sl0.h_out.p, 0) != hipSuccess) return MSM_ERR_HIP;
   }
   return MSM_OK;

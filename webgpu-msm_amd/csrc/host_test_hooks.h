@@ -50,6 +50,23 @@ void dispatch_limb_op(int op, std::integer_sequence<int, OPS...>, const uint32_t
   ((op == OPS ? launch_limb_op<OPS>(a, b, neg, out, n) : (void)0), ...);
 }
 
+// `fn(ctx)` on the context of `device`, or on every context there is for device < 0 (none is created),
+// each under its lock, with its device current and its streams drained.
+template <typename F>
+int guard_each_ctx(int device, F&& fn) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (DevCtx* c : g_ctx) {
+    if (!c || (device >= 0 && c->device != device)) continue;
+    std::lock_guard<std::mutex> lk2(c->mu);
+    DeviceGuard g(c->device);
+    bool ok = true;
+    c->each_stream([&](hipStream_t* s) { ok = ok && hipStreamSynchronize(*s) == hipSuccess; });
+    if (!ok) return MSM_ERR_HIP;
+    if (int rc = fn(c)) return rc;
+  }
+  return MSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -547,6 +564,136 @@ int msm_test_split_scalars(const uint32_t* scalars, size_t n, uint32_t k, uint32
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpy(out, dout.p, (size_t)k * n * 32, hipMemcpyDeviceToHost));
   return MSM_OK;
+}
+
+// ---- guarded workspaces (host_ctx.h g_guard, host_guard.h; tests/test_gpu_guard.py) ---------------
+// The name of buffer index `id` in the guard reports (null past the table's end).  No device needed.
+const char* msm_test_guard_name(uint32_t id) {
+  const auto& v = guard_names();
+  return id < v.size() ? v[id] : nullptr;
+}
+
+// Sets the guard switch and returns its previous value (0 / 1).  MSM_ERR_INVALID_ARG while a device
+// context or a handle holds an allocation made in the other mode (run msm_shutdown first): one process
+// never mixes the two layouts.
+int msm_test_guard(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const bool prev = g_guard.load();
+  if ((on != 0) == prev) return prev ? 1 : 0;
+  bool held = false;
+  auto seen = [&](const char*, Buf& b) { held = held || b.p; };
+  for (DevCtx* c : g_ctx) {
+    if (!c) continue;
+    std::lock_guard<std::mutex> lk2(c->mu);
+    c->each_buf(seen);
+    for (Slot& sl : c->slot) {
+      sl.ws.each_buf(seen);
+      held = held || sl.h_out.p;
+    }
+  }
+  for (auto& kv : g_bases) kv.second->each_buf(seen);
+  if (held) return MSM_ERR_INVALID_ARG;
+  g_guard.store(on != 0);
+  return prev ? 1 : 0;
+}
+
+// Frees every slot's workspace and result buffer and the context's own buffers, with the captured
+// graphs that point into them; handles stay.  The next call allocates every buffer at exactly its own
+// plan's size (guarded or not).
+int msm_test_guard_release(int device) {
+  return guard_each_ctx(device, [](DevCtx* c) -> int {
+    g_alloc_gen.fetch_add(1);
+    c->each_buf([](const char*, Buf& b) { b.release(); });
+    for (Slot& sl : c->slot) {
+      sl.ws.release();
+      for (Segment& sg : sl.seg) sg.drop();
+      sl.h_out.release();
+      sl.h_out_dev = nullptr;
+    }
+    return MSM_OK;
+  });
+}
+
+// Reads every guard band back, and the payload of the five buffers the kernels keep all-zero between
+// MSMs (err, lead_flag, skew_list[0], colsum, bin_cur): one GuardHit per touched band or broken
+// invariant, over the slots, the contexts' own buffers and the live handles' records, and what a
+// handle's preparation left behind.  What is reported is repaired (guards refilled, words cleared), so
+// the next check reports it no more.  Writes at most `cap` records; *count is the number found.
+int msm_test_guard_check(int device, GuardHit* report, size_t cap, size_t* count) {
+  if (!count || (!report && cap)) return MSM_ERR_INVALID_ARG;
+  std::vector<GuardHit> hits;
+  int rc = guard_each_ctx(device, [&](DevCtx* c) -> int {
+    const int dev = c->device;
+    int r = MSM_OK;
+    for (int si = 0; si < NSLOT; si++) {
+      Slot& sl = c->slot[si];
+      Workspace& w = sl.ws;
+      uint32_t id = 0;
+      w.each_buf([&](const char*, Buf& b) {
+        if (r == MSM_OK) r = guard_scan(b, id, dev, si, &hits);
+        id++;
+      });
+      guard_scan_host(sl.h_out, guard_id("h_out"), dev, si, &hits);
+      struct Zero {
+        const char* name;
+        Buf* b;
+        size_t bytes;
+      } zeros[] = {{"err", &w.err, w.err.cap},
+                   {"lead_flag", &w.lead_flag, w.lead_flag.cap},
+                   {"skew_list", &w.skew_list, 4},
+                   {"colsum", &w.colsum, w.colsum.cap},
+                   {"bin_cur", &w.bin_cur, w.bin_cur.cap}};
+      for (const Zero& z : zeros)
+        if (r == MSM_OK) r = guard_scan_zero(*z.b, z.bytes, guard_id(z.name), dev, si, &hits);
+    }
+    c->each_buf([&](const char* n, Buf& b) {
+      if (r == MSM_OK) r = guard_scan(b, guard_id(n), dev, -1, &hits);
+    });
+    for (auto& kv : g_bases)
+      if (kv.second->device == dev)
+        kv.second->each_buf([&](const char* n, Buf& b) {
+          if (r == MSM_OK) r = guard_scan(b, guard_id(n), dev, -1, &hits);
+        });
+    return r;
+  });
+  if (rc != MSM_OK) return rc;
+  {
+    std::lock_guard<std::mutex> gl(g_guard_mu);
+    for (auto it = g_guard_pending.begin(); it != g_guard_pending.end();)
+      if (device < 0 || it->device == device) {
+        hits.push_back(*it);
+        it = g_guard_pending.erase(it);
+      } else {
+        ++it;
+      }
+  }
+  *count = hits.size();
+  for (size_t i = 0; i < hits.size() && i < cap; i++) report[i] = hits[i];
+  return MSM_OK;
+}
+
+// The check's self-test: one byte written with hipMemset (no kernel runs) into buffer `buffer` (an
+// index of msm_test_guard_name's table) of slot `slot` -- where 0: the first byte of the back guard,
+// 1: its last byte, 2: the last byte of the front guard, 3: the second payload word.  Every place
+// lies inside the allocation.  MSM_ERR_INVALID_ARG for a buffer that is not allocated, for a guard of
+// one that is not guarded, and for a payload shorter than two words.
+int msm_test_guard_plant(int device, int slot, uint32_t buffer, int where) {
+  if (slot < 0 || slot >= NSLOT || where < 0 || where > 3) return MSM_ERR_INVALID_ARG;
+  bool found = false;
+  int rc = guard_each_ctx(device, [&](DevCtx* c) -> int {
+    int r = MSM_ERR_INVALID_ARG;
+    uint32_t id = 0;
+    c->slot[slot].ws.each_buf([&](const char*, Buf& b) {
+      if (id++ != buffer || found) return;
+      found = true;
+      if (!b.p || (where < 3 && !b.base) || (where == 3 && b.cap < 8)) return;
+      char* p = static_cast<char*>(b.p);
+      char* at = where == 0 ? p + b.cap : where == 1 ? p + b.cap + GUARD_BACK - 1 : where == 2 ? p - 1 : p + 4;
+      r = hipMemset(at, 0x5A, 1) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess ? MSM_OK : MSM_ERR_HIP;
+    });
+    return r;
+  });
+  return found ? rc : MSM_ERR_INVALID_ARG;
 }
 
 #ifdef MSM_PHASE_PROBE

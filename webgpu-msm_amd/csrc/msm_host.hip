@@ -46,6 +46,7 @@ using namespace msmh;
 namespace {
 #include "host_knobs.h"
 #include "host_ctx.h"
+#include "host_guard.h"
 #include "host_plan.h"
 #include "host_tail.h"
 #include "host_launch.h"

@@ -77,6 +77,13 @@ class BasesInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
 
 
+class GuardHit(ctypes.Structure):
+    """csrc/host_guard.h GuardHit: one finding of msm_test_guard_check."""
+    _fields_ = [("buffer", ctypes.c_uint32), ("device", ctypes.c_int32), ("slot", ctypes.c_int32),
+                ("side", ctypes.c_uint32), ("first", ctypes.c_int64), ("last", ctypes.c_int64),
+                ("count", ctypes.c_uint64)]
+
+
 class Subset(ctypes.Structure):
     """include/msm.h msm_subset_t."""
     _fields_ = [("first", ctypes.c_uint64), ("m", ctypes.c_uint64), ("indices", ctypes.c_void_p)]
@@ -197,6 +204,11 @@ def load() -> ctypes.CDLL:
         "msm_test_peer_state": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
         "msm_test_host_timing": ([ctypes.c_int, sz, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "msm_test_pools": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "msm_test_guard_name": ([ctypes.c_uint32], ctypes.c_char_p),
+        "msm_test_guard": ([ctypes.c_int], ctypes.c_int),
+        "msm_test_guard_release": ([ctypes.c_int], ctypes.c_int),
+        "msm_test_guard_check": ([ctypes.c_int, ctypes.POINTER(GuardHit), sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "msm_test_guard_plant": ([ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name.startswith(("msm_test_", "msm_bases_")) and not hasattr(L, name):
@@ -1204,3 +1216,61 @@ def _test_sharded(mode: int, points, scalars, n: int, devices: Sequence[int], wi
         pp, sp, st = _dev_ptr(points), _dev_ptr(scalars), _stream(stream, points, scalars)
     _check(L.msm_test_sharded(mode, pp, sp, n, _opts(window_size), arr, len(devices), st, op), "msm_test_sharded")
     return _xy(o)
+
+
+# ---- guarded workspaces (csrc/host_ctx.h g_guard, csrc/host_guard.h; tests/test_gpu_guard.py) ----
+_GUARD_SIDES = ("front", "back", "zero")
+
+
+def _test_guard_names() -> list:
+    """The buffer names of the guard reports, by index (msm_test_guard_name).  No GPU needed."""
+    L, names = load(), []
+    while True:
+        s = L.msm_test_guard_name(len(names))
+        if s is None:
+            return names
+        names.append(s.decode())
+
+
+def _test_guard(on: bool) -> bool:
+    """Switch the guarded-allocation mode (msm_test_guard); returns the previous state.  MsmError -1
+    while the library holds an allocation made in the other mode: run msm_shutdown first."""
+    rc = load().msm_test_guard(1 if on else 0)
+    _check(min(rc, 0), "msm_test_guard")
+    return bool(rc)
+
+
+def _test_guard_release(device: int = -1) -> None:
+    """Free the workspaces of the device's context (every context for -1), keeping handles: the next
+    call allocates each buffer at exactly its own plan's size (msm_test_guard_release)."""
+    _check(load().msm_test_guard_release(int(device)), "msm_test_guard_release")
+
+
+def _test_guard_check(device: int = -1) -> list:
+    """Touched guard bands and broken zero invariants (msm_test_guard_check), each a dict: buffer
+    name, device, slot (-1: not a slot's), side ("front" / "back" / "zero"), first and last offset in
+    bytes -- a front guard's from the payload's start (negative), a back guard's from its end, a zero
+    invariant's word from the payload's start -- and the count (bytes; words for "zero").  What is
+    reported is repaired, so the next check is clean."""
+    L, names = load(), _test_guard_names()
+    cap = 64
+    while True:
+        rep, cnt = (GuardHit * cap)(), ctypes.c_size_t(0)
+        _check(L.msm_test_guard_check(int(device), rep, cap, ctypes.byref(cnt)), "msm_test_guard_check")
+        if cnt.value > cap:  # (the first cap were repaired already: they are in `rep`, the rest come again)
+            raise RuntimeError(f"{cnt.value} guard findings, more than {cap}: {_guard_dicts(rep, cap, names)}")
+        return _guard_dicts(rep, cnt.value, names)
+
+
+def _guard_dicts(rep, k: int, names: list) -> list:
+    return [{"buffer": names[h.buffer] if h.buffer < len(names) else int(h.buffer), "device": int(h.device),
+             "slot": int(h.slot), "side": _GUARD_SIDES[h.side], "first": int(h.first), "last": int(h.last),
+             "count": int(h.count)} for h in rep[:k]]
+
+
+def _test_guard_plant(buffer: str, where: int, slot: int = 0, device: int = -1) -> None:
+    """Self-test of the check (msm_test_guard_plant): one byte written with hipMemset into `buffer` of
+    `slot` -- where 0: first byte of the back guard, 1: its last byte, 2: last byte of the front guard,
+    3: the second payload word."""
+    _check(load().msm_test_guard_plant(int(device), int(slot), _test_guard_names().index(buffer), int(where)),
+           "msm_test_guard_plant")
