@@ -15,8 +15,9 @@
  *                   (Aleo's msm over affine points) does, so an inconsistent t does not change it
  *   scalar        : 8 x uint32 big-endian = full 256-bit integer (not reduced mod r); the
  *                   msm_bases_compute* entries also take narrow scalars of ceil(b / 32) words
- *                   (MSM_FLAG_SCALAR_BITS below) and native integer arrays, signed ones included
- *                   (MSM_FLAG_SCALAR_TYPE below)
+ *                   (MSM_FLAG_SCALAR_BITS below), native integer arrays, signed ones included
+ *                   (MSM_FLAG_SCALAR_TYPE below), and little-endian 128- and 256-bit integers and
+ *                   Montgomery-form field elements (MSM_FLAG_SCALAR_FIELD below)
  *   result        : x | y affine = 16 x uint32; identity = (0, 1)
  */
 #ifndef MSM_MI355X_H
@@ -50,6 +51,7 @@ extern "C" {
 #define MSM_FLAG_HALF_WINDOWS 8u /* with MSM_FLAG_WINDOWS: window_lo / window_hi count half windows */
 #define MSM_FLAG_SCALAR_BITS 16u /* scalar_bits is set: narrow scalars (msm_bases_compute* only, below) */
 #define MSM_FLAG_SCALAR_TYPE 32u /* the options are a msm_opts_typed: native integer scalars (msm_bases_compute* only) */
+#define MSM_FLAG_SCALAR_FIELD 64u /* msm_opts_typed.scalar_field is set: wide native scalars (msm_bases_compute* only) */
 
 #define MSM_MAX_DEVICES 16
 
@@ -193,9 +195,56 @@ uint32_t msm_window_count(uint32_t window_bits);
 #define MSM_SCALAR_I16 7u
 #define MSM_SCALAR_I32 8u
 #define MSM_SCALAR_I64 9u
+/* Wide scalar types (MSM_FLAG_SCALAR_FIELD): a column of 128-bit integers or of 256-bit field elements,
+ * as an arkworks / snarkVM prover holds them, goes to the msm_bases_compute* entries as it is -- no
+ * into_bigint() per element, no limb reversal, no zero extension.  Every element is little-endian (the
+ * least significant byte first: u64 limbs of a little-endian host, least significant limb first).
+ *
+ *   MSM_FIELD_U128      16 B: the unsigned integer v
+ *   MSM_FIELD_I128      16 B, two's complement: v; a negative v contributes |v| (-P_i), and -2^127 has
+ *                       magnitude 2^127, as MSM_SCALAR_I64 treats -2^63
+ *   MSM_FIELD_U256      32 B (arkworks BigInt<4>): the full 256-bit integer v, not reduced, as the wire
+ *                       format's
+ *   MSM_FIELD_FR_MONT   32 B (the memory of an arkworks Fr of ark-ed-on-bls12-377): a < r, and the scalar
+ *                       is v = a 2^-256 mod r, with
+ *                       r = 0x04aad957a68b2955982d1347970dec005293a3afc43c8afeb95aee9ac33fd9ff (251 bits)
+ *
+ * The field is msm_opts_typed.scalar_field, in what was the struct's tail padding (offset 44; the
+ * struct stays 48 bytes and scalar_type stays at offset 40); the caller sets the flag and passes
+ * &typed.opts, and the library reads scalar_field only when the flag is set.  MSM_FLAG_SCALAR_FIELD
+ * together with MSM_FLAG_SCALAR_TYPE, or an unknown value, gives MSM_ERR_INVALID_ARG.
+ *
+ * Width, by the rule of the native types: with MSM_FLAG_SCALAR_BITS, scalar_bits = b bounds the
+ * magnitude, 1 <= b <= e (e = 128 or 256); without it b = e.  For MSM_FIELD_FR_MONT b is 251 (v < r <
+ * 2^251): MSM_FLAG_SCALAR_BITS must be unset or say 251.  For b <= 253 the launch geometry is exactly
+ * the narrow geometry of b -- so a column of Fr runs 16 balanced windows at c = 16, without the overflow
+ * window of the 8-word call.  MSM_FIELD_U256 with b = 254..256 runs the full-width geometry on the
+ * little-endian words.  The result is bit-identical to the 8-word call on the same integers (for
+ * MSM_FIELD_I128: on the magnitudes, with P_i negated where v_i < 0).  On a handle of levels > 1 a wide
+ * call always runs unfolded on the level-0 records, b >= 254 included.
+ *
+ * Range errors, by the rule of the narrow and native scalars: a magnitude of 2^b or more, or for
+ * MSM_FIELD_FR_MONT an a >= r, gives MSM_ERR_INVALID_ARG.  The host entries check every vector before
+ * anything is uploaded or enqueued; the device entries check in the recode kernel, which masks the
+ * value to b bits so that the launch runs to its end, and then return the error with their results
+ * unspecified.  The handle stays usable.  MSM_FIELD_U256 at b >= 254 checks nothing.
+ *
+ * Alignment: host vectors need 8-byte alignment; device vectors 4-byte alignment (MSM_ERR_INVALID_ARG
+ * otherwise, from the pointer value, before anything is enqueued).  A 16-byte-aligned device vector is
+ * read with 16-byte vector loads, a 4-byte-aligned one word by word.  A vector of m scalars is m e / 8
+ * bytes; nothing past them is touched, and that is the upload of a host entry.
+ *
+ * Honoured by the eight msm_bases_compute* entries (subsets, the `many` forms, MSM_FLAG_SERIAL,
+ * run_length and window_bits compose unchanged); every other entry that takes msm_opts, msm_bases_create*
+ * included, returns MSM_ERR_INVALID_ARG when the flag is set, before any device work. */
+#define MSM_FIELD_U128 1u
+#define MSM_FIELD_I128 2u
+#define MSM_FIELD_U256 3u
+#define MSM_FIELD_FR_MONT 4u
 typedef struct msm_opts_typed {
-  msm_opts opts;        /* flags has MSM_FLAG_SCALAR_TYPE                                          */
-  uint32_t scalar_type; /* MSM_SCALAR_*: read only when opts.flags & MSM_FLAG_SCALAR_TYPE          */
+  msm_opts opts;         /* flags has MSM_FLAG_SCALAR_TYPE or MSM_FLAG_SCALAR_FIELD                 */
+  uint32_t scalar_type;  /* MSM_SCALAR_*: read only when opts.flags & MSM_FLAG_SCALAR_TYPE          */
+  uint32_t scalar_field; /* MSM_FIELD_*: read only when opts.flags & MSM_FLAG_SCALAR_FIELD          */
 } msm_opts_typed;
 
 /* Per-phase device times (ms) of the most recent MSM on the calling thread's device when

@@ -57,8 +57,23 @@ computing the MSM of n random values of the type:
 
 with the narrow sweep's four timings and the per-phase times of one profiled awaited call.
 
+With --wide the pass is the wide-type sweep of DESIGN.md §9 (MSM_FLAG_SCALAR_FIELD): on a levels-1 handle
+of each size, for the types u128, i128, u256 and fr_mont, the MSM of n random values of the type (u256:
+the full 256 bits; fr_mont: random a < r, the scalar being a 2^-256 mod r):
+
+  {"entry": "wide", "type", "form": "words", "repeat": 0 | 1}
+        (a) the existing call on the same values converted beforehand -- scalar_bits = 128 on big-endian
+        words for the 128-bit types (i128: the magnitudes, the points of negative values negated in a handle
+        of its own), the 8-word call for the 256-bit ones -- measured before and after (b): the two rows'
+        spread is the run-to-run margin.  "convert_ms" is what the conversion costs THIS caller, in numpy
+        (limb reversal, magnitudes) and, for fr_mont, in Python integers (one modular multiplication per
+        element): informational, not a C baseline -- an arkworks prover's into_bigint() is a compiled loop
+  {"entry": "wide", "type", "form": "wide"}   (b) Bases.compute*(scalar_type=type) on the array as it is
+
+with the narrow sweep's four timings and the per-phase times of one profiled awaited call.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
-digit codes); --wide adds c = 17 so that cap can be checked.  Every timed configuration is also
+digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
 result on the host; medians over --runs repeats after one warm-up call.
 """
@@ -128,7 +143,7 @@ def one_size(a):
     emit({"entry": "msm_compute", "ms": round(ms, 4), "runs_ms": runs, "correct": res == exp[0]})
 
     c0 = M.launch_plan(n, pipelined=True)["c"]
-    widths = [c for c in range(c0, c0 + 3) if c <= 16] + ([17] if a.wide else [])
+    widths = [c for c in range(c0, c0 + 3) if c <= 16] + ([17] if a.c17 else [])
     for levels in a.levels:
         for c in widths:
             t0 = time.perf_counter()
@@ -472,6 +487,130 @@ def native_pass(a):
     return 1 if bad else 0
 
 
+def wide_pass(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import as_xy, scalar_dot
+    from oracle import oracle as O
+
+    n, count, k0, step = a.n, a.count, 3, 5
+    R = M.FR_MODULUS
+    bad = []
+
+    def emit(d):
+        d = {"n": n, **d}
+        if not d.get("correct", True):
+            bad.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    phases = ("recode_count", "coarse_scatter", "fine_sort", "accumulate", "bucket_reduce_1", "bucket_reduce_2",
+              "device_total")
+
+    def profile(fn):
+        M.set_profiling(1)
+        try:
+            fn()
+            p = M.last_profile()
+        finally:
+            M.set_profiling(0)
+        return {**{k: round(float(p[k]), 4) for k in phases}, "windows": int(p["windows"]), "c": int(p["window_bits"]),
+                "run_length": int(p["run_length"])}
+
+    def measure(row, exp, host1, dev1, host_many, dev_many):
+        ok = True
+        for key, fn, many in (("single_host", host1, False), ("single_device", dev1, False),
+                              ("pipelined_host", host_many, True), ("pipelined_device", dev_many, True)):
+            ms, runs, res = timed(fn, a.runs)
+            if many:
+                row[key + "_ms_per_msm"] = round(ms / count, 4)
+                ok = ok and [as_xy(r) for r in res] == [exp] * count
+            else:
+                row[key + "_ms"] = round(ms, 4)
+                ok = ok and res == exp
+            row[key + "_runs_ms"] = runs
+        row["phases_ms"] = profile(dev1)
+        row["correct"] = ok
+        emit(row)
+
+    pts = M.gen_points(n, k0=k0, step=step)
+    neg_pts = pts.copy()  # every point negated: x -> -x mod p, t -> -t mod p (multi-word, in numpy)
+    pw = np.array(O.int_to_be_words(O.P), dtype=np.int64)
+    for j in (0, 2):
+        d = pw[None, :] - pts[:, 8 * j:8 * j + 8].astype(np.int64)
+        for k in range(7, 0, -1):  # borrows
+            borrow = d[:, k] < 0
+            d[:, k] += borrow.astype(np.int64) << 32
+            d[:, k - 1] -= borrow
+        zero = ~pts[:, 8 * j:8 * j + 8].any(axis=1)
+        d[zero] = 0
+        neg_pts[:, 8 * j:8 * j + 8] = d.astype(np.uint32)
+    ks = k0 + step * np.arange(n, dtype=np.uint64)
+    rnd = np.random.RandomState(41)
+
+    def be_words(limbs):
+        """[n, k] little-endian u64 limbs -> [n, 2 k] big-endian u32 words: the rewrite call (a)'s caller pays."""
+        return np.ascontiguousarray(limbs.view(np.uint32)[:, ::-1])
+
+    with M.Bases.from_wire(pts, levels=1) as plain:
+        for ty in a.wide_types:
+            e = M.WIDE_TYPES[ty][1]
+            k = e // 64
+            arr = rnd.randint(0, 1 << 32, size=(n, k), dtype=np.uint64) | rnd.randint(0, 1 << 32, size=(n, k), dtype=np.uint64) << np.uint64(32)
+            isneg = np.zeros(n, bool)
+            if ty == "fr_mont":
+                arr[:, 3] %= np.uint64(R >> 192)  # a < r: the top limb below r's
+            arr = np.ascontiguousarray(arr)
+            t0 = time.perf_counter()
+            if ty == "i128":
+                isneg = (arr[:, 1] >> np.uint64(63)).astype(bool)
+                lo = np.where(isneg, ~arr[:, 0] + np.uint64(1), arr[:, 0])
+                hi = np.where(isneg, ~arr[:, 1] + (lo == 0).astype(np.uint64), arr[:, 1])
+                sc = be_words(np.ascontiguousarray(np.stack([lo, hi], axis=1)))
+            elif ty == "fr_mont":
+                rinv = pow(2, -256, R)
+                raw = arr.astype("<u8").tobytes()
+                sc = np.frombuffer(b"".join((int.from_bytes(raw[32 * i:32 * i + 32], "little") * rinv % R).to_bytes(32, "big")
+                                            for i in range(n)), dtype=">u4").astype(np.uint32).reshape(n, 8)
+            else:
+                sc = be_words(arr)
+            convert_ms = (time.perf_counter() - t0) * 1e3
+            words = sc.shape[1]
+            sc8p, sc8n = np.zeros((n, 8), np.uint32), np.zeros((n, 8), np.uint32)
+            sc8p[~isneg, 8 - words:] = sc[~isneg]
+            sc8n[isneg, 8 - words:] = sc[isneg]
+            exp = O.scalar_mul(O.G, (scalar_dot(ks, sc8p) - scalar_dot(ks, sc8n)) % O.R_ORDER)
+            base = {"entry": "wide", "type": ty, "bits": e, "count": count, "vector_bytes": int(arr.nbytes)}
+            d_sc = torch.from_numpy(sc.view(np.int32)).cuda()
+            d_arr = torch.from_numpy(arr.view(np.int64)).cuda()
+            kw = {"scalar_bits": 128} if e == 128 else {}
+            tk = {"scalar_type": ty}
+
+            def words_rows(bases, repeat):  # (a) the existing call on the converted words
+                measure({**base, "form": "words", "repeat": repeat, "convert_ms": round(convert_ms, 4)}, exp,
+                        lambda: bases.compute(sc, **kw), lambda: bases.compute_device(d_sc, **kw),
+                        lambda: bases.compute_many([sc] * count, **kw),
+                        lambda: bases.compute_many_device([d_sc] * count, **kw))
+
+            # (a) over a handle whose points carry the signs (i128), before and after (b) on the array as it is
+            signed_bases = M.Bases.from_wire(np.where(isneg[:, None], neg_pts, pts), levels=1) if isneg.any() else plain
+            try:
+                words_rows(signed_bases, 0)
+                measure({**base, "form": "wide"}, exp,
+                        lambda: plain.compute(arr, **tk), lambda: plain.compute_device(d_arr, **tk),
+                        lambda: plain.compute_many([arr] * count, **tk),
+                        lambda: plain.compute_many_device([d_arr] * count, **tk))
+                words_rows(signed_bases, 1)
+            finally:
+                if signed_bases is not plain:
+                    signed_bases.close()
+    return 1 if bad else 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -512,7 +651,9 @@ def main():
     ap.add_argument("--levels", default="1,2,4")
     ap.add_argument("--count", type=int, default=20)
     ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--wide", action="store_true", help="also time c = 17 (32-bit digit codes)")
+    ap.add_argument("--c17", action="store_true", help="also time c = 17 (32-bit digit codes)")
+    ap.add_argument("--wide", action="store_true", help="the wide-type sweep (MSM_FLAG_SCALAR_FIELD) instead")
+    ap.add_argument("--wide-types", default="u128,i128,u256,fr_mont", help="types of the wide sweep")
     ap.add_argument("--out", default="")
     ap.add_argument("--subset", action="store_true", help="the subset sweep (msm_bases_compute_subset*) instead")
     ap.add_argument("--subset-sizes", default="12,16,18,20", help="log2 term counts m of the subset sweep")
@@ -540,6 +681,19 @@ def main():
                "--subset", "--subset-sizes", ",".join(map(str, a.subset_sizes)), "--count", str(a.count),
                "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
         return subprocess.run(cmd).returncode
+    if a.wide:
+        a.wide_types = [x for x in str(a.wide_types).split(",") if x]
+        if a.n:
+            return wide_pass(a)
+        for lg in (int(x) for x in a.sizes.split(",")):
+            cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n",
+                   str(1 << lg), "--wide", "--wide-types", ",".join(a.wide_types), "--count", str(a.count),
+                   "--runs", str(a.runs)]
+            rc = subprocess.run(cmd + (["--out", a.out] if a.out else [])).returncode
+            if rc != 0:
+                print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)
+                return rc
+        return 0
     if a.native:
         a.native_types = [x for x in str(a.native_types).split(",") if x]
         if a.n:
@@ -572,7 +726,7 @@ def main():
     for lg in (int(x) for x in a.sizes.split(",")):
         cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n", str(1 << lg),
                "--levels", ",".join(map(str, a.levels)), "--count", str(a.count), "--runs", str(a.runs)]
-        cmd += (["--wide"] if a.wide else []) + (["--out", a.out] if a.out else [])
+        cmd += (["--c17"] if a.c17 else []) + (["--out", a.out] if a.out else [])
         rc = subprocess.run(cmd).returncode
         if rc != 0:
             print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)

@@ -144,6 +144,8 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   // own geometry (make_plan); 254 bits and more are the 8-word call as it is.
   // Native scalar types (MSM_FLAG_SCALAR_TYPE): the narrow call of b = scalar_bits, or of the element's
   // own width where that is unset, on the caller's own integer array.
+  // Wide types (MSM_FLAG_SCALAR_FIELD): the same on little-endian 128- / 256-bit elements; always unfolded,
+  // a 256-bit integer of 254 bits and more included (the full-width launch on the level-0 records).
   const bool bits_set = opts && (opts->flags & MSM_FLAG_SCALAR_BITS);
   const uint32_t stype = opts_scalar_type(opts);
   if (typed_flagged(opts) && !typed_width(stype, bits_set, bits_set ? opts->scalar_bits : 0)) return MSM_ERR_INVALID_ARG;
@@ -152,7 +154,8 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
                                : bits_set ? opts->scalar_bits : 256;
   if (sbits < 1 || sbits > 256) return MSM_ERR_INVALID_ARG;
   const bool narrow = sbits < MAIN_BITS;
-  const uint32_t levels = narrow ? 1u : b->levels;
+  const bool wide = stype_wide(stype);
+  const uint32_t levels = narrow || wide ? 1u : b->levels;
   if (sub) {
     if (int rc = subset_check(b->n, levels, sub->first, sub->m, indexed)) return rc;
     for (size_t k = 0; indexed && terms && k < count; k++) {
@@ -176,7 +179,10 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
     o.flags |= MSM_FLAG_SCALAR_BITS;
     o.scalar_bits = sbits;
   }
-  if (stype) {
+  if (wide) {
+    o.flags |= MSM_FLAG_SCALAR_FIELD;
+    ot.scalar_field = stype & ~STYPE_WIDE;
+  } else if (stype) {
     o.flags |= MSM_FLAG_SCALAR_TYPE;
     ot.scalar_type = stype;
   }
@@ -190,9 +196,9 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
   if (count == 0) return MSM_OK;
   for (size_t k = 0; k < count; k++) {
     if (!scalars[k] && terms) return MSM_ERR_INVALID_ARG;
-    // a native vector's alignment, from the pointer value: the element's own on the host, 4 bytes on
-    // the device (the recode reads whole words)
-    if (stype && (reinterpret_cast<uintptr_t>(scalars[k]) & (host ? std::max(ebits / 8, 1u) - 1u : 3u)))
+    // a native vector's alignment, from the pointer value: the element's own on the host (a wide
+    // element's u64 limbs': 8 bytes), 4 bytes on the device (the recode reads whole words)
+    if (stype && (reinterpret_cast<uintptr_t>(scalars[k]) & (host ? std::min(std::max(ebits / 8, 1u), 8u) - 1u : 3u)))
       return MSM_ERR_INVALID_ARG;
   }
   // A bit at or above scalar_bits: host vectors are checked on the host, before anything is uploaded
@@ -223,7 +229,51 @@ int bases_compute(const msm_bases* h, const uint32_t* const* scalars, bool host,
     }
     return a;
   };
+  // A wide vector's elements [i0, i1): whether any magnitude has a bit at or above sbits, or, for
+  // Montgomery-form Fr, any a >= r (fr.cuh's test, the recode kernel's own).
+  auto wide_bad = [&](const uint32_t* vec, size_t i0, size_t i1) -> bool {
+    const uint32_t ew = ebits / 32;
+    if (stype == STYPE_FR_MONT) {
+      for (size_t i = i0; i < i1; i++)
+        if (!fr_is_canonical(vec + i * 8)) return true;
+      return false;
+    }
+    uint32_t acc[8] = {};  // the OR of the magnitudes, little-endian words
+    for (size_t i = i0; i < i1; i++) {
+      const uint32_t* e = vec + i * ew;
+      if (stype == STYPE_I128 && (e[3] >> 31)) {
+        uint32_t cy = 1;
+        for (uint32_t k = 0; k < 4; k++) {
+          const uint64_t x = (uint64_t)(~e[k]) + cy;
+          acc[k] |= (uint32_t)x;
+          cy = (uint32_t)(x >> 32);
+        }
+      } else {
+        for (uint32_t k = 0; k < ew; k++) acc[k] |= e[k];
+      }
+    }
+    for (uint32_t k = 0; k < ew; k++) {
+      const uint32_t keep = sbits >= 32 * k + 32 ? 0xffffffffu : sbits > 32 * k ? (1u << (sbits - 32 * k)) - 1u : 0u;
+      if (acc[k] & ~keep) return true;
+    }
+    return false;
+  };
   auto host_scalars_ok = [&](DevCtx* c) -> bool {
+    if (wide) {
+      // (a 256-bit integer of 254 bits and more checks nothing, as the 254- and 255-bit word format)
+      if (!host || (stype != STYPE_FR_MONT && (sbits >= ebits || sbits >= MAIN_BITS))) return true;
+      for (size_t k = 0; k < count; k++) {
+        if (k && scalars[k] == scalars[k - 1]) continue;
+        std::atomic<uint32_t> any{0};
+        auto scan = [&](int t, int nt) {
+          if (wide_bad(scalars[k], terms * t / nt, terms * (t + 1) / nt)) any.store(1);
+        };
+        if (terms >= (1u << 17)) ctx_packer(c)->run(scan);
+        else scan(0, 1);
+        if (any.load()) return false;
+      }
+      return true;
+    }
     if (stype) {
       if (!host || sbits >= ebits) return true;
       for (size_t k = 0; k < count; k++) {

@@ -141,9 +141,10 @@ struct Plan {
   // The dense-bucket accumulation (finish_plan; k_dense_* in the place of k_accumulate): entries per
   // unit lane E (a unit's segment is 64 E entries) and the unit kernel's grid bound.  Zero otherwise.
   uint32_t dense, dense_E, dense_units;
-  // Native scalar types (msm_opts_typed): MSM_SCALAR_* of the launch's vectors, 0 for word formats, and
-  // the bytes of one vector, ceil(n e / 8).  The geometry in `d` is the narrow one of d.sbits and knows
-  // nothing of the type: only the recode kernel's choice and the upload's length follow it.
+  // Native scalar types (msm_opts_typed): MSM_SCALAR_* of the launch's vectors -- or STYPE_WIDE | MSM_FIELD_*
+  // of a wide type's (host_plan.h) -- 0 for word formats, and the bytes of one vector, ceil(n e / 8).  The
+  // geometry in `d` is the narrow one of d.sbits (a 256-bit integer of 254 bits and more: the full-width
+  // one) and knows nothing of the type: only the recode kernel's choice and the upload's length follow it.
   uint32_t stype;
   size_t sc_bytes;
 };

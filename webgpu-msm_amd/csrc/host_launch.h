@@ -150,9 +150,22 @@ const void* recode_native_fn(uint32_t stype) {
 }
 constexpr uint32_t NATIVE_TYPES[] = {MSM_SCALAR_BIT, MSM_SCALAR_U8,  MSM_SCALAR_U16, MSM_SCALAR_U32, MSM_SCALAR_U64,
                                      MSM_SCALAR_I8,  MSM_SCALAR_I16, MSM_SCALAR_I32, MSM_SCALAR_I64};
-// The recode kernel of a narrow or native plan (both take k_recode_narrow's six arguments).
+// The wide recode (Plan::stype with STYPE_WIDE, narrow geometry): one k_recode_wide instantiation per
+// element kind and code width.
+template <typename T>
+const void* recode_wide_fn(uint32_t stype) {
+  switch (stype) {
+    case STYPE_U128: return reinterpret_cast<const void*>(&k_recode_wide<T, 4, WIDE_U>);
+    case STYPE_I128: return reinterpret_cast<const void*>(&k_recode_wide<T, 4, WIDE_I>);
+    case STYPE_FR_MONT: return reinterpret_cast<const void*>(&k_recode_wide<T, 8, WIDE_MONT>);
+    default: return reinterpret_cast<const void*>(&k_recode_wide<T, 8, WIDE_U>);  // STYPE_U256
+  }
+}
+constexpr uint32_t WIDE_TYPES[] = {STYPE_U128, STYPE_I128, STYPE_U256, STYPE_FR_MONT};
+// The recode kernel of a narrow, native or wide plan (all take k_recode_narrow's six arguments).
 const void* recode_kernel(const Plan& pl) {
   if (!pl.stype) return recode_narrow_kernel(pl.d);
+  if (stype_wide(pl.stype)) return pl.d.c > 16 ? recode_wide_fn<uint32_t>(pl.stype) : recode_wide_fn<uint16_t>(pl.stype);
   return pl.d.c > 16 ? recode_native_fn<uint32_t>(pl.stype) : recode_native_fn<uint16_t>(pl.stype);
 }
 
@@ -167,6 +180,15 @@ void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* 
     NarrowBias nb = narrow_bias(d);
     void* args[] = {&scal, &dd, &digits, &colsum, &nb, &err};
     (void)hipLaunchKernel(recode_kernel(pl), grid, dim3(RC_THREADS), args, lds, s);
+    return;
+  }
+  if (pl.stype) {  // a 256-bit integer of 254 bits and more: the full-width geometry on little-endian words
+    if (d.c > 16)
+      hipLaunchKernelGGL(k_recode_hist_le<uint32_t>, grid, dim3(RC_THREADS), lds, s, sc, d,
+                         static_cast<uint32_t*>(digits), colsum);
+    else
+      hipLaunchKernelGGL(k_recode_hist_le<uint16_t>, grid, dim3(RC_THREADS), lds, s, sc, d,
+                         static_cast<uint16_t*>(digits), colsum);
     return;
   }
   if (d.c > 16) {
@@ -186,6 +208,8 @@ void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* 
 bool is_recode_kernel(const void* f) {
   const void* ks[] = {reinterpret_cast<const void*>(&k_recode_hist<uint32_t>),
                       reinterpret_cast<const void*>(&k_recode_hist<uint16_t>),
+                      reinterpret_cast<const void*>(&k_recode_hist_le<uint32_t>),
+                      reinterpret_cast<const void*>(&k_recode_hist_le<uint16_t>),
                       reinterpret_cast<const void*>(&k_recode_fixed<15, 14, true>),
                       reinterpret_cast<const void*>(&k_recode_fixed<15, 14, false>),
                       reinterpret_cast<const void*>(&k_recode_fixed<14, 16, true>),
@@ -202,6 +226,8 @@ bool is_recode_kernel(const void* f) {
   // and every native one: the same trap
   for (uint32_t ty : NATIVE_TYPES)
     if (f == recode_native_fn<uint16_t>(ty) || f == recode_native_fn<uint32_t>(ty)) return true;
+  for (uint32_t ty : WIDE_TYPES)
+    if (f == recode_wide_fn<uint16_t>(ty) || f == recode_wide_fn<uint32_t>(ty)) return true;
   return false;
 }
 

@@ -8,9 +8,11 @@
 // host thread each, and the join is projective (one EC add per shard, one inversion at the end).
 
 bool devices_listed(const msm_opts* o) { return o && (o->flags & MSM_FLAG_DEVICES); }
-// MSM_FLAG_SCALAR_BITS and MSM_FLAG_SCALAR_TYPE belong to the msm_bases_compute* entries: every other
-// entry refuses them before it touches a device (their scalars are the 8-word format).
-bool narrow_flagged(const msm_opts* o) { return o && (o->flags & (MSM_FLAG_SCALAR_BITS | MSM_FLAG_SCALAR_TYPE)); }
+// MSM_FLAG_SCALAR_BITS, MSM_FLAG_SCALAR_TYPE and MSM_FLAG_SCALAR_FIELD belong to the msm_bases_compute*
+// entries: every other entry refuses them before it touches a device (their scalars are the 8-word format).
+bool narrow_flagged(const msm_opts* o) {
+  return o && (o->flags & (MSM_FLAG_SCALAR_BITS | MSM_FLAG_SCALAR_TYPE | MSM_FLAG_SCALAR_FIELD));
+}
 
 // The listed ordinals, checked for shape (non-null, 1..MSM_MAX_DEVICES entries, non-negative,
 // distinct) before any device is touched, then for being gfx950 devices.

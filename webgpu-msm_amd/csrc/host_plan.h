@@ -133,8 +133,16 @@ constexpr uint32_t NARROW_WIDE_C = 17, NARROW_DENSE = 64;  // the narrow launche
 
 // Native scalar types (include/msm.h MSM_FLAG_SCALAR_TYPE): element bits e and signedness of a
 // MSM_SCALAR_* value (e = 0: unknown), and the type an options struct carries (0: none).
+// Wide types (MSM_FLAG_SCALAR_FIELD) share the plan's one type field and every function below: inside
+// the library MSM_FIELD_x is the type STYPE_WIDE | MSM_FIELD_x (the public MSM_SCALAR_* values stay nine).
+constexpr uint32_t STYPE_WIDE = 0x100u;
+constexpr uint32_t STYPE_U128 = STYPE_WIDE | MSM_FIELD_U128, STYPE_I128 = STYPE_WIDE | MSM_FIELD_I128,
+                   STYPE_U256 = STYPE_WIDE | MSM_FIELD_U256, STYPE_FR_MONT = STYPE_WIDE | MSM_FIELD_FR_MONT;
+bool stype_wide(uint32_t type) { return (type & STYPE_WIDE) != 0; }
 uint32_t scalar_type_bits(uint32_t type) {
   switch (type) {
+    case STYPE_U128: case STYPE_I128: return 128;
+    case STYPE_U256: case STYPE_FR_MONT: return 256;
     case MSM_SCALAR_BIT: return 1;
     case MSM_SCALAR_U8: case MSM_SCALAR_I8: return 8;
     case MSM_SCALAR_U16: case MSM_SCALAR_I16: return 16;
@@ -143,16 +151,23 @@ uint32_t scalar_type_bits(uint32_t type) {
     default: return 0;
   }
 }
-bool scalar_type_signed(uint32_t type) { return type >= MSM_SCALAR_I8 && type <= MSM_SCALAR_I64; }
-bool typed_flagged(const msm_opts* o) { return o && (o->flags & MSM_FLAG_SCALAR_TYPE); }
+bool scalar_type_signed(uint32_t type) { return (type >= MSM_SCALAR_I8 && type <= MSM_SCALAR_I64) || type == STYPE_I128; }
+bool typed_flagged(const msm_opts* o) { return o && (o->flags & (MSM_FLAG_SCALAR_TYPE | MSM_FLAG_SCALAR_FIELD)); }
+// (both flags together, or a value outside its flag's table: a type of no width, which typed_width refuses)
 uint32_t opts_scalar_type(const msm_opts* o) {
-  return typed_flagged(o) ? reinterpret_cast<const msm_opts_typed*>(o)->scalar_type : 0u;
+  if (!typed_flagged(o)) return 0u;
+  const msm_opts_typed* t = reinterpret_cast<const msm_opts_typed*>(o);
+  if (!(o->flags & MSM_FLAG_SCALAR_FIELD)) return t->scalar_type & STYPE_WIDE ? ~0u : t->scalar_type;
+  if ((o->flags & MSM_FLAG_SCALAR_TYPE) || t->scalar_field >= STYPE_WIDE) return ~0u;
+  return STYPE_WIDE | t->scalar_field;
 }
 // The magnitude bits b of a typed call: scalar_bits where MSM_FLAG_SCALAR_BITS is set (1..e; a bit
-// vector's must be 1), else e.  0: an argument error.
+// vector's must be 1), else e.  A Montgomery-form Fr is below r < 2^251: b = 251, said or unsaid.
+// 0: an argument error.
 uint32_t typed_width(uint32_t type, bool has_bits, uint32_t bits) {
   const uint32_t e = scalar_type_bits(type);
   if (!e) return 0;
+  if (type == STYPE_FR_MONT) return !has_bits || bits == FR_BITS ? FR_BITS : 0;
   if (!has_bits) return e;
   return bits >= 1 && bits <= e ? bits : 0;
 }
@@ -219,7 +234,11 @@ int make_plan(size_t n, const msm_opts* o, const DevShape& sh, Plan* pl, bool pi
       return MSM_ERR_INVALID_ARG;
     }
   } else if (typed_flagged(o)) {
-    return MSM_ERR_INVALID_ARG;  // (the entry resolves an unset width to the element's before it plans)
+    // (the entry resolves an unset width to the element's before it plans)  Only a 256-bit integer of
+    // 254 bits and more comes here unset: the full-width geometry above as it is, on little-endian words.
+    if (opts_scalar_type(o) != STYPE_U256 || (o->flags & MSM_FLAG_WINDOWS)) return MSM_ERR_INVALID_ARG;
+    pl->stype = STYPE_U256;
+    pl->sc_bytes = typed_vector_bytes(n, STYPE_U256);
   }
   if (o && (o->flags & MSM_FLAG_WINDOWS)) {
     // a window range needs an explicit width, so that every caller's ranges cut the same windows

@@ -446,6 +446,42 @@ int msm_test_native_plan(size_t n, uint32_t scalar_type, uint32_t scalar_bits, u
   return MSM_OK;
 }
 
+// The plan of one wide-type MSM (MSM_FLAG_SCALAR_FIELD with MSM_FLAG_SCALAR_BITS) of n terms, as the entry
+// makes it: out = msm_test_narrow_plan's six fields for scalar_bits (254 bits and more of a 256-bit
+// integer: the plain launch, 8 words), then the bytes of one vector and of its region in a slot's wire
+// buffer.  The entry's argument rules apply (unknown field, scalar_bits 0 or past the element's width, a
+// Montgomery-form Fr of any width but 251: MSM_ERR_INVALID_ARG).  Host code only.
+int msm_test_wide_plan(size_t n, uint32_t field, uint32_t scalar_bits, uint32_t window_bits, uint32_t out[8]) {
+  msm_opts_typed op{};
+  op.opts.window_bits = window_bits;
+  op.opts.flags = MSM_FLAG_SCALAR_FIELD | MSM_FLAG_SCALAR_BITS;
+  op.opts.scalar_bits = scalar_bits;
+  op.scalar_field = field;
+  const uint32_t stype = opts_scalar_type(&op.opts);
+  if (!out || !typed_width(stype, true, scalar_bits)) return MSM_ERR_INVALID_ARG;
+  // (as bases_compute: the width is said to the planner only below 254 bits)
+  if (scalar_bits >= MAIN_BITS) op.opts.flags = MSM_FLAG_SCALAR_FIELD;
+  Plan pl;
+  if (int rc = make_plan(n, &op.opts, DevShape{}, &pl, false, 1, true)) return rc;
+  if (pl.stype != stype) return MSM_ERR_INVALID_ARG;
+  const uint32_t v[8] = {pl.d.c,  pl.d.Wr,     pl.d.q,
+                         pl.d.nhi, pl.d.sw ? pl.d.sw : 8u, pl.d.packed,
+                         (uint32_t)pl.sc_bytes, (uint32_t)typed_region_bytes(n, stype)};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// fr.cuh on the host: n values of 8 little-endian words each; ok[i] = fr_is_canonical(in_i) and
+// out_i = fr_from_mont(in_i) (computed whatever ok says, as the recode kernel does).
+int msm_test_fr_from_mont(const uint32_t* in_le, size_t n, uint32_t* out_le, uint8_t* ok) {
+  if ((!in_le || !out_le || !ok) && n) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n; i++) {
+    ok[i] = fr_is_canonical(in_le + 8 * i) ? 1 : 0;
+    fr_from_mont(in_le + 8 * i, out_le + 8 * i);
+  }
+  return MSM_OK;
+}
+
 // The dense-bucket part of the plan of a narrow launch (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
 // of nm MSMs of n terms at width window_bits (0: auto), pipelined or lone: out = {dense (0 / 1),
 // entries per unit lane E, keys W * B, the unit kernel's grid bound, run length K}, for the default

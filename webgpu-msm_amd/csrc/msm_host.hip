@@ -136,7 +136,8 @@ int msm_compute_cocompute(const uint32_t* points_be, const uint32_t* scalars_be,
   if (!out_xy_be || ((!points_be || !scalars_be) && n) || !(cpu_work_ratio >= 0.0)) return MSM_ERR_INVALID_ARG;
   // a window range has no CPU counterpart (the host Pippenger computes every window): joining a
   // range's GPU share with a whole CPU share would be silently wrong
-  if (opts && (opts->flags & (MSM_FLAG_WINDOWS | MSM_FLAG_SCALAR_BITS | MSM_FLAG_SCALAR_TYPE))) return MSM_ERR_INVALID_ARG;
+  if (opts && (opts->flags & (MSM_FLAG_WINDOWS | MSM_FLAG_SCALAR_BITS | MSM_FLAG_SCALAR_TYPE | MSM_FLAG_SCALAR_FIELD)))
+    return MSM_ERR_INVALID_ARG;
   // cpuShare = floor(cpuWorkRatio * n) (submission.ts:98); >= n is the reference's CPU-only branch
   const double share_d = cpu_work_ratio * (double)n;
   const size_t share = share_d >= (double)n ? n : (size_t)share_d;

@@ -11,7 +11,9 @@
 //                      k_recode_narrow is the same for scalars of 1..8 words over the windows of
 //                      their own bits (msm_bases_compute* with MSM_FLAG_SCALAR_BITS), and
 //                      k_recode_native for the caller's own integer arrays (bit / 8 / 16 / 32 / 64-bit
-//                      elements, signed ones included: MSM_FLAG_SCALAR_TYPE)
+//                      elements, signed ones included: MSM_FLAG_SCALAR_TYPE), k_recode_wide for
+//                      little-endian 128- / 256-bit integers and Montgomery-form Fr (MSM_FLAG_SCALAR_FIELD;
+//                      k_recode_hist_le where a 256-bit integer takes the full-width geometry)
 //   k_part_scatter     digits -> coarse bins (each chunk reserves and writes one contiguous slice
 //                      per bin); its range / indexed variants map a subset launch's positions to
 //                      a handle's records (k_stage_indices checks a device caller's indices first)
@@ -33,6 +35,7 @@
 // bucket count.
 #include "ec.cuh"
 #include "msm_dev.h"
+#include "fr.cuh"
 
 
 namespace msm {
@@ -991,6 +994,162 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_native(BatchPtrs scalar_s
     }
   }
   if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  __syncthreads();
+  flush_hist(lds_hist, d, w0, colsum);
+}
+
+// Wide scalars (msm_opts_typed.scalar_field, MSM_FLAG_SCALAR_FIELD): elements of SW = 4 or 8 LITTLE-endian
+// words -- u128 / i128, u256 (arkworks BigInt<4>) and Fr in Montgomery form -- over the narrow geometry
+// of d.sbits = b <= 253 magnitude bits.  The body is k_recode_narrow's bias-add and per-window funnel
+// shift; what differs is the word order at the load (word 0 is the least significant), for WIDE_I the
+// magnitude and sign XOR of k_recode_native (|v| in 128-bit unsigned arithmetic, so -2^127 is 2^127), and
+// for WIDE_MONT fr_from_mont (fr.cuh: v = a 2^-256 mod r, 8 rounds of word REDC) ahead of the bias-add,
+// with a >= r reported.  A lane takes R = 2 adjacent scalars, 32 or 64 B, as 16-B vector loads where the
+// vector is 16-B aligned and word by word where it is only 4-B aligned; the lane that holds the odd
+// tail of the span reads only its own scalar's words, so nothing past byte n SW 4 is touched.
+// Magnitude bits at or above b are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE); REDC's output is
+// below r whatever a was, and is masked like the rest, so every digit stays inside its window.
+constexpr uint32_t WIDE_U = 0, WIDE_I = 1, WIDE_MONT = 2;
+template <typename T, uint32_t SW, uint32_t MODE>
+__global__ void __launch_bounds__(RC_THREADS) k_recode_wide(BatchPtrs scalar_sets, MsmDims d,
+                                                            T* __restrict__ digits, uint32_t* __restrict__ colsum,
+                                                            NarrowBias bias, uint32_t* __restrict__ err) {
+  using DC = DigitCode<T>;
+  constexpr uint32_t R = 2;        // scalars per lane
+  constexpr uint32_t LW = R * SW;  // words per lane
+  static_assert(SW == 4 || SW == 8, "128- or 256-bit elements");
+  static_assert(MODE == WIDE_U || (MODE == WIDE_I && SW == 4) || (MODE == WIDE_MONT && SW == 8), "element kinds");
+  extern __shared__ uint32_t lds_hist[];  // [Wr][nbc]
+  const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
+  const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
+  const uint32_t w0 = blockIdx.y * d.Wr;
+  const uint32_t nh = d.Wr * d.nbc;
+  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
+  // value bits of every word (little-endian): all of it below b, none of it at and above
+  uint32_t wmask[SW];
+#pragma unroll
+  for (uint32_t k = 0; k < SW; k++)
+    wmask[k] = d.sbits >= 32 * k + 32 ? 0xffffffffu : d.sbits > 32 * k ? (1u << (d.sbits - 32 * k)) - 1u : 0u;
+  const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
+  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
+  bool bad = false;
+  __syncthreads();
+  for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
+    const uint32_t cnt = min(R, hi - i);
+    uint32_t raw[LW];
+    const uint32_t* p = scalars + (size_t)i * SW;
+    if (cnt == R && vec) {  // (i is even and an element 16 or 32 B: the lane's run is 16-B aligned)
+#pragma unroll
+      for (uint32_t k = 0; k < LW / 4; k++) {
+        const uint4 v = reinterpret_cast<const uint4*>(p)[k];
+        raw[4 * k] = v.x, raw[4 * k + 1] = v.y, raw[4 * k + 2] = v.z, raw[4 * k + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < LW; k++) raw[k] = k < cnt * SW ? p[k] : 0u;
+    }
+    uint32_t t[R][SW + 1];
+    bool neg[R];
+#pragma unroll
+    for (uint32_t r = 0; r < R; r++) {
+      uint32_t m[SW];  // the magnitude, little-endian words
+#pragma unroll
+      for (uint32_t k = 0; k < SW; k++) m[k] = raw[r * SW + k];
+      neg[r] = MODE == WIDE_I && (m[SW - 1] >> 31) != 0;
+      if (MODE == WIDE_I) {  // |v| = ~v + 1 in SW-word unsigned arithmetic
+        uint32_t cy = 1;
+#pragma unroll
+        for (uint32_t k = 0; k < SW; k++) {
+          const uint64_t x = (uint64_t)(~m[k]) + cy;
+          m[k] = neg[r] ? (uint32_t)x : m[k];
+          cy = (uint32_t)(x >> 32);
+        }
+      }
+      if constexpr (MODE == WIDE_MONT) {
+        bad = bad || !fr_is_canonical(m);
+        fr_from_mont(m, m);
+      }
+      uint32_t cy = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < SW; k++) {
+        bad = bad || (m[k] & ~wmask[k]) != 0;
+        const uint64_t x = (uint64_t)(m[k] & wmask[k]) + bias.v[k] + cy;
+        t[r][k] = (uint32_t)x;
+        cy = (uint32_t)(x >> 32);
+      }
+      t[r][SW] = cy;
+    }
+    T* row = digits + (size_t)w0 * d.n + i;
+    uint32_t* h = lds_hist;
+    for (uint32_t w = 0; w < d.Wr; w++) {
+      const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
+      const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
+      const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
+      uint32_t code[R];
+#pragma unroll
+      for (uint32_t r = 0; r < R; r++) {
+        const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
+#pragma unroll
+        for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
+        t[r][SW] >>= b;
+        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+        const bool live = digit != 0 && r < cnt;
+        // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
+        atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
+        code[r] = live ? mag | ((digit < 0) != neg[r] ? DC::SIGN : 0u) : DC::ZERO;
+      }
+      if (pair_store && cnt == R) {
+        *reinterpret_cast<uint32_t*>(row) = code[0] | code[1] << 16;
+      } else {
+        row[0] = (T)code[0];
+        if (cnt == R) row[1] = (T)code[1];
+      }
+      row += d.n;
+      h += d.nbc;
+    }
+  }
+  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  __syncthreads();
+  flush_hist(lds_hist, d, w0, colsum);
+}
+
+// MSM_FIELD_U256 of 254..256 bits: k_recode_hist on little-endian words -- the full-width geometry,
+// overflow window included, on the caller's BigInt<4> array.  A kernel of its own, so that the 8-word
+// launches keep theirs as they are.  16-B vector loads where the vector is 16-B aligned, else word
+// by word.
+template <typename T>
+__global__ void __launch_bounds__(RC_THREADS) k_recode_hist_le(BatchPtrs scalar_sets, MsmDims d,
+                                                               T* __restrict__ digits, uint32_t* __restrict__ colsum) {
+  extern __shared__ uint32_t lds_hist[];  // [Wr][nbc]
+  const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
+  const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
+  const uint32_t w0 = blockIdx.y * d.Wr;
+  const uint32_t nh = d.Wr * d.nbc;
+  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
+  const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
+  __syncthreads();
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += RC_THREADS) {
+    uint32_t s[8];
+    const uint32_t* p = scalars + (size_t)i * 8;
+    if (vec) {
+      const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
+      s[0] = a.x, s[1] = a.y, s[2] = a.z, s[3] = a.w, s[4] = b.x, s[5] = b.y, s[6] = b.z, s[7] = b.w;
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++) s[k] = p[k];
+    }
+    recode(s, d, [&](uint32_t wa, int32_t digit) {
+      const uint32_t w = wa - d.w0;  // local window (the launch covers every window: w0 = 0)
+      if (w >= d.Wr) return;
+      uint32_t code = DigitCode<T>::ZERO;
+      if (digit != 0) {
+        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+        code = mag | (digit < 0 ? DigitCode<T>::SIGN : 0u);
+        atomicAdd(&lds_hist[w * d.nbc + (mag >> win_fb(d, wa))], 1u);
+      }
+      digits[(size_t)(w0 + w) * d.n + i] = (T)code;
+    });
+  }
   __syncthreads();
   flush_hist(lds_hist, d, w0, colsum);
 }

@@ -126,6 +126,7 @@ struct Job {
   std::vector<uint32_t> indices;
   uint32_t scalar_bits = 0;  // computeMsmPrepared: narrow scalars (MSM_FLAG_SCALAR_BITS); 0 = the 8-word format
   uint32_t scalar_type = 0;  // computeMsmPrepared: a native integer array (MSM_FLAG_SCALAR_TYPE); 0 = a word format
+  uint32_t scalar_field = 0; // computeMsmPrepared: wide scalars (MSM_FLAG_SCALAR_FIELD, MSM_FIELD_*); 0 = none
   uint32_t out[16] = {0};
   int rc = 0;
 };
@@ -154,6 +155,10 @@ void execute(napi_env, void* data) {
   if (j->scalar_type) {
     ob.flags |= MSM_FLAG_SCALAR_TYPE;
     obt.scalar_type = j->scalar_type;
+  }
+  if (j->scalar_field) {
+    ob.flags |= MSM_FLAG_SCALAR_FIELD;
+    obt.scalar_field = j->scalar_field;
   }
   if (j->bases && j->subset) {
     const uint32_t* ix = j->indices.data();
@@ -242,6 +247,22 @@ const NativeType* native_type(napi_env env, napi_value v) {
   size_t len = 0;
   if (napi_get_value_string_utf8(env, v, name, sizeof(name), &len) != napi_ok) return nullptr;
   for (const NativeType& t : NATIVE_TYPES)
+    if (!strcmp(name, t.name)) return &t;
+  return nullptr;
+}
+// computeMsmPrepared's wide `scalarType` names: the MSM_FIELD_* value and the element's bytes.  Such a
+// vector comes as a BigUint64Array, Uint32Array or Uint8Array of little-endian limbs, words or bytes.
+struct WideType {
+  const char* name;
+  uint32_t field, bytes;
+};
+const WideType WIDE_TYPES[] = {{"u128", MSM_FIELD_U128, 16}, {"i128", MSM_FIELD_I128, 16},
+                               {"u256", MSM_FIELD_U256, 32}, {"fr_mont", MSM_FIELD_FR_MONT, 32}};
+const WideType* wide_type(napi_env env, napi_value v) {
+  char name[8] = {0};
+  size_t len = 0;
+  if (napi_get_value_string_utf8(env, v, name, sizeof(name), &len) != napi_ok) return nullptr;
+  for (const WideType& t : WIDE_TYPES)
     if (!strcmp(name, t.name)) return &t;
   return nullptr;
 }
@@ -601,6 +622,8 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
 // With `scalarType` (a name of NATIVE_TYPES) the scalars are a typed array of that integer type as it is
 // (MSM_FLAG_SCALAR_TYPE): its class must be the type's, scalarBits then bounds the magnitude, and a
 // bitmap's term count is `count`, else the index list's length, the handle's n, or 8 per byte.
+// A name of WIDE_TYPES declares little-endian 128- / 256-bit elements (MSM_FLAG_SCALAR_FIELD): a
+// BigUint64Array, Uint32Array or Uint8Array of exactly the call's terms.
 napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv);
 napi_value ComputeMsmPrepared(napi_env env, napi_callback_info info) {
   size_t argc = 7;
@@ -676,13 +699,20 @@ napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv) 
     return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
   };
   const bool has_first = given(2), has_idx = given(3), has_bits = given(4), has_count = given(6);
-  const NativeType* ty = native_type(env, argv[5]);
+  const WideType* wt = wide_type(env, argv[5]);
+  const NativeType* ty = wt ? nullptr : native_type(env, argv[5]);
   double first = 0, bits = 0, count = 0;
   const void* sc = nullptr;
   const uint32_t* ix = nullptr;
-  size_t slen = 0, ilen = 0;
+  size_t slen = 0, ilen = 0, welem = 0;  // welem: bytes per element of a wide vector's array
   bool sshared = false;
-  if (!h || !ty || !get_typed_array(env, argv[1], ty->cls, &sc, &slen, &sshared) ||
+  if (wt) {
+    const struct { napi_typedarray_type cls; size_t bytes; } classes[] = {
+        {napi_biguint64_array, 8}, {napi_uint32_array, 4}, {napi_uint8_array, 1}};
+    for (const auto& k : classes)
+      if (!welem && get_typed_array(env, argv[1], k.cls, &sc, &slen, &sshared)) welem = k.bytes;
+  }
+  if (!h || (!ty && !welem) || (ty && !get_typed_array(env, argv[1], ty->cls, &sc, &slen, &sshared)) ||
       (has_first && (napi_get_value_double(env, argv[2], &first) != napi_ok || !(first >= 0) ||
                      first > 9007199254740992.0 || first != (double)(uint64_t)first)) ||
       (has_idx && !get_u32_array(env, argv[3], &ix, &ilen)) ||
@@ -692,17 +722,24 @@ napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv) 
     napi_throw_type_error(env, nullptr,
                           "computeMsmPrepared(id, scalars, first?, indices?, scalarBits?, scalarType, count?): scalars "
                           "must be the typed array of scalarType (Uint8Array for bit and u8, Int8Array .. "
-                          "BigInt64Array / BigUint64Array for the rest)");
+                          "BigInt64Array / BigUint64Array for the rest; a BigUint64Array, Uint32Array or Uint8Array "
+                          "for u128, i128, u256 and fr_mont)");
     return nullptr;
   }
-  if (has_bits && (bits < 1 || bits > ty->bits)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  const uint32_t ebits = wt ? wt->bytes * 8 : ty->bits;
+  if (has_bits && (bits < 1 || bits > ebits)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  if (wt && (slen * welem) % wt->bytes) {
+    napi_throw_range_error(env, nullptr, "the array is not a whole number of elements");
+    return nullptr;
+  }
   msm_bases_info_t inf;
   int rc = msm_bases_info(h, &inf);
   if (rc != MSM_OK) return throw_rc(env, rc);  // released, or never a handle
   const bool subset = has_first || has_idx;
-  const size_t held = ty->bits == 1 ? slen * 8 : slen;  // scalars the array can hold
+  const size_t held = wt ? slen * welem / wt->bytes : ty->bits == 1 ? slen * 8 : slen;  // scalars the array can hold
   const size_t m = has_count ? (size_t)count : has_idx ? ilen : subset ? held : (size_t)inf.n;
-  if (m > held || (!subset && m < inf.n)) {
+  // (a wide vector holds exactly the call's terms: its length is the only count there is to check)
+  if (m > held || (!subset && m < inf.n) || (wt && m != held)) {
     napi_throw_range_error(env, nullptr, "fewer scalars than the call has terms");
     return nullptr;
   }
@@ -714,12 +751,14 @@ napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv) 
   j->bases = h;
   j->n = m;
   j->scalar_bits = has_bits ? (uint32_t)bits : 0;
-  j->scalar_type = ty->type;
+  j->scalar_type = ty ? ty->type : 0;
+  j->scalar_field = wt ? wt->field : 0;
   j->subset = subset;
   j->indexed = has_idx;
   j->first = (uint64_t)first;
   if (has_idx) j->indices.assign(ix, ix + ilen);
-  if (sshared) {
+  // (a wide vector wants 8-byte alignment, which a Uint8Array view need not have: then a copy)
+  if (sshared && !(wt && (reinterpret_cast<uintptr_t>(sc) & 7))) {
     j->p_scalars = static_cast<const uint32_t*>(sc);
     if (napi_create_reference(env, argv[1], 1, &j->ref_scalars) != napi_ok) {
       delete j;
@@ -727,7 +766,7 @@ napi_value ComputeMsmPreparedTyped(napi_env env, size_t argc, napi_value* argv) 
       return nullptr;
     }
   } else {  // detachable memory: the worker reads a copy (the vector's storage is aligned for any element)
-    const size_t bytes = (m * ty->bits + 7) / 8;
+    const size_t bytes = ((size_t)m * ebits + 7) / 8;
     j->scalars.resize((bytes + 3) / 4 + 1);
     memcpy(j->scalars.data(), sc, bytes);
   }

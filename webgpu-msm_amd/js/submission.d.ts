@@ -30,7 +30,11 @@ export declare function prepare_bases(
 // values included (Int8Array for "i8", Uint8Array for "u8" and for a "bit" bitmap, .. BigInt64Array for
 // "i64", BigUint64Array for "u64"; another class throws TypeError); scalarBits then bounds the
 // magnitude (|v| < 2^b, b up to the element's width) and `m` counts a bitmap's terms.
-export type ScalarType = "bit" | "u8" | "i8" | "u16" | "i16" | "u32" | "i32" | "u64" | "i64";
+// The wide names take little-endian elements of 16 bytes ("u128"; "i128", two's complement) or 32 bytes
+// ("u256"; "fr_mont", an ark-ed-on-bls12-377 Fr as it lies in memory, Montgomery form) as a
+// BigUint64Array, Uint32Array or Uint8Array that holds exactly the call's terms.
+export type ScalarType =
+  | "bit" | "u8" | "i8" | "u16" | "i16" | "u32" | "i32" | "u64" | "i64" | "u128" | "i128" | "u256" | "fr_mont";
 export type NativeScalars =
   | Uint8Array | Int8Array | Uint16Array | Int16Array | Uint32Array | Int32Array | BigUint64Array | BigInt64Array;
 export type BasesSubset = {

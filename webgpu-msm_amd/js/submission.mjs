@@ -230,6 +230,11 @@ export function prepare_bases(baseAffinePoints, options) {
 // "u64" BigUint64Array, and "bit" a Uint8Array bitmap (scalar i is bit i & 7 of byte i >> 3) whose term
 // count is { m }, else indices.length, the handle's n, or 8 per byte.  Another class throws TypeError.
 // scalarBits = b then bounds the magnitude, |v| < 2^b with b up to the element's width.
+// The wide names (msm_opts_typed.scalar_field, MSM_FLAG_SCALAR_FIELD) -- "u128", "i128" (two's
+// complement), "u256" and "fr_mont" (an arkworks Fr of ark-ed-on-bls12-377 as it lies in memory:
+// Montgomery form) -- take little-endian elements of 16 / 32 bytes as a BigUint64Array, Uint32Array or
+// Uint8Array that holds exactly the call's terms; another length rejects.
+const WIDE_BYTES = { u128: 16, i128: 16, u256: 32, fr_mont: 32 };
 const NATIVE_CLASS = {
   bit: Uint8Array, u8: Uint8Array, i8: Int8Array, u16: Uint16Array, i16: Int16Array, u32: Uint32Array, i32: Int32Array,
   u64: BigUint64Array, i64: BigInt64Array,
@@ -243,9 +248,15 @@ export const compute_msm_prepared = async (handle, scalars, subset) => {
     if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("subset.indices: a Uint32Array");
     if (first !== undefined && !(Number.isSafeInteger(first) && first >= 0)) throw new RangeError("subset.first: a non-negative integer");
     if (scalarType !== undefined) {
-      const cls = NATIVE_CLASS[scalarType];
-      if (!cls) throw new TypeError("subset.scalarType: one of " + Object.keys(NATIVE_CLASS).join(", "));
-      if (!(scalars instanceof cls)) throw new TypeError(`subset.scalarType ${scalarType}: scalars must be a ${cls.name}`);
+      const cls = NATIVE_CLASS[scalarType], wide = WIDE_BYTES[scalarType];
+      if (!cls && !wide)
+        throw new TypeError("subset.scalarType: one of " + Object.keys(NATIVE_CLASS).concat(Object.keys(WIDE_BYTES)).join(", "));
+      if (cls && !(scalars instanceof cls)) throw new TypeError(`subset.scalarType ${scalarType}: scalars must be a ${cls.name}`);
+      if (wide) {
+        if (!(scalars instanceof BigUint64Array || scalars instanceof Uint32Array || scalars instanceof Uint8Array))
+          throw new TypeError(`subset.scalarType ${scalarType}: scalars must be a BigUint64Array, Uint32Array or Uint8Array`);
+        if (scalars.byteLength % wide) throw new RangeError(`subset.scalarType ${scalarType}: ${wide} bytes per scalar`);
+      }
       if (m !== undefined && !(Number.isSafeInteger(m) && m >= 0)) throw new RangeError("subset.m: a non-negative integer");
       // (an options object is a subset call, as above: the prefix of as many bases as scalars)
       const result = await addon.computeMsmPrepared(handle.id, scalars, first === undefined ? 0 : first, indices,

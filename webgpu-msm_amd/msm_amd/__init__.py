@@ -29,6 +29,7 @@ __all__ = [
     "window_count",
     "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P", "Bases", "BasesInfo",
     "MsmOptsTyped", "MSM_FLAG_SCALAR_TYPE", "SCALAR_TYPES", "scalars_to_native",
+    "MSM_FLAG_SCALAR_FIELD", "WIDE_TYPES", "FR_MODULUS", "scalars_to_wide",
 ]
 
 P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
@@ -57,8 +58,9 @@ class MsmOpts(ctypes.Structure):
 
 class MsmOptsTyped(MsmOpts):
     """include/msm.h msm_opts_typed: a msm_opts followed by scalar_type (MSM_SCALAR_*), read by libmsm
-    only when flags has MSM_FLAG_SCALAR_TYPE -- the shorter MsmOpts keeps its 40 bytes."""
-    _fields_ = [("scalar_type", ctypes.c_uint32)]
+    only when flags has MSM_FLAG_SCALAR_TYPE, and scalar_field (MSM_FIELD_*), read only when flags has
+    MSM_FLAG_SCALAR_FIELD -- the shorter MsmOpts keeps its 40 bytes."""
+    _fields_ = [("scalar_type", ctypes.c_uint32), ("scalar_field", ctypes.c_uint32)]
 
 
 class MsmProfile(ctypes.Structure):
@@ -95,6 +97,7 @@ MSM_FLAG_WINDOWS = 4  # msm_opts carries a window range
 MSM_FLAG_HALF_WINDOWS = 8  # with MSM_FLAG_WINDOWS: the range counts half windows
 MSM_FLAG_SCALAR_BITS = 16  # msm_opts carries the scalars' width (narrow scalars, Bases.compute* only)
 MSM_FLAG_SCALAR_TYPE = 32  # the options are a MsmOptsTyped: native integer scalars (Bases.compute* only)
+MSM_FLAG_SCALAR_FIELD = 64  # MsmOptsTyped.scalar_field is set: wide native scalars (Bases.compute* only)
 MSM_MAX_DEVICES = 16
 # include/msm.h MSM_SCALAR_*: name -> (value, numpy dtype of the array, element bits e)
 SCALAR_TYPES = {
@@ -103,6 +106,11 @@ SCALAR_TYPES = {
     "u64": (5, np.dtype(np.uint64), 64), "i8": (6, np.dtype(np.int8), 8), "i16": (7, np.dtype(np.int16), 16),
     "i32": (8, np.dtype(np.int32), 32), "i64": (9, np.dtype(np.int64), 64),
 }
+# include/msm.h MSM_FIELD_*: name -> (value, element bits e).  Little-endian elements of e / 8 bytes: 128-bit
+# integers, 256-bit integers (arkworks BigInt<4>) and Fr of ark-ed-on-bls12-377 in Montgomery form.
+WIDE_TYPES = {"u128": (1, 128), "i128": (2, 128), "u256": (3, 256), "fr_mont": (4, 256)}
+# r, the order of the curve's prime subgroup: the modulus of the scalar field Fr (251 bits)
+FR_MODULUS = 0x04aad957a68b2955982d1347970dec005293a3afc43c8afeb95aee9ac33fd9ff
 MSM_STREAM_NULL = 1  # hip_stream value: order after the null (legacy default) stream
 
 
@@ -182,6 +190,8 @@ def load() -> ctypes.CDLL:
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_narrow_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_native_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_wide_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_fr_from_mont": ([u32p, sz, u32p, ctypes.c_void_p], ctypes.c_int),
         "msm_test_dense_plan": ([sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, u32p],
                                 ctypes.c_int),
         "msm_test_dense_segments": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
@@ -264,9 +274,13 @@ def _opts(window_size: Optional[int], run_length: Optional[int] = None, device: 
     2w is window w's lower-half buckets, 2w + 1 its upper half).  `scalar_bits` = b declares narrow
     scalars of ceil(b / 32) words (MSM_FLAG_SCALAR_BITS; the Bases.compute* calls only).
     `scalar_type` (a SCALAR_TYPES name, or a raw MSM_SCALAR_* value) declares native integer scalars
-    (MSM_FLAG_SCALAR_TYPE; the same calls only): the options are then a MsmOptsTyped."""
+    (MSM_FLAG_SCALAR_TYPE; the same calls only): the options are then a MsmOptsTyped.  A WIDE_TYPES
+    name declares wide scalars instead (MSM_FLAG_SCALAR_FIELD, MsmOptsTyped.scalar_field)."""
     if scalar_type is None:
         o = MsmOpts(int(window_size or 0), int(run_length or 0), int(device), int(flags))
+    elif isinstance(scalar_type, str) and scalar_type in WIDE_TYPES:
+        o = MsmOptsTyped(int(window_size or 0), int(run_length or 0), int(device), int(flags) | MSM_FLAG_SCALAR_FIELD)
+        o.scalar_field = WIDE_TYPES[scalar_type][0]
     else:
         o = MsmOptsTyped(int(window_size or 0), int(run_length or 0), int(device), int(flags) | MSM_FLAG_SCALAR_TYPE)
         o.scalar_type = SCALAR_TYPES[scalar_type][0] if isinstance(scalar_type, str) else int(scalar_type)
@@ -382,6 +396,53 @@ def scalars_to_native(values, scalar_type: str) -> np.ndarray:
     return np.array(vals, dtype=dt).reshape(-1)
 
 
+def scalars_to_wide(values, scalar_type: str) -> np.ndarray:
+    """Python ints -> the array a Bases.compute*(scalar_type=<a WIDE_TYPES name>) call takes: uint64
+    [n, e / 64], little-endian limbs (least significant first).  "i128" takes negative values (two's
+    complement); "fr_mont" takes v < r and encodes the Montgomery form v 2^256 mod r, the memory of an
+    arkworks Fr.  A value the type cannot hold raises ValueError."""
+    if scalar_type not in WIDE_TYPES:
+        raise ValueError(f"unknown wide scalar type {scalar_type!r}")
+    e = WIDE_TYPES[scalar_type][1]
+    vals = [int(v) for v in values]
+    lo, hi = (-(1 << 127), 1 << 127) if scalar_type == "i128" else (0, FR_MODULUS if scalar_type == "fr_mont" else 1 << e)
+    if any(not lo <= v < hi for v in vals):
+        raise ValueError(f"a scalar does not fit {scalar_type}")
+    if scalar_type == "fr_mont":
+        vals = [(v << 256) % FR_MODULUS for v in vals]
+    buf = b"".join((v & ((1 << e) - 1)).to_bytes(e // 8, "little") for v in vals)
+    return np.frombuffer(buf, dtype="<u8").astype(np.uint64).reshape(-1, e // 64)
+
+
+class WideArrayError(TypeError, ValueError):
+    """An array that a wide scalar type does not take.  A TypeError; also a ValueError, which is what these
+    type names raised with any array while they were unknown."""
+
+
+def _wide_check(arr, name: str, where: str = "") -> None:
+    """The arrays a wide type takes: C-contiguous [n, e / 64] 64-bit, [n, e / 32] uint32 or [n, e / 8] uint8
+    (numpy: uint64 / uint32 / uint8; torch: int64 / uint8).  TypeError for anything else."""
+    e = WIDE_TYPES[name][1]
+    dt = str(getattr(arr, "dtype", None))
+    size = {"uint64": 8, "uint32": 4, "uint8": 1, "torch.int64": 8, "torch.uint8": 1}.get(dt)
+    shape = tuple(getattr(arr, "shape", ()))
+    if size is None or len(shape) != 2 or shape[1] * size * 8 != e:
+        raise WideArrayError(f"scalar_type {name!r} takes [n, {e // 64}] 64-bit, [n, {e // 32}] uint32 or [n, {e // 8}] uint8 "
+                        f"arrays, not {dt} {shape}{where}")
+    contiguous = arr.flags["C_CONTIGUOUS"] if isinstance(arr, np.ndarray) else arr.is_contiguous()
+    if not contiguous:
+        raise WideArrayError(f"scalar_type {name!r} takes C-contiguous arrays{where}")
+
+
+def _wide_device(t, name) -> None:
+    """A device vector of a wide type: a tensor is checked as _wide_check does and must be on a device; a
+    raw device pointer is taken as it is."""
+    if name in WIDE_TYPES and not isinstance(t, int):
+        if isinstance(t, np.ndarray) or not getattr(t, "is_cuda", False):
+            raise WideArrayError(f"scalar_type {name!r}: the device entries take a device tensor or a raw pointer")
+        _wide_check(t, name)
+
+
 _TORCH_NATIVE = {"torch.bool": "bool", "torch.uint8": "u8", "torch.int8": "i8", "torch.int16": "i16",
                  "torch.int32": "i32", "torch.int64": "i64", "torch.uint16": "u16", "torch.uint32": "u32",
                  "torch.uint64": "u64"}
@@ -394,6 +455,10 @@ def _native_type(scalars, scalar_type, scalar_bits):
     if scalar_type is None:
         return None, scalar_bits
     if scalar_type != "native":
+        if scalar_type in WIDE_TYPES:  # ("native" never infers one: a [n, 4] uint64 array is ambiguous)
+            if scalars is not None and not isinstance(scalars, (int, list, tuple)):
+                _wide_check(scalars, scalar_type)
+            return scalar_type, scalar_bits
         if scalar_type not in SCALAR_TYPES:
             raise ValueError(f"unknown scalar type {scalar_type!r}")
         return scalar_type, scalar_bits
@@ -412,7 +477,22 @@ def _native_type(scalars, scalar_type, scalar_bits):
 
 def _native_host(scalars, name: str) -> np.ndarray:
     """A host vector of a native type as a flat contiguous numpy array of the type's dtype: typed
-    arrays (and CPU torch tensors) pass through uncopied when contiguous; ints are packed."""
+    arrays (and CPU torch tensors) pass through uncopied when contiguous; ints are packed.
+    A wide type's vector stays [n, k] (its first dimension counts the scalars) and is copied only where
+    its memory is not 8-byte aligned."""
+    if name in WIDE_TYPES:
+        if hasattr(scalars, "numpy") and not isinstance(scalars, np.ndarray):
+            _wide_check(scalars, name)
+            scalars = scalars.numpy()  # a CPU tensor: shares its memory (torch has no uint64: int64 limbs)
+            scalars = scalars.view(np.uint64) if scalars.dtype == np.int64 else scalars
+        if not isinstance(scalars, np.ndarray):
+            return scalars_to_wide(scalars, name)
+        _wide_check(scalars, name)
+        if scalars.ctypes.data & 7:
+            buf = np.empty(scalars.nbytes // 8, dtype=np.uint64)
+            buf.view(np.uint8)[:] = scalars.reshape(-1).view(np.uint8)
+            scalars = buf.view(scalars.dtype).reshape(scalars.shape)
+        return scalars
     dt = SCALAR_TYPES[name][1]
     if hasattr(scalars, "numpy") and not isinstance(scalars, np.ndarray):
         scalars = scalars.numpy()  # a CPU tensor: shares its memory
@@ -674,6 +754,9 @@ class Bases:
     # SCALAR_TYPES name -- the vector is then a flat array of that integer type, negative values
     # included, or for "bit" a little-order bitmap -- or "native", the type of the array's own numpy /
     # torch dtype (bool: "u8" with scalar_bits = 1).  scalar_bits then bounds the magnitude, |v| < 2^b.
+    # A WIDE_TYPES name (include/msm.h MSM_FLAG_SCALAR_FIELD) takes little-endian 128- / 256-bit elements:
+    # [n, e / 64] uint64 (torch: int64), [n, e / 32] uint32 or [n, e / 8] uint8, C-contiguous; "fr_mont" is
+    # Fr in Montgomery form (scalars_to_wide packs ints).  "native" never infers a wide type.
 
     def compute(self, scalars, window_size: Optional[int] = None, run_length: Optional[int] = None,
                 scalar_bits: Optional[int] = None, scalar_type=None) -> Tuple[int, int]:
@@ -698,6 +781,7 @@ class Bases:
                        stream: int = 0, scalar_bits: Optional[int] = None, scalar_type=None) -> Tuple[int, int]:
         """One MSM of device-resident scalars (a torch tensor or a raw device pointer, n x 8 words)."""
         ty, scalar_bits = _native_type(d_scalars, scalar_type, scalar_bits)
+        _wide_device(d_scalars, ty)
         o, op = _out(16)
         _check(load().msm_bases_compute_device(self._h or None, _dev_ptr(d_scalars),
                                                _opts(window_size, run_length, scalar_bits=scalar_bits,
@@ -732,6 +816,8 @@ class Bases:
         """The same with device-resident scalar vectors."""
         count = len(scalars_list)
         ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
+        for t in scalars_list:
+            _wide_device(t, ty)
         ss = (ctypes.c_void_p * max(count, 1))(*[_dev_ptr(t) for t in scalars_list])
         o, op = _out(16 * max(count, 1))
         _check(load().msm_bases_compute_many_device(self._h or None, ctypes.cast(ss, ctypes.c_void_p), count,
@@ -812,6 +898,7 @@ class Bases:
         """The same with device-resident scalars (a torch tensor [m, 8], or a raw device pointer with
         `m`) and, in indexed form, a device-resident int32/uint32 index tensor (or pointer)."""
         ty, scalar_bits = _native_type(d_scalars, scalar_type, scalar_bits)
+        _wide_device(d_scalars, ty)
         if ty == "bit" and m is None:
             raise ValueError("a bit vector's length is not its byte count: pass m")
         m = len(d_scalars) if m is None else int(m)
@@ -860,6 +947,8 @@ class Bases:
         """The same with device-resident scalar (and index) vectors."""
         count = len(scalars_list)
         ty, scalar_bits = _native_type(_first(scalars_list), scalar_type, scalar_bits)
+        for t in scalars_list:
+            _wide_device(t, ty)
         if ty == "bit" and m is None:
             raise ValueError("a bit vector's length is not its byte count: pass m")
         if m is None:
@@ -1136,6 +1225,32 @@ def _test_narrow_plan(n: int, scalar_bits: int, window_size: int = 0) -> dict:
     _check(load().msm_test_narrow_plan(n, int(scalar_bits), int(window_size),
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_narrow_plan")
     return dict(zip(("c", "windows", "q", "nhi", "words", "packed"), (int(v) for v in out)))
+
+
+def _test_wide_plan(n: int, scalar_type, scalar_bits: int, window_size: int = 0) -> dict:
+    """The plan of a wide-type launch (msm_test_wide_plan; no GPU needed): _test_narrow_plan's fields for
+    scalar_bits, plus vector_bytes and region_bytes.  `scalar_type` is a WIDE_TYPES name or a raw
+    MSM_FIELD_* value."""
+    out = np.zeros(8, dtype=np.uint32)
+    ty = WIDE_TYPES[scalar_type][0] if isinstance(scalar_type, str) else int(scalar_type)
+    _check(load().msm_test_wide_plan(n, ty, int(scalar_bits), int(window_size),
+                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_wide_plan")
+    return dict(zip(("c", "windows", "q", "nhi", "words", "packed", "vector_bytes", "region_bytes"),
+                    (int(v) for v in out)))
+
+
+def _test_fr_from_mont(values) -> Tuple[list, list]:
+    """csrc/fr.cuh on the host (msm_test_fr_from_mont; no GPU needed): for every 256-bit int a, whether a < r
+    and a 2^-256 mod r.  Returns (decoded ints, canonical flags)."""
+    vals = [int(v) for v in values]
+    buf = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype="<u4").astype(np.uint32)
+    out = np.zeros_like(buf)
+    ok = np.zeros(len(vals), dtype=np.uint8)
+    _check(load().msm_test_fr_from_mont(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(vals),
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                        ok.ctypes.data_as(ctypes.c_void_p)), "msm_test_fr_from_mont")
+    raw = out.astype("<u4").tobytes()
+    return [int.from_bytes(raw[32 * i: 32 * i + 32], "little") for i in range(len(vals))], [bool(x) for x in ok]
 
 
 def _test_native_plan(n: int, scalar_type, scalar_bits: int, window_size: int = 0) -> dict:
