@@ -255,6 +255,7 @@ struct Slot {
   bool acc_timed = false;
   bool stagger = false;  // this slot's pipelined launches are staggered (stagger_launches)
   bool pipelined = false;  // a launch of a pipelined run (another launch in flight beside it)
+  uint32_t skew_seen = 0;  // wait_slot's latch: the skewed workgroups of the slot's last launch (msm_test_acc_state)
 };
 constexpr int NSLOT = 4;      // at most this many launches in flight (one HIP stream each)
 constexpr int NCHUNK_EV = 8;  // events marking uploaded point chunks

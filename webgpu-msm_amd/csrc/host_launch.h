@@ -675,6 +675,7 @@ int wait_slot(DevCtx* c, int si, uint32_t* total_out = nullptr) {
   const uint32_t* h = reinterpret_cast<const uint32_t*>(sl.h_out.p);
   const uint32_t err = h[outb / 4];
   if (total_out) *total_out = h[outb / 4 + 1];
+  sl.skew_seen = h[outb / 4 + 2];
   if (h[outb / 4 + 2]) {
     // only the second k_bucket_reduce_2 clears the skew list and the lead flag: if the re-run
     // cannot be enqueued or does not complete, clear them here, or the slot's next MSM would append

@@ -67,6 +67,29 @@ int guard_each_ctx(int device, F&& fn) {
   return MSM_OK;
 }
 
+// A device field element's 9 limbs (value sum_k v_k 2^(29 k), whatever representative the kernel
+// stored) as an Fq, by Horner over hostfield's loader and multiply.  The device's Montgomery factor
+// 2^261 stays in: it cancels in an affine ratio.
+msmh::Fq fq_from_limbs29(const uint32_t* v) {
+  const uint64_t radix[4] = {1ull << 29, 0, 0, 0};
+  const msmh::Fq r29 = msmh::fq_from_std(radix);
+  msmh::Fq acc = msmh::fq_zero();
+  for (int k = 8; k >= 0; k--) {
+    const uint64_t limb[4] = {v[k], 0, 0, 0};
+    acc = msmh::fq_add(msmh::fq_mul(acc, r29), msmh::fq_from_std(limb));
+  }
+  return acc;
+}
+// A stored extended point (store_pt: X | Y | T | Z, 9 limbs each) -> affine x | y, 8 BE words each,
+// through the tail's inversion (pt_to_affine_std).
+void limbs_point_to_xy_be(const uint32_t* rec, uint32_t* xy_be) {
+  msmh::Pt p{fq_from_limbs29(rec), fq_from_limbs29(rec + 9), fq_from_limbs29(rec + 18), fq_from_limbs29(rec + 27)};
+  uint64_t x[4], y[4];
+  msmh::pt_to_affine_std(p, x, y);
+  msmh::std_to_be_words(x, xy_be);
+  msmh::std_to_be_words(y, xy_be + 8);
+}
+
 }  // namespace
 
 extern "C" {
@@ -599,6 +622,63 @@ int msm_test_split_scalars(const uint32_t* scalars, size_t n, uint32_t k, uint32
                      S);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpy(out, dout.p, (size_t)k * n * 32, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// ---- the run accumulation's state (tests/test_gpu_acc_chains.py, tests/_acc_model.py) -------------
+// What the last MSM of the default device's lone-MSM slot (slot 0) left in that slot's workspace, read
+// back after the call: nothing is launched.  info = {M, K, nkeys, runs, workgroups, the skewed
+// workgroups' count, whether the launch took the second (PART_JOIN) pass, c}; the count is wait_slot's
+// latch of the flag word, taken before the final reduction clears skew_list[0] (profiling mode 1 runs
+// the joins in line: no second pass, and the count stays 0).  Every array pointer
+// may be null (call once for info, then with buffers): bucket_start [nkeys + 1], run_key [runs],
+// sorted_entry [M], cross_key and lead_open [workgroups], skewed [count] (the list's order is the
+// launch's own).  key_xy [nk][16] and wg_xy [nw][16] receive the affine x | y (BE words) of
+// buckets[keys[i]] and lead_val[wgs[i]], converted on the host (limbs_point_to_xy_be); a slot the
+// launch did not write comes back as whatever it holds.  MSM_ERR_INVALID_ARG unless the slot's last
+// launch was one MSM through k_accumulate.
+int msm_test_acc_state(uint32_t info[8], uint32_t* bucket_start, uint32_t* run_key, uint32_t* sorted_entry,
+                       uint32_t* cross_key, uint32_t* lead_open, uint32_t* skewed, const uint32_t* keys, size_t nk,
+                       uint32_t* key_xy, const uint32_t* wgs, size_t nw, uint32_t* wg_xy) {
+  if (!info || (nk && (!keys || !key_xy)) || (nw && (!wgs || !wg_xy))) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  Slot& sl = c->slot[0];
+  const Plan& pl = sl.pl;
+  Workspace& w = sl.ws;
+  if (pl.d.nm != 1 || pl.dense || !pl.K || !sl.h_out.p || !w.bucket_start.p || !sl.stream) return MSM_ERR_INVALID_ARG;
+  HIPCHECK(hipStreamSynchronize(sl.stream));
+  const size_t outb = (size_t)pl.d.W * pl.nterms * 32 * 4;
+  const uint32_t M = reinterpret_cast<const uint32_t*>(sl.h_out.p)[outb / 4 + 1];
+  const uint32_t nkeys = pl.d.W * pl.d.B;
+  const uint32_t runs = (M + pl.K - 1) / pl.K, nwg = (runs + ACC_THREADS - 1) / ACC_THREADS;
+  if (M > pl.Mmax || runs > pl.runs_max || sl.skew_seen > nwg) return MSM_ERR_INVALID_ARG;
+  const uint32_t v[8] = {M, pl.K, nkeys, runs, nwg, sl.skew_seen, sl.skew_seen ? 1u : 0u, pl.d.c};
+  memcpy(info, v, sizeof v);
+  auto fetch = [](uint32_t* dst, const Buf& b, size_t first, size_t words) -> hipError_t {
+    if (!dst || !words) return hipSuccess;
+    if (!b.p || (first + words) * 4 > b.cap) return hipErrorInvalidValue;
+    return hipMemcpy(dst, static_cast<const uint32_t*>(b.p) + first, words * 4, hipMemcpyDeviceToHost);
+  };
+  HIPCHECK(fetch(bucket_start, w.bucket_start, 0, (size_t)nkeys + 1));
+  HIPCHECK(fetch(run_key, w.run_key, 0, runs));
+  HIPCHECK(fetch(sorted_entry, w.sorted_entry, 0, M));
+  HIPCHECK(fetch(cross_key, w.cross_key, 0, nwg));
+  HIPCHECK(fetch(lead_open, w.lead_open, 0, nwg));
+  HIPCHECK(fetch(skewed, w.skew_list, 1, sl.skew_seen));
+  uint32_t rec[PT_WORDS];
+  for (size_t i = 0; i < nk; i++) {
+    if (keys[i] >= nkeys) return MSM_ERR_INVALID_ARG;
+    HIPCHECK(fetch(rec, w.buckets, (size_t)keys[i] * PT_WORDS, PT_WORDS));
+    limbs_point_to_xy_be(rec, key_xy + i * 16);
+  }
+  for (size_t i = 0; i < nw; i++) {
+    if (wgs[i] >= nwg) return MSM_ERR_INVALID_ARG;
+    HIPCHECK(fetch(rec, w.lead_val, (size_t)wgs[i] * PT_WORDS, PT_WORDS));
+    limbs_point_to_xy_be(rec, wg_xy + i * 16);
+  }
   return MSM_OK;
 }
 

@@ -1813,6 +1813,10 @@ __device__ __forceinline__ void acc_tile(uint32_t wg, uint32_t (*sh_head)[PT_WOR
   // leaves the workgroup, are deferred to k_chain_join's logarithmic scan; otherwise every chain
   // has at most two pass heads and is joined right here with at most three adds.  (The top
   // window of canonical scalars holds ~110 entries per bucket, so two-pass chains are common.)
+  // (The two lane-0 terms ask for a pass head in a workgroup of one or two live runs.  Only the
+  // list's last workgroup has so few, and its last run never continues, so neither can fire:
+  // tests/_acc_model.py UNREACHABLE.  A lead chain that leaves a full workgroup is 256 pass heads
+  // and takes the first term.)
   const uint32_t hk = sh_hkey[lt];
   auto is_pass = [&](uint32_t r) {
     const uint32_t k = sh_hkey[r];
@@ -1958,8 +1962,8 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) k_chain_join(const uin
 
 // Chains leads that run through whole workgroups (a bucket spanning three or more workgroups):
 // segmented suffix scan lead_val[g] <- lead_val[g] + lead_val[g+1] + ... while lead_open.  One
-// workgroup walks the leads from the end in tiles of LS_THREADS; a no-op unless k_accumulate saw
-// an open lead.
+// workgroup walks the leads from the end in tiles of LS_THREADS; a no-op unless k_chain_join found
+// an open lead (lead_flag).
 constexpr uint32_t LS_THREADS = 512;
 extern "C" __global__ void __launch_bounds__(LS_THREADS) k_lead_scan(uint32_t* __restrict__ lead_val,
                                                                      const uint32_t* __restrict__ lead_open,
@@ -2502,7 +2506,8 @@ extern "C" __global__ void __launch_bounds__(RED2_THREADS) k_bucket_reduce_2(con
       const bool skew = skew_list[0] != 0 || *lead_flag != 0;
       out_host[tail] = *err;
       out_host[tail + 1] = *total;
-      out_host[tail + 2] = (skew && !final_pass) ? 1u : 0u;
+      // (nonzero: run the joins; the skewed workgroups' count where there is one, for msm_test_acc_state)
+      out_host[tail + 2] = (skew && !final_pass) ? max(skew_list[0], 1u) : 0u;
       *err = 0;  // flags start the next MSM cleared (no memset node in the graph)
       if (final_pass || !skew) {
         *lead_flag = 0;
@@ -2642,7 +2647,7 @@ __device__ __forceinline__ void red2_flags(uint32_t nwindows_terms, uint32_t* __
   const bool skew = skew_list[0] != 0 || *lead_flag != 0;
   out_host[tail] = *err;
   out_host[tail + 1] = *total;
-  out_host[tail + 2] = (skew && !final_pass) ? 1u : 0u;
+  out_host[tail + 2] = (skew && !final_pass) ? max(skew_list[0], 1u) : 0u;
   *err = 0;
   if (final_pass || !skew) {
     *lead_flag = 0;

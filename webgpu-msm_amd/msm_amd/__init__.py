@@ -195,6 +195,7 @@ def load() -> ctypes.CDLL:
         "msm_test_dense_plan": ([sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, u32p],
                                 ctypes.c_int),
         "msm_test_dense_segments": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
+        "msm_test_acc_state": ([u32p, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp], ctypes.c_int),
         "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
@@ -1287,6 +1288,34 @@ def _test_dense_segments(bucket_start, S: int) -> Tuple[np.ndarray, np.ndarray]:
     unit, unit_ = _out(int(bs[-1]) // int(S) + nkeys)
     _check(load().msm_test_dense_segments(_ptr(bs), nkeys, int(S), seg_, unit_), "msm_test_dense_segments")
     return seg, unit
+
+
+def _test_acc_state(keys=(), workgroups=()) -> dict:
+    """What the last lone MSM of the default device left in its slot's workspace (msm_test_acc_state, test
+    hook; tests/test_gpu_acc_chains.py): M, K, nkeys, runs, workgroups, second_pass, c; bucket_start
+    [nkeys + 1], run_key [runs], sorted_entry [M], cross_key and lead_open [workgroups], the skewed
+    workgroups (sorted), and the affine (x, y) of buckets[key] for `keys` and of lead_val[wg] for
+    `workgroups`, as dicts."""
+    L = load()
+    info, info_ = _out(8)
+    _check(L.msm_test_acc_state(info_, None, None, None, None, None, None, None, 0, None, None, 0, None),
+           "msm_test_acc_state")
+    M, K, nkeys, runs, nwg, nskew, second, c = (int(v) for v in info)
+    ks = np.ascontiguousarray(_u32(list(keys)).reshape(-1))
+    ws = np.ascontiguousarray(_u32(list(workgroups)).reshape(-1))
+    bs, rk, se = np.zeros(nkeys + 1, np.uint32), np.zeros(max(runs, 1), np.uint32), np.zeros(max(M, 1), np.uint32)
+    ck, lo = np.zeros(max(nwg, 1), np.uint32), np.zeros(max(nwg, 1), np.uint32)
+    sk = np.zeros(max(nskew, 1), np.uint32)
+    kxy, wxy = np.zeros((max(len(ks), 1), 16), np.uint32), np.zeros((max(len(ws), 1), 16), np.uint32)
+    _check(L.msm_test_acc_state(info_, _ptr(bs), _ptr(rk), _ptr(se), _ptr(ck), _ptr(lo), _ptr(sk), _ptr(ks), len(ks),
+                                _ptr(kxy), _ptr(ws), len(ws), _ptr(wxy)), "msm_test_acc_state")
+    if [int(v) for v in info] != [M, K, nkeys, runs, nwg, nskew, second, c]:
+        raise RuntimeError("msm_test_acc_state: the slot changed between the two reads")
+    return {"M": M, "K": K, "nkeys": nkeys, "runs": runs, "workgroups": nwg, "second_pass": bool(second), "c": c,
+            "bucket_start": bs, "run_key": rk[:runs], "sorted_entry": se[:M], "cross_key": ck[:nwg],
+            "lead_open": lo[:nwg], "skewed": sorted(int(v) for v in sk[:nskew]),
+            "buckets": {int(k): _xy(kxy[i]) for i, k in enumerate(ks)},
+            "lead_val": {int(g): _xy(wxy[i]) for i, g in enumerate(ws)}}
 
 
 def _test_subset_plan(n_handle: int, levels: int, window_size: int, first: int, m: int, indexed: bool) -> dict:
