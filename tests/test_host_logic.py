@@ -195,7 +195,8 @@ def _host_mont_words(v):
 def test_lone_msm_tail_threads_agree(n):
     """The window-parallel tail of a lone MSM (TailCrew: helper threads sum each window's terms,
     the caller runs the outer Horner) equals the one-thread Horner (which every GPU parity test
-    checks end to end), identity terms included."""
+    checks end to end, and tests/test_red_model.py::test_tail_value against the Python oracle for
+    every chunk length), identity terms included."""
     L = M.load()
     words = L.msm_test_tail_words(n)
     rng = np.random.default_rng(n)

@@ -330,6 +330,18 @@ uint32_t dense_entries(uint64_t Mmax, uint32_t nkeys, const DevShape& sh) {
   return 64;
 }
 
+// The reduction's fields of a plan whose geometry is set, for chunks of L buckets (finish_plan; the
+// test hooks of host_test_hooks.h give an L of their own).
+void plan_chunks(Plan* pl, uint32_t L) {
+  pl->L = L;
+  pl->nchunks = (pl->d.B + L - 1) / L;
+  // every k_bucket_reduce_2 workgroup sums at most pow2ceil(nchunks)/2 points (the R_k terms' size)
+  pl->nv = pl->nchunks >= 2 ? 2 : 1;
+  uint32_t cbits = 0;
+  while ((1u << cbits) < pl->nchunks) cbits++;
+  pl->nterms = pl->nv + cbits;
+}
+
 // The launch-shape fields that follow from the geometry d.
 int finish_plan(const MsmDims& d, const msm_opts* o, const DevShape& sh, Plan* pl, bool pipelined) {
   const size_t n = d.n;
@@ -342,13 +354,7 @@ int finish_plan(const MsmDims& d, const msm_opts* o, const DevShape& sh, Plan* p
     pl->dense_E = dense_entries((uint64_t)d.W * n, d.W * d.B, sh);
     pl->dense_units = (uint32_t)dense_unit_bound((uint64_t)d.W * n, d.W * d.B, pl->dense_E);
   }
-  pl->L = bucket_reduce_L(d, sh);
-  pl->nchunks = (d.B + pl->L - 1) / pl->L;
-  // every k_bucket_reduce_2 workgroup sums at most pow2ceil(nchunks)/2 points (the R_k terms' size)
-  pl->nv = pl->nchunks >= 2 ? 2 : 1;
-  uint32_t cbits = 0;
-  while ((1u << cbits) < pl->nchunks) cbits++;
-  pl->nterms = pl->nv + cbits;
+  plan_chunks(pl, bucket_reduce_L(d, sh));
   pl->Mmax = (size_t)d.W * n;
   pl->runs_max = (pl->Mmax + pl->K - 1) / pl->K + 1;
   if (pl->Mmax >= (1ull << 31)) return MSM_ERR_INVALID_ARG;

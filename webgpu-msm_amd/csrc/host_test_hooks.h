@@ -682,6 +682,147 @@ int msm_test_acc_state(uint32_t info[8], uint32_t* bucket_start, uint32_t* run_k
   return MSM_OK;
 }
 
+// ---- the bucket reduction's state and maps (tests/test_gpu_red_state.py, tests/_red_model.py) ------
+// Whether L is a chunk length the reduction is instantiated for (RED1_LS, or 4).
+static bool red_l_known(uint32_t L) {
+  if (L == 4) return true;
+  for (uint32_t l : RED1_LS)
+    if (l == L) return true;
+  return false;
+}
+
+// What the reduction of the last lone MSM of the default device's slot 0 left behind, read back after
+// the call as msm_test_acc_state does: nothing is launched, and every array may be null (with its
+// count 0).  info = {L, nchunks, ngroups, nv, nterms, W, B, the second stage that ran (0: k_red2_groups
+// + k_red2_terms, 1: k_bucket_reduce_2, 2: k_bucket_reduce_1g + k_red2_terms), whether the first stage
+// ran on lane pairs, RG_OUT, c, the widest window, then three words of a bit mask of the empty
+// windows (bit w of word w / 32), 0, 0}.  chunks[i] = w * nchunks + c -> u_xy / t_xy [i][16], the affine
+// x | y (BE words, limbs_point_to_xy_be) of red_U / red_T; gpts[i] = (w * ngroups + g) * RG_OUT + idx
+// -> g_xy [i][16] of red_G; terms[i] = w * nterms + t -> term_xy [i][16] of the terms in h_out (host
+// Montgomery X | Y | T | Z).  The identity comes back as (0, 1).  MSM_ERR_INVALID_ARG for an index past
+// its table, for red_G where no launch of this plan writes it (k_bucket_reduce_2) or of an empty
+// window (k_red2_groups leaves it as the previous launch wrote it), and for red_U / red_T after
+// k_bucket_reduce_1g (never written).  A dense plan is read like any other.
+int msm_test_red_state(uint32_t info[16], const uint32_t* chunks, size_t nc, uint32_t* u_xy, uint32_t* t_xy,
+                       const uint32_t* gpts, size_t ng, uint32_t* g_xy, const uint32_t* terms, size_t nt,
+                       uint32_t* term_xy) {
+  if (!info || (nc && (!chunks || !u_xy || !t_xy)) || (ng && (!gpts || !g_xy)) || (nt && (!terms || !term_xy)))
+    return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  Slot& sl = c->slot[0];
+  const Plan& pl = sl.pl;
+  Workspace& w = sl.ws;
+  const MsmDims& d = pl.d;
+  if (d.nm != 1 || !pl.L || !sl.h_out.p || !w.bucket_start.p || !sl.stream || d.W > 96) return MSM_ERR_INVALID_ARG;
+  HIPCHECK(hipStreamSynchronize(sl.stream));
+  const uint32_t G = red2_groups(pl);
+  const bool tree = red2_tree(pl), fold = tree && red_fold();
+  uint32_t v[16] = {pl.L, pl.nchunks, G, pl.nv, pl.nterms, d.W, d.B, tree ? (fold ? 2u : 0u) : 1u,
+                    (!fold && red1_pairs()) ? 1u : 0u, RG_OUT, d.c};
+  auto fetch = [](uint32_t* dst, const Buf& b, size_t first, size_t words) -> hipError_t {
+    if (!b.p || (first + words) * 4 > b.cap) return hipErrorInvalidValue;
+    return hipMemcpy(dst, static_cast<const uint32_t*>(b.p) + first, words * 4, hipMemcpyDeviceToHost);
+  };
+  std::vector<bool> empty(d.W);
+  for (uint32_t i = 0; i < d.W; i++) {
+    uint32_t a, b;
+    HIPCHECK(fetch(&a, w.bucket_start, (size_t)i * d.B, 1));
+    HIPCHECK(fetch(&b, w.bucket_start, (size_t)(i + 1) * d.B, 1));
+    empty[i] = a == b;
+    if (empty[i]) v[11 + i / 32] |= 1u << (i % 32);
+  }
+  memcpy(info, v, sizeof v);
+  uint32_t rec[PT_WORDS];
+  if (nc && fold) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < nc; i++) {
+    if (chunks[i] >= d.W * pl.nchunks) return MSM_ERR_INVALID_ARG;
+    HIPCHECK(fetch(rec, w.red_U, (size_t)chunks[i] * PT_WORDS, PT_WORDS));
+    limbs_point_to_xy_be(rec, u_xy + i * 16);
+    HIPCHECK(fetch(rec, w.red_T, (size_t)chunks[i] * PT_WORDS, PT_WORDS));
+    limbs_point_to_xy_be(rec, t_xy + i * 16);
+  }
+  if (ng && !tree) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < ng; i++) {
+    if (gpts[i] >= d.W * G * RG_OUT || empty[gpts[i] / (G * RG_OUT)]) return MSM_ERR_INVALID_ARG;
+    HIPCHECK(fetch(rec, w.red_G, (size_t)gpts[i] * PT_WORDS, PT_WORDS));
+    limbs_point_to_xy_be(rec, g_xy + i * 16);
+  }
+  for (size_t i = 0; i < nt; i++) {
+    if (terms[i] >= d.W * pl.nterms) return MSM_ERR_INVALID_ARG;
+    pt_to_be_affine(term_at(reinterpret_cast<const uint32_t*>(sl.h_out.p) + (size_t)terms[i] * 32), term_xy + i * 16);
+  }
+  return MSM_OK;
+}
+
+// The first stage's grid maps of the plan of nm MSMs of n points with `opts` (window width and range,
+// narrow scalars; may be null) and chunks of L buckets (0: the plan's own), on the host: the very
+// red1_lane / red1_group the kernels call.  info = {L, nchunks, ngroups, W, Wr, B, Wm, w0}.  lanes
+// [nlanes][2] = the (window, chunk) of lane index 0 .. nlanes - 1, groups [ngrid][3] = the (window,
+// group, live) of workgroup index 0 .. ngrid - 1; 0xffffffff in every word where the map returns
+// false.  No device needed.
+int msm_test_red_map(size_t n, uint32_t nm, const msm_opts* opts, uint32_t L, uint32_t info[8], uint32_t* lanes,
+                     size_t nlanes, uint32_t* groups, size_t ngrid) {
+  if (!info || nm < 1 || nm > MSM_MAX_BATCH || (nlanes && !lanes) || (ngrid && !groups) || (L && !red_l_known(L)))
+    return MSM_ERR_INVALID_ARG;
+  Plan pl;
+  if (int rc = make_plan(n, opts, DevShape{}, &pl, false, nm, true)) return rc;
+  if (L) plan_chunks(&pl, L);
+  const MsmDims& d = pl.d;
+  const uint32_t G = red2_groups(pl);
+  const uint32_t v[8] = {pl.L, pl.nchunks, G, d.W, d.Wr, d.B, d.Wm, d.w0};
+  memcpy(info, v, sizeof v);
+  for (size_t i = 0; i < nlanes; i++) {
+    uint32_t w = ~0u, c = ~0u;
+    if (!red1_lane(d, pl.L, pl.nchunks, (uint32_t)i, w, c)) w = c = ~0u;
+    lanes[2 * i] = w;
+    lanes[2 * i + 1] = c;
+  }
+  for (size_t i = 0; i < ngrid; i++) {
+    uint32_t w = ~0u, g = ~0u;
+    bool live = false;
+    const bool ok = red1_group(d, pl.L, pl.nchunks, G, (uint32_t)i, w, g, live);
+    groups[3 * i] = ok ? w : ~0u;
+    groups[3 * i + 1] = ok ? g : ~0u;
+    groups[3 * i + 2] = ok ? (live ? 1u : 0u) : ~0u;
+  }
+  return MSM_OK;
+}
+
+// k_red2_terms' map on the host: red2_term(term, nv, ngroups) as out = {idx, g0, g1, kbit, npts,
+// bitsel}, and groups[j] = red2_term_group(j) for j < min(npts, cap).  No device needed.
+int msm_test_red_map_term(uint32_t nv, uint32_t ngroups, uint32_t term, uint32_t out[6], uint32_t* groups, size_t cap) {
+  if (!out || nv < 1 || ngroups < 1 || (cap && !groups)) return MSM_ERR_INVALID_ARG;
+  const Red2Term t = red2_term(term, nv, ngroups);
+  const uint32_t v[6] = {t.idx, t.g0, t.g1, t.kbit, t.npts, t.bitsel ? 1u : 0u};
+  memcpy(out, v, sizeof v);
+  for (uint32_t j = 0; j < t.npts && j < cap; j++) groups[j] = red2_term_group(t, j);
+  return MSM_OK;
+}
+
+// msm_test_tail for a plan of the caller's: one MSM of n points with `opts` (window width and range;
+// may be null) and chunks of L buckets (0: the plan's own).  info = {Wr, nterms, nv, L, w0, Wm}; with
+// terms (Wr * nterms * 32 words, as msm_test_tail reads them) the tail's affine result: helpers = 0
+// runs horner_tail, otherwise a TailCrew of that many threads.  No device needed.
+int msm_test_tail_plan(size_t n, const msm_opts* opts, uint32_t L, const uint32_t* terms, int helpers,
+                       uint32_t info[6], uint32_t out_xy_be[16]) {
+  if (!info || helpers < 0 || helpers > 16 || (terms && !out_xy_be) || (L && !red_l_known(L))) return MSM_ERR_INVALID_ARG;
+  Plan pl;
+  if (int rc = make_plan(n, opts, DevShape{}, &pl)) return rc;
+  if (L) plan_chunks(&pl, L);
+  const uint32_t v[6] = {pl.d.Wr, pl.nterms, pl.nv, pl.L, pl.d.w0, pl.d.Wm};
+  memcpy(info, v, sizeof v);
+  if (!terms) return MSM_OK;
+  TailCrew crew(helpers);
+  crew.arm();
+  const Pt r = helpers ? crew.run(pl, terms) : horner_tail(pl, terms);
+  crew.disarm();
+  pt_to_be_affine(r, out_xy_be);
+  return MSM_OK;
+}
+
 // ---- guarded workspaces (host_ctx.h g_guard, host_guard.h; tests/test_gpu_guard.py) ---------------
 // The name of buffer index `id` in the guard reports (null past the table's end).  No device needed.
 const char* msm_test_guard_name(uint32_t id) {

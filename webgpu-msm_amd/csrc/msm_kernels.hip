@@ -2233,7 +2233,7 @@ __host__ __device__ __forceinline__ uint32_t red1_live_chunks(const MsmDims& d, 
 // Lane -> (window, chunk) of k_bucket_reduce_1.  Live chunks of every MSM's windows come first, so
 // real work is whole waves at the front of the grid; then the dead ones (empty unless the scalars
 // are non-canonical), which exit early.
-__device__ __forceinline__ bool red1_lane(const MsmDims& d, uint32_t L, uint32_t nchunks, uint32_t gd, uint32_t& w,
+__host__ __device__ __forceinline__ bool red1_lane(const MsmDims& d, uint32_t L, uint32_t nchunks, uint32_t gd, uint32_t& w,
                                           uint32_t& c) {
   uint32_t live = 0;  // per MSM
   for (uint32_t l = 0; l < d.Wr; l++) live += red1_live_chunks(d, L, nchunks, d.w0 + l);
@@ -2614,7 +2614,7 @@ struct Red2Term {
   uint32_t idx, g0, g1, kbit, npts;
   bool bitsel;
 };
-__device__ __forceinline__ Red2Term red2_term(uint32_t term, uint32_t nv, uint32_t ngroups) {
+__host__ __device__ __forceinline__ Red2Term red2_term(uint32_t term, uint32_t nv, uint32_t ngroups) {
   Red2Term r{0, 0, 0, 0, 0, false};
   if (term < nv) {
     const uint32_t sl = (ngroups + nv - 1) / nv;
@@ -2634,7 +2634,7 @@ __device__ __forceinline__ Red2Term red2_term(uint32_t term, uint32_t nv, uint32
   }
   return r;
 }
-__device__ __forceinline__ uint32_t red2_term_group(const Red2Term& t, uint32_t j) {
+__host__ __device__ __forceinline__ uint32_t red2_term_group(const Red2Term& t, uint32_t j) {
   return t.bitsel ? (((j >> t.kbit) << (t.kbit + 1)) | (1u << t.kbit) | (j & ((1u << t.kbit) - 1u))) : t.g0 + j;
 }
 
@@ -2682,7 +2682,7 @@ extern "C" __global__ void __launch_bounds__(4 * RG_CH) k_red2_groups(const uint
 // launch of the stage (k_red2_groups) is gone.  Live groups first (red1_group), then the dead ones
 // (chunks a canonical scalar's digit cannot reach); a group without entries writes identities, and
 // an empty window's groups are not read.
-__device__ __forceinline__ bool red1_group(const MsmDims& d, uint32_t L, uint32_t nchunks, uint32_t G, uint32_t gd,
+__host__ __device__ __forceinline__ bool red1_group(const MsmDims& d, uint32_t L, uint32_t nchunks, uint32_t G, uint32_t gd,
                                            uint32_t& w, uint32_t& g, bool& live) {
   uint32_t lg = 0;  // live groups per MSM
   for (uint32_t l = 0; l < d.Wr; l++) lg += (red1_live_chunks(d, L, nchunks, d.w0 + l) + RG_CH - 1) / RG_CH;

@@ -196,6 +196,10 @@ def load() -> ctypes.CDLL:
                                 ctypes.c_int),
         "msm_test_dense_segments": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
         "msm_test_acc_state": ([u32p, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp], ctypes.c_int),
+        "msm_test_red_state": ([u32p, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp], ctypes.c_int),
+        "msm_test_red_map": ([sz, ctypes.c_uint32, optp, ctypes.c_uint32, u32p, vp, sz, vp, sz], ctypes.c_int),
+        "msm_test_red_map_term": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, vp, sz], ctypes.c_int),
+        "msm_test_tail_plan": ([sz, optp, ctypes.c_uint32, vp, ctypes.c_int, u32p, u32p], ctypes.c_int),
         "msm_test_bases_records": ([vp, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_split_scalars": ([vp, sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_field_op": ([ctypes.c_uint32, vp, vp, u32p, sz], ctypes.c_int),
@@ -1316,6 +1320,89 @@ def _test_acc_state(keys=(), workgroups=()) -> dict:
             "lead_open": lo[:nwg], "skewed": sorted(int(v) for v in sk[:nskew]),
             "buckets": {int(k): _xy(kxy[i]) for i, k in enumerate(ks)},
             "lead_val": {int(g): _xy(wxy[i]) for i, g in enumerate(ws)}}
+
+
+RED_PATHS = ("groups+terms", "reduce_2", "fold")  # msm_test_red_state's second-stage path, by value
+
+
+def _test_red_state(chunks=(), group_points=(), terms=()) -> dict:
+    """What the bucket reduction of the last lone MSM of the default device left in its slot
+    (msm_test_red_state, test hook; tests/test_gpu_red_state.py): chunk length L, nchunks, ngroups, nv,
+    nterms, windows W, buckets B, the second-stage path (a RED_PATHS name), pairs, RG_OUT, c and the set of
+    empty windows; and the affine (x, y) of red_U / red_T for `chunks` [(w, c)], of red_G for
+    `group_points` [(w, g, idx)] and of the window terms for `terms` [(w, t)], as dicts."""
+    L = load()
+    info, info_ = _out(16)
+    _check(L.msm_test_red_state(info_, None, 0, None, None, None, 0, None, None, 0, None), "msm_test_red_state")
+    keys = ("L", "nchunks", "ngroups", "nv", "nterms", "W", "B", "path", "pairs", "rg_out", "c")
+    st = dict(zip(keys, (int(v) for v in info[:11])))
+    st["empty"] = {w for w in range(st["W"]) if (int(info[11 + w // 32]) >> (w % 32)) & 1}
+    st["path"], st["pairs"] = RED_PATHS[st["path"]], bool(st["pairs"])
+    chunks, group_points, terms = list(chunks), list(group_points), list(terms)
+    ci = np.ascontiguousarray(_u32([w * st["nchunks"] + c for w, c in chunks]).reshape(-1))
+    gi = np.ascontiguousarray(_u32([(w * st["ngroups"] + g) * st["rg_out"] + i for w, g, i in group_points]).reshape(-1))
+    ti = np.ascontiguousarray(_u32([w * st["nterms"] + t for w, t in terms]).reshape(-1))
+    u, t, g, tx = (np.zeros((max(len(a), 1), 16), np.uint32) for a in (ci, ci, gi, ti))
+    before = info.copy()
+    _check(L.msm_test_red_state(info_, _ptr(ci), len(ci), _ptr(u), _ptr(t), _ptr(gi), len(gi), _ptr(g), _ptr(ti), len(ti),
+                                _ptr(tx)), "msm_test_red_state")
+    if not np.array_equal(before, info):
+        raise RuntimeError("msm_test_red_state: the slot changed between the two reads")
+    st["U"] = {k: _xy(u[i]) for i, k in enumerate(chunks)}
+    st["T"] = {k: _xy(t[i]) for i, k in enumerate(chunks)}
+    st["G"] = {k: _xy(g[i]) for i, k in enumerate(group_points)}
+    st["terms"] = {k: _xy(tx[i]) for i, k in enumerate(terms)}
+    return st
+
+
+def _test_red_map(n: int, nm: int = 1, chunk_len: int = 0, window_size: Optional[int] = None,
+                  windows: Optional[Tuple[int, int]] = None, scalar_bits: Optional[int] = None, extra: int = 0) -> dict:
+    """The first reduction stage's grid maps on the host (msm_test_red_map: the kernels' own red1_lane and
+    red1_group) for the plan of nm MSMs of n points: L, nchunks, ngroups, W, Wr, B, Wm, w0, `lanes`
+    [W nchunks + extra][2] = (window, chunk) and `groups` [W ngroups + extra][3] = (window, group, live),
+    0xffffffff where the map says false.  chunk_len = 0 takes the plan's own.  No GPU needed."""
+    L = load()
+    info, info_ = _out(8)
+    o = _opts(window_size, windows=windows, scalar_bits=scalar_bits)
+    _check(L.msm_test_red_map(n, nm, o, chunk_len, info_, None, 0, None, 0), "msm_test_red_map")
+    d = dict(zip(("L", "nchunks", "ngroups", "W", "Wr", "B", "Wm", "w0"), (int(v) for v in info)))
+    lanes = np.zeros((d["W"] * d["nchunks"] + extra, 2), np.uint32)
+    groups = np.zeros((d["W"] * d["ngroups"] + extra, 3), np.uint32)
+    _check(L.msm_test_red_map(n, nm, o, chunk_len, info_, _ptr(lanes), len(lanes), _ptr(groups), len(groups)),
+           "msm_test_red_map")
+    d["lanes"], d["groups"] = lanes, groups
+    return d
+
+
+def _test_red_map_term(nv: int, ngroups: int, term: int) -> dict:
+    """k_red2_terms' map on the host (msm_test_red_map_term): red2_term's idx, g0, g1, kbit, npts, bitsel
+    and `groups` = red2_term_group(j) for j < npts.  No GPU needed."""
+    o, o_ = _out(6)
+    _check(load().msm_test_red_map_term(nv, ngroups, term, o_, None, 0), "msm_test_red_map_term")
+    g = np.zeros(max(int(o[4]), 1), np.uint32)
+    _check(load().msm_test_red_map_term(nv, ngroups, term, o_, _ptr(g), int(o[4])), "msm_test_red_map_term")
+    d = dict(zip(("idx", "g0", "g1", "kbit", "npts", "bitsel"), (int(v) for v in o)))
+    d["groups"] = [int(v) for v in g[:d["npts"]]]
+    return d
+
+
+def _test_tail_plan(n: int, terms=None, helpers: int = 0, chunk_len: int = 0, window_size: Optional[int] = None,
+                    windows: Optional[Tuple[int, int]] = None):
+    """The host tail on caller-given window terms for a plan of the caller's (msm_test_tail_plan):
+    without `terms` the plan's {windows, nterms, nv, L, w0, Wm}; with them ([windows nterms, 32] host
+    Montgomery words) the tail's affine (x, y).  No GPU needed."""
+    info, info_ = _out(6)
+    o = _opts(window_size, windows=windows)
+    if terms is None:
+        _check(load().msm_test_tail_plan(n, o, chunk_len, None, 0, info_, None), "msm_test_tail_plan")
+        return dict(zip(("windows", "nterms", "nv", "L", "w0", "Wm"), (int(v) for v in info)))
+    t = np.ascontiguousarray(_u32(terms).reshape(-1))
+    _check(load().msm_test_tail_plan(n, o, chunk_len, None, 0, info_, None), "msm_test_tail_plan")
+    if t.size != int(info[0]) * int(info[1]) * 32:
+        raise ValueError("terms: windows * nterms * 32 words")
+    out, out_ = _out(16)
+    _check(load().msm_test_tail_plan(n, o, chunk_len, _ptr(t), int(helpers), info_, out_), "msm_test_tail_plan")
+    return _xy(out)
 
 
 def _test_subset_plan(n_handle: int, levels: int, window_size: int, first: int, m: int, indexed: bool) -> dict:
