@@ -35,7 +35,7 @@ extern "C" {
 #define MSM_ERR_INVALID_ARG (-1)        /* null pointer / bad option                          */
 #define MSM_ERR_UNSUPPORTED_WINDOW (-2) /* lib.rs:200,208,223,231 `Unsupported window size`  */
 #define MSM_ERR_COORD_RANGE (-3)        /* bytes.rs:19 Fq::from_bigint(..).unwrap() (coord >= p) */
-#define MSM_ERR_BAD_POINT (-4)          /* z == 0 (not a projective point)                    */
+#define MSM_ERR_BAD_POINT (-4)          /* z == 0 (not a projective point); a compressed x of no such point */
 #define MSM_ERR_HIP (-5)                /* HIP runtime failure                                */
 #define MSM_ERR_NO_DEVICE (-6)          /* no gfx950 device visible: there is no CPU fallback */
 #define MSM_ERR_OOM (-7)                /* device allocation failed                           */
@@ -411,6 +411,52 @@ typedef struct msm_bases_info_t {
 int msm_bases_create(const uint32_t* points_be, size_t n, const msm_opts* opts, uint32_t levels, msm_bases** out);
 int msm_bases_create_device(const uint32_t* d_points_be, size_t n, const msm_opts* opts, uint32_t levels,
                             void* hip_stream, msm_bases** out);
+
+/* Compressed points: an Aleo group element is its x-coordinate, so a base vector may arrive as x
+ * alone -- 8 x uint32 per point, big-endian word order as every field element here -- and y is
+ * recovered on the device (k_decompress_x: one inversion, a Tonelli-Shanks square root over the
+ * 2^47-part of Fq*, p - 1 = 2^47 q).  y^2 = (a x^2 - 1) / (d x^2 - 1); the denominator is never 0.
+ *
+ *   MSM_POINTS_X_SUBGROUP  the eight words are x < p.  y is THE root whose point lies in the
+ *       prime-order subgroup, [r](x, y) = O (at most one does: (x, -y) = -(x, y) + (0, -1)).  x = 0
+ *       is the identity (0, 1).  A non-square y^2, or an x neither of whose points is in the
+ *       subgroup, is MSM_ERR_BAD_POINT.  This differs from the reference's getPointFromX
+ *       (FieldMath.ts:31-55), which returns -y without a check when [r](x, y) != O: it hands back a
+ *       point outside the subgroup where this library reports an error.
+ *   MSM_POINTS_X_YSIGN     bit 255 (the top bit of word 0) is a sign flag, bits 253 and 254 must be
+ *       zero, the low 253 bits are x < p (MSM_ERR_COORD_RANGE otherwise).  y is the root with
+ *       (y > p - y) == flag, compared on canonical integers.  No subgroup test: every curve point is
+ *       representable, torsion points included ((0, flag 1) is the order-2 point (0, p - 1)).
+ *       y = 0 with the flag set is MSM_ERR_BAD_POINT (non-canonical), as is a non-square y^2.
+ *
+ * msm_decompress_points* write wire records (x | y | t = x y | z = 1, 32 words each), which every
+ * msm_compute* entry reads as they are; a point in error is written as the identity.
+ * msm_bases_create_compressed* make the handle msm_bases_create* makes from the same points (the
+ * decompressed x|y goes through the same preparation), from a 32-byte-per-point upload; everything
+ * said of msm_bases_create* above holds, and the handle's info and compute entries do not know the
+ * difference.  Rules: an unknown form, a scalar flag, MSM_FLAG_DEVICES or MSM_FLAG_WINDOWS on opts
+ * give MSM_ERR_INVALID_ARG; device pointers must be 16-byte aligned (MSM_ERR_INVALID_ARG, decided
+ * from the pointer value before anything is enqueued); MSM_ERR_COORD_RANGE takes precedence over
+ * MSM_ERR_BAD_POINT (neither says which point); n = 0 works.  opts may set device (and, for a
+ * creation, window_bits).  The device entries are ordered after the work queued on hip_stream and
+ * return when the result is complete.
+ *
+ * msm_compress_points is the host-side inverse for affine points (x | y, 16 words each, both < p,
+ * MSM_ERR_COORD_RANGE otherwise): X_SUBGROUP writes x, X_YSIGN x with the flag of y.  It tests
+ * neither the curve equation nor subgroup membership. */
+#define MSM_POINTS_X_SUBGROUP 1u
+#define MSM_POINTS_X_YSIGN 2u
+int msm_decompress_points(const uint32_t* xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                          uint32_t* points_be /* [n][32] wire records */);
+int msm_decompress_points_device(const uint32_t* d_xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                                 void* hip_stream, uint32_t* d_points_be);
+int msm_bases_create_compressed(const uint32_t* xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                                uint32_t levels, msm_bases** out);
+int msm_bases_create_compressed_device(const uint32_t* d_xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                                       uint32_t levels, void* hip_stream, msm_bases** out);
+int msm_compress_points(const uint32_t* xy_be /* [n][16] affine */, size_t n, uint32_t form,
+                        uint32_t* xs_be); /* host only; does not test subgroup membership */
+
 int msm_bases_destroy(msm_bases* bases);
 int msm_bases_info(const msm_bases* bases, msm_bases_info_t* out);
 int msm_bases_compute(const msm_bases* bases, const uint32_t* scalars_be, const msm_opts* opts,

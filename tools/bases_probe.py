@@ -72,6 +72,19 @@ the full 256 bits; fr_mont: random a < r, the scalar being a 2^-256 mod r):
 
 with the narrow sweep's four timings and the per-phase times of one profiled awaited call.
 
+With --compressed the pass is the compressed-creation sweep of DESIGN.md §9 (MSM_POINTS_X_*): at each size,
+for both forms, one line
+
+  {"entry": "compressed", "form", "from_x_ms", "from_x_device_ms", "decompress_device_ms",
+   "from_wire_ms", "from_device_ms", ...}
+
+with the creation of a levels-1 handle from host x-coordinates (32 n bytes up, then k_decompress_x and the
+preparation) and from device-resident ones, the awaited device-to-device msm_decompress_points_device on its
+own (the kernel, one launch and the read-back of its error word), and -- the comparison that matters,
+same points, same run -- the wire creations from host records (128 n bytes up) and from device-resident
+ones.  Each creation is timed with its msm_bases_destroy; one MSM on the compressed handle is checked
+against the closed form, and the decompressed records against the generator's.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -611,6 +624,58 @@ def wide_pass(a):
     return 1 if bad else 0
 
 
+def compressed_pass(a):
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from _closed_form import closed_form
+
+    n = a.n
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    pts = M.gen_points(n, k0=3, step=5)
+    sc = M.gen_scalars(n, seed=500)
+    exp = closed_form(3, 5, sc)
+    d_pts = dev(pts)
+    d_out = torch.zeros((n, 32), dtype=torch.int32, device="cuda")
+    xs = {"subgroup": np.ascontiguousarray(pts[:, :8]), "ysign": M.compress_points(pts, "ysign")}
+    torch.cuda.synchronize()
+
+    def create(make):
+        def run():
+            make().close()
+        return run
+
+    wire_ms, wire_runs, _ = timed(create(lambda: M.Bases.from_wire(pts, levels=1)), a.runs)
+    dwire_ms, dwire_runs, _ = timed(create(lambda: M.Bases.from_device(d_pts, n, levels=1)), a.runs)
+    for form, w in xs.items():
+        d_xs = dev(w)
+        torch.cuda.synchronize()
+        with M.Bases.from_x(w, form, levels=1) as b:
+            correct = b.compute(sc) == exp
+        hx_ms, hx_runs, _ = timed(create(lambda: M.Bases.from_x(w, form, levels=1)), a.runs)
+        dx_ms, dx_runs, _ = timed(create(lambda: M.Bases.from_x_device(d_xs, n, form, levels=1)), a.runs)
+        k_ms, k_runs, _ = timed(lambda: M.decompress_points_device(d_xs, n, d_out, form), a.runs)
+        same = bool(np.array_equal(d_out.cpu().numpy().view(np.uint32), pts))
+        d = {"n": n, "entry": "compressed", "form": form, "from_x_ms": round(hx_ms, 4),
+             "from_x_device_ms": round(dx_ms, 4), "decompress_device_ms": round(k_ms, 4),
+             "decompress_ns_per_point": round(k_ms * 1e6 / n, 2), "from_wire_ms": round(wire_ms, 4),
+             "from_device_ms": round(dwire_ms, 4), "runs_ms": {"from_x": hx_runs, "from_x_device": dx_runs,
+                                                               "decompress_device": k_runs, "from_wire": wire_runs,
+                                                               "from_device": dwire_runs},
+             "correct": bool(correct), "records_equal": same}
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+        if not (correct and same):
+            return 1
+    return 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -666,12 +731,24 @@ def main():
     ap.add_argument("--dense", action="store_true", help="the dense-bucket sweep (DENSE_MIN, MSM_DENSE_MIN) instead")
     ap.add_argument("--native", action="store_true", help="the native-type sweep (MSM_FLAG_SCALAR_TYPE) instead")
     ap.add_argument("--native-types", default="bit,u8,i8,u16,i16,i32,i64,u64", help="types of the native sweep")
+    ap.add_argument("--compressed", action="store_true", help="the compressed-creation sweep (MSM_POINTS_X_*) instead")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
     a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
     if a.dense:
         return dense_sweep(a)
+    if a.compressed:
+        if a.n:
+            return compressed_pass(a)
+        for lg in (int(x) for x in a.sizes.split(",")):
+            cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--n",
+                   str(1 << lg), "--compressed", "--runs", str(a.runs)]
+            rc = subprocess.run(cmd + (["--out", a.out] if a.out else [])).returncode
+            if rc != 0:
+                print(f"bases_probe: size 2^{lg} ended with status {rc}; stopping", file=sys.stderr)
+                return rc
+        return 0
     if a.subset:
         a.subset_sizes = [int(x) for x in str(a.subset_sizes).split(",")]
         if a.n:

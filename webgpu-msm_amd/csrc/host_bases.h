@@ -41,11 +41,25 @@ bool bases_flags_ok(const msm_opts* o) {  // a handle lives on one device and ru
   return !o || !(o->flags & (MSM_FLAG_DEVICES | MSM_FLAG_WINDOWS | MSM_FLAG_HALF_WINDOWS));
 }
 
-int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* opts, uint32_t levels,
+// Compressed points (msm.h MSM_POINTS_X_*): k_decompress_x over n device-resident x vectors into `dst`,
+// x|y (wire = 0) or wire records (wire = 1), errors into err[0].
+static_assert(DX_FORM_SUBGROUP == MSM_POINTS_X_SUBGROUP && DX_FORM_YSIGN == MSM_POINTS_X_YSIGN, "k_decompress_x's forms");
+bool points_form_ok(uint32_t form) { return form == MSM_POINTS_X_SUBGROUP || form == MSM_POINTS_X_YSIGN; }
+bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15u); }
+void launch_decompress(const uint32_t* d_xs, uint32_t* dst, uint32_t n, uint32_t form, uint32_t wire, uint32_t* err,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(k_decompress_x, dim3(grid_for(n, DX_THREADS)), dim3(DX_THREADS), 0, s, d_xs, dst, n, form, wire,
+                     err);
+}
+
+// `form` 0: `points` are wire records; MSM_POINTS_X_*: compressed points, decompressed into the slot's
+// dx_pts as x|y and prepared from there, so the records are those of the wire creation of the same points.
+int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, const msm_opts* opts, uint32_t levels,
                  hipStream_t user_stream, msm_bases** out) {
   if (!out) return MSM_ERR_INVALID_ARG;
   *out = nullptr;
   if ((!points && n) || levels > 8 || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  if (form && (!points_form_ok(form) || (!host && !aligned16(points)))) return MSM_ERR_INVALID_ARG;
   const uint32_t wb = opts ? opts->window_bits : 0;
   if (wb && (wb < 4 || wb > 20)) return MSM_ERR_UNSUPPORTED_WINDOW;
   if (!levels) levels = bases_auto_levels(n);
@@ -95,7 +109,18 @@ int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* op
     if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
     if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
     const uint32_t nt = prep_nt((size_t)levels * n);
-    if (host) {
+    if (form) {
+      const uint32_t* d_xs = points;
+      if (host) {  // 32 n bytes up, into the wire buffer
+        if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK) return done(r);
+        if ((r = upload_scalars(c, points, n, s0.ws.wire_pts.as<uint32_t>(), s0.stream, c->ev_chunk[0])) != MSM_OK)
+          return done(r);
+        d_xs = s0.ws.wire_pts.as<uint32_t>();
+      }
+      if ((r = s0.ws.dx_pts.ensure(n * 64)) != MSM_OK) return done(r);
+      launch_decompress(d_xs, s0.ws.dx_pts.as<uint32_t>(), (uint32_t)n, form, 0, errp, s0.stream);
+      launch_prepare(s0.ws.dx_pts.as<uint32_t>(), rec, (uint32_t)n, errp, nt, s0.stream, PT_FMT_XY);
+    } else if (host) {
       if ((r = s0.ws.wire_pts.ensure(n * 128)) != MSM_OK) return done(r);
       if ((r = upload_points(c, points, n, s0.ws.wire_pts.as<uint32_t>(), rec, errp, s0.stream)) != MSM_OK)
         return done(r);
@@ -126,6 +151,77 @@ int create_bases(const uint32_t* points, bool host, size_t n, const msm_opts* op
   const uintptr_t id = g_bases_next++;
   g_bases[id] = b;
   *out = reinterpret_cast<msm_bases*>(id);
+  return MSM_OK;
+}
+
+// msm_decompress_points*: n compressed points to wire records, host to host (through the slot's wire
+// buffer and dx_pts) or device to device (the caller's buffers).
+int decompress_points(const uint32_t* xs, bool host, size_t n, uint32_t form, const msm_opts* opts,
+                      hipStream_t user_stream, uint32_t* points) {
+  if (((!xs || !points) && n) || !points_form_ok(form) || !bases_flags_ok(opts) || narrow_flagged(opts))
+    return MSM_ERR_INVALID_ARG;
+  if (!host && (!aligned16(xs) || !aligned16(points))) return MSM_ERR_INVALID_ARG;
+  if (n >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  msm_opts od{};
+  od.device = opts ? opts->device : -1;
+  return on_device(&od, [&](DevCtx* c) -> int {
+    if (!n) return MSM_OK;
+    Slot& s0 = c->slot[0];
+    Buf errb;
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    auto done = [&](int code) {  // as create_bases'
+      drain_streams(c, 1, code);
+      if (errb.base) {
+        std::lock_guard<std::mutex> gl(g_guard_mu);
+        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+      }
+      errb.release();
+      return code;
+    };
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    const uint32_t* d_xs = xs;
+    uint32_t* d_out = points;
+    if (host) {
+      if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK || (r = s0.ws.dx_pts.ensure(n * 128)) != MSM_OK) return done(r);
+      if ((r = upload_scalars(c, xs, n, s0.ws.wire_pts.as<uint32_t>(), s0.stream, c->ev_chunk[0])) != MSM_OK)
+        return done(r);
+      d_xs = s0.ws.wire_pts.as<uint32_t>();
+      d_out = s0.ws.dx_pts.as<uint32_t>();
+    }
+    launch_decompress(d_xs, d_out, (uint32_t)n, form, 1, errp, s0.stream);
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if ((host && hipMemcpyAsync(points, d_out, n * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
+        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+}
+
+// msm_compress_points: affine x|y to x, with y's sign flag in bit 255 for MSM_POINTS_X_YSIGN.
+int compress_points(const uint32_t* xy, size_t n, uint32_t form, uint32_t* xs) {
+  if (((!xy || !xs) && n) || !points_form_ok(form)) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n; i++) {
+    uint64_t x[4], y[4];
+    be_words_to_std(xy + 16 * i, x);
+    be_words_to_std(xy + 16 * i + 8, y);
+    if (!std_lt_p(x) || !std_lt_p(y)) return MSM_ERR_COORD_RANGE;
+  }
+  for (size_t i = 0; i < n; i++) {
+    uint64_t y[4], y2[4];
+    be_words_to_std(xy + 16 * i + 8, y);
+    for (int k = 3; k >= 0; k--) y2[k] = (y[k] << 1) | (k ? y[k - 1] >> 63 : 0);
+    // y > p - y: 2 y > p, and 2 y (even, below 2^254) is never p
+    const bool big = !std_lt_p(y2);
+    for (int k = 0; k < 8; k++) xs[8 * i + k] = xy[16 * i + k];
+    if (form == MSM_POINTS_X_YSIGN && big) xs[8 * i] |= 0x80000000u;
+  }
   return MSM_OK;
 }
 

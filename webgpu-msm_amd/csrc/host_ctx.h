@@ -174,6 +174,7 @@ struct Workspace {
   Buf split_sc;            // k_split_scalars' virtual scalars of a folded launch (msm_bases_*, levels > 1)
   Buf sub_idx;             // base indices [nm][m] of an indexed subset launch (msm_bases_compute_subset*)
   Buf seg_base, unit_key, partials;  // the dense-bucket accumulation's segment map and per-unit sums (Plan::dense)
+  Buf dx_pts;              // k_decompress_x's output: x|y of a compressed creation, wire records of msm_decompress_points
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
@@ -187,7 +188,7 @@ struct Workspace {
     WS_BUF(lead_val), WS_BUF(lead_open), WS_BUF(cross_key), WS_BUF(lead_flag), WS_BUF(skew_list);
     WS_BUF(g_head), WS_BUF(g_hkey), WS_BUF(g_tkey), WS_BUF(red_U), WS_BUF(red_T);
     WS_BUF(wire_pts), WS_BUF(wire_sc), WS_BUF(red_G), WS_BUF(split_sc), WS_BUF(sub_idx);
-    WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials);
+    WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials), WS_BUF(dx_pts);
 #ifdef MSM_DUMMY_ALLOC
     WS_BUF(dummy_tiles), WS_BUF(dummy_cursor);
 #endif

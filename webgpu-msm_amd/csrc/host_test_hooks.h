@@ -351,6 +351,23 @@ int msm_test_wide_masks(uint32_t out[4]) {
   return MSM_OK;
 }
 
+// k_decompress_x's constants as the kernel reads them (msm_kernels.hip dx_*; tests/test_sqrt_model.py
+// recomputes each from p): out[0] the 2-adicity of p - 1, out[1] the words of the exponent the loop
+// runs, out[2] the bits of the order the ladder runs, out[3..11] (q - 1) / 2 and out[11..19] r as
+// little-endian words, out[19..28] omega's Montgomery limbs.
+int msm_test_decompress_constants(uint32_t out[28]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  out[0] = DX_TWO_ADICITY;
+  out[1] = DX_EXP_WORDS;
+  out[2] = DX_ORDER_BITS;
+  for (uint32_t i = 0; i < 8; i++) {
+    out[3 + i] = dx_exp_word(i);
+    out[11 + i] = dx_order_word(i);
+  }
+  for (uint32_t i = 0; i < NL; i++) out[19 + i] = dx_omega_limb(i);
+  return MSM_OK;
+}
+
 // out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
 // msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
 int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {

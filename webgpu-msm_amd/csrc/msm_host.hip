@@ -99,7 +99,7 @@ const char* msm_strerror(int code) {
     case MSM_ERR_INVALID_ARG: return "invalid argument";
     case MSM_ERR_UNSUPPORTED_WINDOW: return "unsupported window size";
     case MSM_ERR_COORD_RANGE: return "coordinate not in [0, p)";
-    case MSM_ERR_BAD_POINT: return "invalid point (z == 0)";
+    case MSM_ERR_BAD_POINT: return "invalid point (z == 0, or a compressed x of no such point)";
     case MSM_ERR_HIP: return "HIP runtime error";
     case MSM_ERR_NO_DEVICE: return "no gfx950 (MI355X) device available";
     case MSM_ERR_OOM: return "device out of memory";
@@ -250,12 +250,39 @@ int msm_compute_shared(const uint32_t* points_be, const uint32_t* const* scalars
 }
 
 int msm_bases_create(const uint32_t* points_be, size_t n, const msm_opts* opts, uint32_t levels, msm_bases** out) {
-  return create_bases(points_be, true, n, opts, levels, nullptr, out);
+  return create_bases(points_be, true, n, 0, opts, levels, nullptr, out);
 }
 
 int msm_bases_create_device(const uint32_t* d_points_be, size_t n, const msm_opts* opts, uint32_t levels,
                             void* hip_stream, msm_bases** out) {
-  return create_bases(d_points_be, false, n, opts, levels, (hipStream_t)hip_stream, out);
+  return create_bases(d_points_be, false, n, 0, opts, levels, (hipStream_t)hip_stream, out);
+}
+
+int msm_bases_create_compressed(const uint32_t* xs_be, size_t n, uint32_t form, const msm_opts* opts, uint32_t levels,
+                                msm_bases** out) {
+  if (out) *out = nullptr;
+  if (!points_form_ok(form)) return MSM_ERR_INVALID_ARG;
+  return create_bases(xs_be, true, n, form, opts, levels, nullptr, out);
+}
+
+int msm_bases_create_compressed_device(const uint32_t* d_xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                                       uint32_t levels, void* hip_stream, msm_bases** out) {
+  if (out) *out = nullptr;
+  if (!points_form_ok(form)) return MSM_ERR_INVALID_ARG;
+  return create_bases(d_xs_be, false, n, form, opts, levels, (hipStream_t)hip_stream, out);
+}
+
+int msm_decompress_points(const uint32_t* xs_be, size_t n, uint32_t form, const msm_opts* opts, uint32_t* points_be) {
+  return decompress_points(xs_be, true, n, form, opts, nullptr, points_be);
+}
+
+int msm_decompress_points_device(const uint32_t* d_xs_be, size_t n, uint32_t form, const msm_opts* opts,
+                                 void* hip_stream, uint32_t* d_points_be) {
+  return decompress_points(d_xs_be, false, n, form, opts, (hipStream_t)hip_stream, d_points_be);
+}
+
+int msm_compress_points(const uint32_t* xy_be, size_t n, uint32_t form, uint32_t* xs_be) {
+  return compress_points(xy_be, n, form, xs_be);
 }
 
 int msm_bases_destroy(msm_bases* h) {

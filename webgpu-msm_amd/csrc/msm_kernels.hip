@@ -340,6 +340,233 @@ extern "C" __global__ void __launch_bounds__(PP_THREADS) k_shift_bases(const uin
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// compressed points (msm_decompress_points*, msm_bases_create_compressed*): y from x
+// ---------------------------------------------------------------------------------------------
+// p - 1 = 2^47 q with q odd, so a square root is Tonelli-Shanks over the 2^47-part of the
+// multiplicative group.  The constants below are functions, so that the host's test hook
+// (msm_test_decompress_constants) reads the very values the kernel uses; tests/test_sqrt_model.py
+// recomputes each of them from p.
+constexpr uint32_t DX_TWO_ADICITY = 47;
+constexpr uint32_t DX_EXP_WORDS = 7;  // (q - 1) / 2 has 205 bits
+// (q - 1) / 2, little-endian words.
+__host__ __device__ constexpr uint32_t dx_exp_word(uint32_t i) {
+  constexpr uint32_t E[8] = {0x00010a11u, 0x76fed000u, 0xb00159aau, 0x4d1e5c37u,
+                             0xa55660b4u, 0x655e9a2cu, 0x000012abu, 0u};
+  return E[i];
+}
+// The order r of the prime-order subgroup (251 bits), little-endian words.
+constexpr uint32_t DX_ORDER_BITS = 251;
+__host__ __device__ constexpr uint32_t dx_order_word(uint32_t i) {
+  constexpr uint32_t E[8] = {0xc33fd9ffu, 0xb95aee9au, 0xc43c8afeu, 0x5293a3afu,
+                             0x970dec00u, 0x982d1347u, 0xa68b2955u, 0x04aad957u};
+  return E[i];
+}
+// omega = 11^q, a generator of the 2^47-th roots of unity (11 is the least non-residue), as
+// Montgomery limbs.
+__host__ __device__ constexpr uint32_t dx_omega_limb(uint32_t i) {
+  constexpr uint32_t W[NL] = {117700138u, 288663353u, 196695082u, 116731750u, 508254431u,
+                              393715903u, 414881643u, 49231371u, 571788u};
+  return W[i];
+}
+
+__device__ __forceinline__ bool fe_eq_limbs(const fe& a, const fe& b) {
+  bool eq = true;
+#pragma unroll
+  for (int i = 0; i < NL; i++) eq = eq && a.v[i] == b.v[i];
+  return eq;
+}
+// Whether an fe_mul output is 1.  Its value is below 2p and its limbs are normalised, so it is one of
+// two integers, R mod p and R mod p + p, each with one limb pattern: the comparison is exact without
+// a reduction (unlike one between two lazy values, which goes through fe_to_std).
+__device__ __forceinline__ bool fe_mul_out_is_one(const fe& t, const fe& one, const fe& one_p) {
+  return fe_eq_limbs(t, one) || fe_eq_limbs(t, one_p);
+}
+// p - a for a canonical standard-form a in (0, p); 0 stays 0.
+__device__ __forceinline__ fe fe_std_neg(const fe& a) {
+  fe r;
+  int32_t borrow = 0;
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    const int32_t t = (int32_t)P29[i] - (int32_t)a.v[i] + borrow;
+    borrow = t < 0 ? -1 : 0;
+    r.v[i] = (uint32_t)t & LMASK;
+    any |= a.v[i];
+  }
+  return any ? r : a;
+}
+
+// A square root of u (Montgomery form, an fe_mul output) by Tonelli-Shanks, or some value whose
+// square is not u when u is a non-residue: the caller compares r^2 with u (which also accepts
+// u = 0, r = 0).  w = u^((q-1)/2), r = u w, t = u^q; while t != 1, with 2^i the order of t,
+// b = c^(2^(m-i-1)) moves r by b and t by b^2.  The loops' trip counts differ per lane (a wave
+// pays its deepest lane); none is unrolled.
+__device__ inline fe fe_sqrt_ts(const fe& u) {
+  const fe one = fe_one();
+  const fe one_p = fe_add_n(one, fe_const(P29));
+  fe w = one;
+#pragma unroll 1
+  for (int wi = DX_EXP_WORDS - 1; wi >= 0; wi--) {
+    const uint32_t e = dx_exp_word(wi);
+#pragma unroll 1
+    for (int b = 31; b >= 0; b--) {
+      w = fe_sqr(w);
+      if ((e >> b) & 1u) w = fe_mul(w, u);
+    }
+  }
+  fe r = fe_mul(u, w);
+  fe t = fe_mul(r, w);
+  fe c;
+#pragma unroll
+  for (int i = 0; i < NL; i++) c.v[i] = dx_omega_limb(i);
+  uint32_t m = DX_TWO_ADICITY;
+#pragma unroll 1
+  while (!fe_mul_out_is_one(t, one, one_p)) {
+    uint32_t i = 0;
+    fe t2 = t;
+#pragma unroll 1
+    do {
+      t2 = fe_sqr(t2);
+      i++;
+    } while (i < m && !fe_mul_out_is_one(t2, one, one_p));
+    if (i >= m) break;  // t's order is not below 2^m: u is 0 or a non-residue
+    fe b = c;
+#pragma unroll 1
+    for (uint32_t j = i + 1; j < m; j++) b = fe_sqr(b);
+    c = fe_sqr(b);
+    t = fe_mul(t, c);
+    r = fe_mul(r, b);
+    m = i;
+  }
+  return r;
+}
+
+// [r] P for the subgroup order r: double-and-add over the constant's bits, so every lane takes the
+// same path.  P's coordinates are fe_mul outputs (Z = 1), as pt_dbl's and pt_add's bound proofs
+// take them.
+__device__ inline xyzt pt_mul_order(const xyzt& p) {
+  xyzt acc = pt_identity();
+#pragma unroll 1
+  for (int k = DX_ORDER_BITS - 1; k >= 0; k--) {
+    acc = pt_dbl(acc);
+    if ((dx_order_word((uint32_t)k >> 5) >> (k & 31)) & 1u) acc = pt_add(acc, p);
+  }
+  return acc;
+}
+
+// Compressed points -> affine points: x (8 big-endian words, msm.h MSM_POINTS_X_*) to the 64-byte
+// x|y that k_prepare_points(PT_FMT_XY) reads, or with `wire` to a whole 128-byte record
+// (t = x y, z = 1).  One lane per point; a wave's 2 KiB of input arrives with two 16-byte loads per
+// lane, and the output goes through LDS (slots swizzled as k_prepare_points') to leave in coalesced
+// 16-byte stores.
+//   y^2 = (a x^2 - 1) / (d x^2 - 1) = (x^2 + 1) / (1 - d x^2)       (a = -1)
+// The denominator is never 0: d = 3021 is a non-residue, so d x^2 = 1 has no solution.
+// form 1 (subgroup): y is the root with [r](x, y) = O.  (x, -y) = -(x, y) + (0, -1) and r is odd, so
+// [r](x, -y) = O exactly when [r](x, y) = (0, -1): one ladder decides both roots.
+// form 2 (ysign): bit 255 says whether y > p - y; bits 253 and 254 must be zero.
+// A bad lane (MSM_DEV_ERR_COORD_RANGE, MSM_DEV_ERR_BAD_POINT into err[0]) writes the identity, so
+// whatever runs next reads a valid point.
+// One wave per workgroup: a lane's work differs with its input's depth, and small workgroups spread a
+// vector over more compute units; two waves per SIMD (256 VGPRs) keep the multiplies' latency covered.
+constexpr uint32_t DX_THREADS = 64;
+constexpr uint32_t DX_FORM_SUBGROUP = 1, DX_FORM_YSIGN = 2;
+extern "C" __global__ void __launch_bounds__(DX_THREADS, 2) k_decompress_x(const uint32_t* __restrict__ xs,
+                                                                        uint32_t* __restrict__ out, uint32_t n,
+                                                                        uint32_t form, uint32_t wire,
+                                                                        uint32_t* __restrict__ err) {
+  __shared__ uint4 st[DX_THREADS * 8];
+  const uint32_t p0 = blockIdx.x * DX_THREADS;
+  const uint32_t np = min(DX_THREADS, n - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  uint32_t xw[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) xw[k] = 0;
+  if (live) load_be_words(xs + (size_t)(p0 + i) * 8, xw);
+  bool flag = false, in_range = true;
+  if (form == DX_FORM_YSIGN) {
+    flag = (xw[7] >> 31) != 0;
+    in_range = (xw[7] & 0x60000000u) == 0;
+    xw[7] &= 0x1FFFFFFFu;
+  }
+  in_range = in_range && words_lt_p(xw);
+  if (!in_range) {  // (a lane past the block's last point holds x = 0)
+    atomicOr(err, MSM_DEV_ERR_COORD_RANGE);
+#pragma unroll
+    for (int k = 0; k < 8; k++) xw[k] = 0;  // goes on as the identity
+    flag = false;
+  }
+  const fe one = fe_one();
+  const fe xm = fe_to_mont(fe_from_words_le(xw));
+  const fe x2 = fe_sqr(xm);
+  const fe num = fe_add_n(x2, one);
+  const fe den = fe_sub(one, fe_mul_d(x2));
+  const fe u = fe_mul(num, fe_inv(den));
+  const fe r = fe_sqrt_ts(u);
+  // the non-residue test, on canonical values (the limbs of two lazy values do not compare)
+  bool bad = !fe_eq_limbs(fe_to_std(fe_sqr(r)), fe_to_std(u));
+  fe ys = fe_to_std(r);
+  bool neg;
+  if (form == DX_FORM_SUBGROUP) {
+    xyzt p;
+    p.X = xm;
+    p.Y = r;
+    p.T = fe_mul(xm, r);
+    p.Z = one;
+    const xyzt q = pt_mul_order(p);
+    const fe qx = fe_to_std(q.X), qy = fe_to_std(q.Y), qz = fe_to_std(q.Z);
+    const bool x0 = fe_eq_limbs(qx, fe_zero());
+    const bool is_o = x0 && fe_eq_limbs(qy, qz);                          // (0 : z : z)
+    const bool is_t2 = x0 && fe_eq_limbs(fe_add_n(qy, qz), fe_const(P29));  // (0 : -z : z)
+    bad = bad || !(is_o || is_t2);
+    neg = is_t2;
+  } else {
+    // y > p - y on canonical integers: 2 y > p (2 y < 2^254 is even, p odd: never equal)
+    uint32_t yw[8], y2[8];
+    fe_to_words_le(ys, yw);
+#pragma unroll
+    for (int k = 7; k >= 0; k--) y2[k] = (yw[k] << 1) | (k ? yw[k - 1] >> 31 : 0u);
+    const bool big = !words_lt_p(y2);
+    const bool zero = fe_eq_limbs(ys, fe_zero());
+    bad = bad || (zero && flag);  // y = 0 has no sign: the flag must be clear
+    neg = big != flag;
+  }
+  fe ts = fe_to_std(fe_mul(xm, r));
+  if (neg) {
+    ys = fe_std_neg(ys);
+    ts = fe_std_neg(ts);
+  }
+  if (bad) {
+    if (live) atomicOr(err, MSM_DEV_ERR_BAD_POINT);
+#pragma unroll
+    for (int k = 0; k < 8; k++) xw[k] = 0;
+    ys = fe_zero();
+    ys.v[0] = 1;
+    ts = fe_zero();
+  }
+  uint32_t yw[8], tw[8];
+  fe_to_words_le(ys, yw);
+  fe_to_words_le(ts, tw);
+  // big-endian word order: word 0 is the most significant 32 bits
+  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
+  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
+  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
+  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
+  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
+  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
+  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
+  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+  __syncthreads();
+  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
+  uint4* dst = reinterpret_cast<uint4*>(out) + ((size_t)p0 << sh);
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * DX_THREADS + threadIdx.x;
+    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
+  }
+}
+
 // The virtual scalars of a folded launch (levels = k > 1): out[m][j n + i] = bits [j S, (j+1) S)
 // of scalar i of MSM m, wire layout (32 B, big-endian words, upper bits zero).  blockIdx.y = level
 // j, blockIdx.z = MSM of the batch (its wire scalars from scalar_sets.p[z], its k n virtual

@@ -578,16 +578,19 @@ const msm_bases* get_handle(napi_env env, napi_value v) {
   return reinterpret_cast<const msm_bases*>((uintptr_t)id);
 }
 
+// prepareBases(points, levels?, windowSize?, form?): with `form` (MSM_POINTS_X_*) the array holds
+// compressed points, 8 words each, and y is recovered on the device (msm_bases_create_compressed).
 napi_value PrepareBases(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value argv[3];
+  size_t argc = 4;
+  napi_value argv[4];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   const uint32_t* pts;
   size_t plen;
   if (argc < 1 || !get_u32_array(env, argv[0], &pts, &plen)) {
-    napi_throw_type_error(env, nullptr, "prepareBases(points: Uint32Array, levels?, windowSize?)");
+    napi_throw_type_error(env, nullptr, "prepareBases(points: Uint32Array, levels?, windowSize?, form?)");
     return nullptr;
   }
+  const uint32_t form = argc > 3 ? get_window(env, argv[3]) : 0;
   msm_opts o;
   memset(&o, 0, sizeof(o));
   o.device = -1;
@@ -595,7 +598,8 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
   const uint32_t levels = argc > 1 ? get_window(env, argv[1]) : 0;
   msm_bases* h = nullptr;
   // synchronous: the points are read before this returns (upload and preparation, ~3 ms at 2^20)
-  int rc = msm_bases_create(pts, plen / 32, &o, levels, &h);
+  int rc = form ? msm_bases_create_compressed(pts, plen / 8, form, &o, levels, &h)
+                : msm_bases_create(pts, plen / 32, &o, levels, &h);
   if (rc != MSM_OK) return throw_rc(env, rc);
   msm_bases_info_t inf;
   rc = msm_bases_info(h, &inf);
@@ -613,6 +617,25 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_set_named_property(env, obj, f.name, v));
   }
   return obj;
+}
+
+// decompressPoints(xs: Uint32Array of n x 8 words, form) -> Uint32Array of n x 32 wire words
+// (msm_decompress_points; synchronous, as prepareBases is).
+napi_value DecompressPoints(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint32_t* xs;
+  size_t len;
+  if (argc < 2 || !get_u32_array(env, argv[0], &xs, &len)) {
+    napi_throw_type_error(env, nullptr, "decompressPoints(xs: Uint32Array, form)");
+    return nullptr;
+  }
+  const size_t n = len / 8;
+  std::vector<uint32_t> out(n * 32 + 1);
+  int rc = msm_decompress_points(xs, n, get_window(env, argv[1]), nullptr, out.data());
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  return make_u32(env, out.data(), n * 32);
 }
 
 // computeMsmPrepared(id, scalars[, first, indices]): with `first` (a number) or `indices` (a
@@ -855,6 +878,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"prepareBases", nullptr, PrepareBases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeMsmPrepared", nullptr, ComputeMsmPrepared, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"releaseBases", nullptr, ReleaseBases, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decompressPoints", nullptr, DecompressPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -20,6 +20,20 @@ export declare function prepare_bases(
   baseAffinePoints: BigIntPoint[] | U32ArrayPoint[] | Uint32Array,
   options?: { levels?: number; windowSize?: number }
 ): BasesHandle;
+// Compressed points: `form` "x" is Aleo's form, the x-coordinate alone (y: the root whose point lies in
+// the prime-order subgroup); "x_ysign" is x with y's sign (y > p - y) in bit 255 -- carried by a flat
+// Uint32Array of n x 8 big-endian words, or given as `signs` beside bigint x-coordinates.  y is
+// recovered on the GPU; an x of no such point throws with the library's code ("-4"; "-3" out of range).
+export type PointForm = "x" | "x_ysign";
+export declare function prepare_bases(
+  xs: bigint[] | Uint32Array,
+  options: { form: PointForm; signs?: boolean[]; levels?: number; windowSize?: number }
+): BasesHandle;
+// The same points as a flat Uint32Array of n x 32 wire words (x|y|t|z, z = 1), as compute_msm takes them.
+export declare function decompress_points(
+  xs: bigint[] | Uint32Array,
+  options?: { form?: PointForm; signs?: boolean[] }
+): Uint32Array;
 // With `subset` the MSM runs over a subset of the handle's bases and `scalars` gives its length m:
 // the range [first, first + m), or the bases indices[0..m) (each < handle.n, repeats allowed;
 // `first` must then be absent or 0).  An index or a range outside the handle rejects.

@@ -211,9 +211,50 @@ function scalarWords(scalars, bits) {
   return sb;
 }
 
+// Compressed points (include/msm.h MSM_POINTS_X_*): { form: "x" } takes Aleo's form, x alone -- a
+// bigint[] or a flat Uint32Array of n x 8 big-endian words -- and y is the root whose point lies in the
+// prime-order subgroup (what the reference's getPointFromX computes on the host, here on the GPU and
+// with an error, not -y, when neither root does).  { form: "x_ysign" } takes x with y's sign: a flat
+// array carries the flag in bit 255 of each x; for bigints { signs } (an array of booleans, true for
+// y > p - y) gives it and it is set here.  An x of no such point throws with the library's code
+// (-4, or -3 for an x out of range).
+const POINT_FORMS = { x: 1, x_ysign: 2 };
+function xWords(xs, form, signs) {
+  if (xs instanceof Uint32Array) {
+    if (signs !== undefined) throw new TypeError("options.signs: only with bigint x-coordinates");
+    return xs.subarray(0, Math.floor(xs.length / 8) * 8);
+  }
+  if (signs !== undefined && (form !== "x_ysign" || signs.length !== xs.length))
+    throw new TypeError('options.signs: one boolean per point, with form "x_ysign"');
+  const out = new Uint32Array(xs.length * 8);
+  xs.forEach((x, i) => {
+    wordsOf(x, out, 8 * i);
+    if (signs !== undefined) {
+      if (out[8 * i] >>> 31) throw new RangeError("x does not leave bit 255 free for the sign");
+      if (signs[i]) out[8 * i] = (out[8 * i] | 0x80000000) >>> 0;
+    }
+  });
+  return out;
+}
+function formCode(form) {
+  if (!Object.prototype.hasOwnProperty.call(POINT_FORMS, form))
+    throw new TypeError("options.form: one of " + Object.keys(POINT_FORMS).join(", "));
+  return POINT_FORMS[form];
+}
+
 export function prepare_bases(baseAffinePoints, options) {
   const levels = options && options.levels ? options.levels | 0 : 0;
+  if (options && options.form !== undefined && options.form !== null)
+    return addon.prepareBases(xWords(baseAffinePoints, options.form, options.signs), levels, windowFrom(options),
+                              formCode(options.form));
   return addon.prepareBases(pointWords(baseAffinePoints), levels, windowFrom(options));
+}
+
+// Compressed points -> a flat Uint32Array of n x 32 wire words (x|y|t|z, z = 1), which compute_msm
+// takes as it is.  Synchronous, as prepare_bases is.
+export function decompress_points(xs, options) {
+  const form = options && options.form !== undefined ? options.form : "x";
+  return addon.decompressPoints(xWords(xs, form, options ? options.signs : undefined), formCode(form));
 }
 
 // With a third argument the MSM runs over a subset of the handle's bases, and `scalars` gives its

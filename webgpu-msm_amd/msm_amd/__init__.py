@@ -175,6 +175,13 @@ def load() -> ctypes.CDLL:
         "msm_last_profile": ([ctypes.POINTER(MsmProfile)], ctypes.c_int),
         "msm_bases_create": ([vp, sz, optp, ctypes.c_uint32, ctypes.POINTER(vp)], ctypes.c_int),
         "msm_bases_create_device": ([vp, sz, optp, ctypes.c_uint32, vp, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_bases_create_compressed": ([vp, sz, ctypes.c_uint32, optp, ctypes.c_uint32, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_bases_create_compressed_device": ([vp, sz, ctypes.c_uint32, optp, ctypes.c_uint32, vp, ctypes.POINTER(vp)],
+                                               ctypes.c_int),
+        "msm_decompress_points": ([vp, sz, ctypes.c_uint32, optp, vp], ctypes.c_int),
+        "msm_decompress_points_device": ([vp, sz, ctypes.c_uint32, optp, vp, vp], ctypes.c_int),
+        "msm_compress_points": ([vp, sz, ctypes.c_uint32, vp], ctypes.c_int),
+        "msm_test_decompress_constants": ([u32p], ctypes.c_int),
         "msm_bases_destroy": ([vp], ctypes.c_int),
         "msm_bases_info": ([vp, ctypes.POINTER(BasesInfo)], ctypes.c_int),
         "msm_bases_compute": ([vp, vp, optp, u32p], ctypes.c_int),
@@ -226,7 +233,7 @@ def load() -> ctypes.CDLL:
         "msm_test_guard_plant": ([ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
-        if name.startswith(("msm_test_", "msm_bases_")) and not hasattr(L, name):
+        if name.startswith(("msm_test_", "msm_bases_", "msm_decompress_", "msm_compress_")) and not hasattr(L, name):
             continue  # a test hook or the handle API an older library variant (MSM_AMD_LIB A/B builds) predates
         f = getattr(L, name)
         f.argtypes = args
@@ -351,6 +358,85 @@ def points_to_wire(points) -> np.ndarray:
     for i, p in enumerate(pts):  # U32ArrayPoint: four BE u32[8]
         for j, k in enumerate(keys):
             out[i, 8 * j: 8 * j + 8] = np.asarray(get(p, k), dtype=np.uint32)
+    return out
+
+
+# Compressed point forms (include/msm.h MSM_POINTS_X_*): 8 BE words per point, x alone ("subgroup": y is
+# the root whose point is in the prime-order subgroup, Aleo's form) or x with y's sign in bit 255 ("ysign").
+POINT_FORMS = {"subgroup": 1, "ysign": 2}
+
+
+def _point_form(form) -> int:
+    if isinstance(form, str):
+        if form not in POINT_FORMS:
+            raise ValueError(f"unknown point form {form!r}: one of {sorted(POINT_FORMS)}")
+        return POINT_FORMS[form]
+    return int(form)
+
+
+def xs_to_wire(xs, form="subgroup", signs=None) -> np.ndarray:
+    """x-coordinates -> compressed points [n, 8] u32.  Python ints are packed as 8 BE words; for
+    form="ysign" `signs` gives each point's flag (y > p - y) and is set here, in bit 255 -- an x with
+    that bit already set does not fit the field and is passed through for the library to refuse.  An
+    [n, 8] uint32 array is taken as already marshalled (msm_compress_points' output, flags included);
+    `signs` must then be None."""
+    if isinstance(xs, np.ndarray) and xs.dtype != object:
+        if signs is not None:
+            raise ValueError("signs are for integer x-coordinates; a word array carries its own flags")
+        return np.ascontiguousarray(_u32(xs).reshape(-1, 8))
+    vals = [int(v) for v in xs]
+    if signs is not None:
+        if _point_form(form) != POINT_FORMS["ysign"]:
+            raise ValueError('signs need form="ysign"')
+        flags = [bool(f) for f in signs]
+        if len(flags) != len(vals):
+            raise ValueError("signs and xs differ in length")
+        for v in vals:
+            if v >> 255:
+                raise ValueError("x does not leave bit 255 free for the sign")
+        vals = [v | (int(f) << 255) for v, f in zip(vals, flags)]
+    if not vals:
+        return np.zeros((0, 8), dtype=np.uint32)
+    buf = b"".join(_int_be_words(v) for v in vals)
+    return np.frombuffer(buf, dtype=">u4").astype(np.uint32).reshape(-1, 8)
+
+
+def decompress_points(xs, form="subgroup", signs=None, device: int = -1) -> np.ndarray:
+    """Compressed points (anything xs_to_wire takes) -> wire points [n, 32], y recovered on the device
+    (msm_decompress_points).  MsmError -3 for an x out of range, -4 for an x of no such point."""
+    w = xs_to_wire(xs, form, signs)
+    out = np.zeros((w.shape[0], 32), dtype=np.uint32)
+    _check(load().msm_decompress_points(_ptr(w), w.shape[0], _point_form(form), _opts(None, None, device), _ptr(out)),
+           "msm_decompress_points")
+    return out
+
+
+def decompress_points_device(d_xs, n: int, d_points, form="subgroup", device: int = -1, stream: int = 0) -> None:
+    """The same between device buffers (torch tensors or raw pointers, 16-byte aligned): n x 8 words in,
+    n x 32 words out; complete on return."""
+    _check(load().msm_decompress_points_device(_dev_ptr(d_xs), n, _point_form(form), _opts(None, None, device),
+                                               _stream(stream, d_xs, d_points), _dev_ptr(d_points)),
+           "msm_decompress_points_device")
+
+
+def compress_points(points, form="subgroup") -> np.ndarray:
+    """Affine points -> compressed points [n, 8] (msm_compress_points, host only): wire points [n, 32]
+    with z = 1, [n, 16] x|y words, or (x, y) integer pairs.  Subgroup membership is not tested."""
+    if isinstance(points, np.ndarray) and points.dtype != object:
+        a = _u32(points)
+        if a.ndim != 2 or a.shape[1] not in (16, 32):
+            raise ValueError("points: [n, 32] wire words or [n, 16] x|y words")
+        if a.shape[1] == 32:
+            z = a[:, 24:32]
+            if a.shape[0] and not (np.all(z[:, :7] == 0) and np.all(z[:, 7] == 1)):
+                raise ValueError("compress_points takes affine points (z = 1)")
+        xy = np.ascontiguousarray(a[:, :16])
+    else:
+        pts = [(int(p[0]), int(p[1])) for p in points]
+        buf = b"".join(_int_be_words(x) + _int_be_words(y) for x, y in pts)
+        xy = np.frombuffer(buf, dtype=">u4").astype(np.uint32).reshape(-1, 16)
+    out = np.zeros((xy.shape[0], 8), dtype=np.uint32)
+    _check(load().msm_compress_points(_ptr(xy), xy.shape[0], _point_form(form), _ptr(out)), "msm_compress_points")
     return out
 
 
@@ -744,6 +830,30 @@ class Bases:
         h = ctypes.c_void_p()
         _check(load().msm_bases_create_device(_dev_ptr(d_points), n, _opts(window_size, None, device), int(levels),
                                               _stream(stream, d_points), ctypes.byref(h)), "msm_bases_create_device")
+        return cls(h.value or 0)
+
+    @classmethod
+    def from_x(cls, xs, form="subgroup", signs=None, levels: int = 0, window_size: Optional[int] = None,
+               device: int = -1) -> "Bases":
+        """Host compressed points (anything xs_to_wire takes): 32 bytes per point go up, y is recovered
+        on the device, and the handle is the one from_wire makes from the same points.  An x of no
+        point of the form fails here (MsmError -4), as does one out of range (-3)."""
+        w = xs_to_wire(xs, form, signs)
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_create_compressed(_ptr(w), w.shape[0], _point_form(form),
+                                                  _opts(window_size, None, device), int(levels), ctypes.byref(h)),
+               "msm_bases_create_compressed")
+        return cls(h.value or 0)
+
+    @classmethod
+    def from_x_device(cls, d_xs, n: int, form="subgroup", levels: int = 0, window_size: Optional[int] = None,
+                      device: int = -1, stream: int = 0) -> "Bases":
+        """Compressed points already in HBM (a torch tensor or a raw device pointer, 16-byte aligned)."""
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_create_compressed_device(_dev_ptr(d_xs), n, _point_form(form),
+                                                         _opts(window_size, None, device), int(levels),
+                                                         _stream(stream, d_xs), ctypes.byref(h)),
+               "msm_bases_create_compressed_device")
         return cls(h.value or 0)
 
     @property
@@ -1180,6 +1290,15 @@ def _test_wide_masks() -> Tuple[int, int, int, int]:
     o, op_ = _out(4)
     _check(load().msm_test_wide_masks(op_), "msm_test_wide_masks")
     return tuple(int(x) for x in o)
+
+
+def _test_decompress_constants() -> dict:
+    """k_decompress_x's constants as the library holds them (tests/test_sqrt_model.py recomputes them)."""
+    o, op = _out(28)
+    _check(load().msm_test_decompress_constants(op), "msm_test_decompress_constants")
+    le = lambda w: sum(int(v) << (32 * i) for i, v in enumerate(w))  # noqa: E731
+    return {"two_adicity": int(o[0]), "exp_words": int(o[1]), "order_bits": int(o[2]), "exp": le(o[3:11]),
+            "order": le(o[11:19]), "omega_mont_limbs": [int(v) for v in o[19:28]]}
 
 
 def _test_limb_op(name: str, a, b=None, neg=None) -> np.ndarray:
