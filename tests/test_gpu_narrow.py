@@ -17,6 +17,9 @@ from test_gpu_subset import _dev, _points
 pytestmark = pytest.mark.gpu
 
 N = 4097  # one past the recode workgroup's span: two workgroups, the second with one scalar; odd
+# two workgroups and even (paired 4-B code stores), the second of 38 scalars: at one and two words
+# (four scalars per lane) its last lane holds two, at three words and more every lane is full
+N_EVEN = 4134
 BITS = (1, 2, 8, 31, 32, 33, 63, 64, 65, 127, 128, 129, 224, 225, 253, 254, 256)
 WIDTHS = (None, 4, 13, 16, 17)  # 17 takes the 32-bit digit codes
 
@@ -67,20 +70,21 @@ def _scalars(b, m=N, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def _expected(b, seed=0):
-    return _oracle(_points(N), _scalars(b, N, seed))
+def _expected(b, seed=0, n=N):
+    return _oracle(_points(n), _scalars(b, n, seed))
 
 
 # ---- parity -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("b", BITS)
 def test_parity_with_oracle(b):
-    sc, exp = _scalars(b), _expected(b)
-    assert sc.shape == (N, _words(b))
-    d_sc = _dev(sc)
-    with M.Bases.from_wire(_points(N), levels=1) as h:
-        for c in WIDTHS:
-            assert h.compute(sc, window_size=c, scalar_bits=b) == exp, (b, c)
-            assert h.compute_device(d_sc, window_size=c, scalar_bits=b) == exp, (b, c)
+    for n in (N, N_EVEN):
+        sc, exp = _scalars(b, n), _expected(b, n=n)
+        assert sc.shape == (n, _words(b))
+        d_sc = _dev(sc)
+        with M.Bases.from_wire(_points(n), levels=1) as h:
+            for c in WIDTHS:
+                assert h.compute(sc, window_size=c, scalar_bits=b) == exp, (b, n, c)
+                assert h.compute_device(d_sc, window_size=c, scalar_bits=b) == exp, (b, n, c)
 
 
 @pytest.mark.parametrize("n", [1, 2])

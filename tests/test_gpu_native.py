@@ -19,7 +19,10 @@ pytestmark = pytest.mark.gpu
 
 TYPES = {"bit": 1, "u8": 8, "i8": 8, "u16": 16, "i16": 16, "u32": 32, "i32": 32, "u64": 64, "i64": 64}
 N = 4097  # one past the recode workgroup's span: two workgroups, the second with one scalar; odd
-SIZES = (1, 2, 31, 33, 4095, N)
+# two workgroups and even (paired 4-B code stores), the second of 38 scalars: a ragged last lane of two for u8 /
+# i8 and of six after one full lane for bit, full lanes for the two-per-lane types
+N_EVEN = 4134
+SIZES = (1, 2, 31, 33, 4095, N, N_EVEN)
 WIDTHS = (None, 4, 13, 17)  # 17 takes the 32-bit digit codes
 
 

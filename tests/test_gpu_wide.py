@@ -23,7 +23,8 @@ pytestmark = pytest.mark.gpu
 TYPES = {"u128": 128, "i128": 128, "u256": 256, "fr_mont": 256}
 R = M.FR_MODULUS
 N = 4097  # one past the recode workgroup's span: two workgroups, the second with one scalar; odd (no paired stores)
-SIZES = (1, 2, 3, 4095, N)
+N_EVEN = 4134  # two workgroups and even: paired 4-B code stores in every lane, the second workgroup's full lanes too
+SIZES = (1, 2, 3, 4095, N, N_EVEN)
 WIDTHS = (None, 4, 13, 17)  # 17 takes the 32-bit digit codes
 
 

@@ -98,25 +98,8 @@ void launch_recode_fixed(const MsmDims& d, const BatchPtrs& sc, void* digits, ui
     hipLaunchKernelGGL((k_recode_fixed<Q, NHI, false>), grid, dim3(RC_THREADS), lds, s, sc, d,
                        static_cast<uint16_t*>(digits), colsum);
 }
-// The narrow recode (MsmDims::sw): one k_recode_narrow instantiation per scalar word count and code
-// width, and its bias C = sum_w (2^(b_w - 1) - 1) 2^off_w over the launch's windows (the sum stays
-// below 2^(T - 1), so it fits the scalar's own words).
-template <typename T>
-const void* recode_narrow_fn(uint32_t sw) {
-  switch (sw) {
-    case 1: return reinterpret_cast<const void*>(&k_recode_narrow<T, 1>);
-    case 2: return reinterpret_cast<const void*>(&k_recode_narrow<T, 2>);
-    case 3: return reinterpret_cast<const void*>(&k_recode_narrow<T, 3>);
-    case 4: return reinterpret_cast<const void*>(&k_recode_narrow<T, 4>);
-    case 5: return reinterpret_cast<const void*>(&k_recode_narrow<T, 5>);
-    case 6: return reinterpret_cast<const void*>(&k_recode_narrow<T, 6>);
-    case 7: return reinterpret_cast<const void*>(&k_recode_narrow<T, 7>);
-    default: return reinterpret_cast<const void*>(&k_recode_narrow<T, 8>);
-  }
-}
-const void* recode_narrow_kernel(const MsmDims& d) {
-  return d.c > 16 ? recode_narrow_fn<uint32_t>(d.sw) : recode_narrow_fn<uint16_t>(d.sw);
-}
+// The bias C = sum_w (2^(b_w - 1) - 1) 2^off_w of the narrow, native and wide recodes over the
+// launch's windows (the sum stays below 2^(T - 1), so it fits the scalar's own words).
 NarrowBias narrow_bias(const MsmDims& d) {
   NarrowBias nb{};
   for (uint32_t w = 0; w < d.Wr; w++) {
@@ -132,41 +115,45 @@ NarrowBias narrow_bias(const MsmDims& d) {
   return nb;
 }
 
-// The native recode (Plan::stype): one k_recode_native instantiation per element width, signedness
-// and code width.  MSM_SCALAR_U32 has the bytes of the one-word narrow format: k_recode_narrow<T, 1>.
-template <typename T>
-const void* recode_native_fn(uint32_t stype) {
-  switch (stype) {
-    case MSM_SCALAR_BIT: return reinterpret_cast<const void*>(&k_recode_native<T, 1, false>);
-    case MSM_SCALAR_U8: return reinterpret_cast<const void*>(&k_recode_native<T, 8, false>);
-    case MSM_SCALAR_I8: return reinterpret_cast<const void*>(&k_recode_native<T, 8, true>);
-    case MSM_SCALAR_U16: return reinterpret_cast<const void*>(&k_recode_native<T, 16, false>);
-    case MSM_SCALAR_I16: return reinterpret_cast<const void*>(&k_recode_native<T, 16, true>);
-    case MSM_SCALAR_I32: return reinterpret_cast<const void*>(&k_recode_native<T, 32, true>);
-    case MSM_SCALAR_U64: return reinterpret_cast<const void*>(&k_recode_native<T, 64, false>);
-    case MSM_SCALAR_I64: return reinterpret_cast<const void*>(&k_recode_native<T, 64, true>);
-    default: return reinterpret_cast<const void*>(&k_recode_narrow<T, 1>);  // MSM_SCALAR_U32
-  }
-}
-constexpr uint32_t NATIVE_TYPES[] = {MSM_SCALAR_BIT, MSM_SCALAR_U8,  MSM_SCALAR_U16, MSM_SCALAR_U32, MSM_SCALAR_U64,
-                                     MSM_SCALAR_I8,  MSM_SCALAR_I16, MSM_SCALAR_I32, MSM_SCALAR_I64};
-// The wide recode (Plan::stype with STYPE_WIDE, narrow geometry): one k_recode_wide instantiation per
-// element kind and code width.
-template <typename T>
-const void* recode_wide_fn(uint32_t stype) {
-  switch (stype) {
-    case STYPE_U128: return reinterpret_cast<const void*>(&k_recode_wide<T, 4, WIDE_U>);
-    case STYPE_I128: return reinterpret_cast<const void*>(&k_recode_wide<T, 4, WIDE_I>);
-    case STYPE_FR_MONT: return reinterpret_cast<const void*>(&k_recode_wide<T, 8, WIDE_MONT>);
-    default: return reinterpret_cast<const void*>(&k_recode_wide<T, 8, WIDE_U>);  // STYPE_U256
-  }
-}
-constexpr uint32_t WIDE_TYPES[] = {STYPE_U128, STYPE_I128, STYPE_U256, STYPE_FR_MONT};
-// The recode kernel of a narrow, native or wide plan (all take k_recode_narrow's six arguments).
+// The biased recode kernels (all take k_recode_narrow's six arguments): a row per scalar format -- the
+// narrow word counts (Plan::stype 0, MsmDims::sw), the native types and the wide kinds (Plan::stype) --
+// and a column per code width.  MSM_SCALAR_U32 has the bytes of the one-word narrow format.
+struct RecodeRow {
+  uint32_t stype, sw;
+  const void* fn[2];  // 16-bit codes, 32-bit codes (c > 16)
+};
+#define RECODE_ROW(stype, sw, K, ...)                                        \
+  {stype, sw, {reinterpret_cast<const void*>(&K<uint16_t, __VA_ARGS__>), \
+               reinterpret_cast<const void*>(&K<uint32_t, __VA_ARGS__>)}}
+const RecodeRow RECODE_TABLE[] = {
+    RECODE_ROW(0, 1, k_recode_narrow, 1),
+    RECODE_ROW(0, 2, k_recode_narrow, 2),
+    RECODE_ROW(0, 3, k_recode_narrow, 3),
+    RECODE_ROW(0, 4, k_recode_narrow, 4),
+    RECODE_ROW(0, 5, k_recode_narrow, 5),
+    RECODE_ROW(0, 6, k_recode_narrow, 6),
+    RECODE_ROW(0, 7, k_recode_narrow, 7),
+    RECODE_ROW(0, 8, k_recode_narrow, 8),
+    RECODE_ROW(MSM_SCALAR_BIT, 0, k_recode_native, 1, false),
+    RECODE_ROW(MSM_SCALAR_U8, 0, k_recode_native, 8, false),
+    RECODE_ROW(MSM_SCALAR_I8, 0, k_recode_native, 8, true),
+    RECODE_ROW(MSM_SCALAR_U16, 0, k_recode_native, 16, false),
+    RECODE_ROW(MSM_SCALAR_I16, 0, k_recode_native, 16, true),
+    RECODE_ROW(MSM_SCALAR_U32, 0, k_recode_narrow, 1),
+    RECODE_ROW(MSM_SCALAR_I32, 0, k_recode_native, 32, true),
+    RECODE_ROW(MSM_SCALAR_U64, 0, k_recode_native, 64, false),
+    RECODE_ROW(MSM_SCALAR_I64, 0, k_recode_native, 64, true),
+    RECODE_ROW(STYPE_U128, 0, k_recode_wide, 4, WIDE_U),
+    RECODE_ROW(STYPE_I128, 0, k_recode_wide, 4, WIDE_I),
+    RECODE_ROW(STYPE_U256, 0, k_recode_wide, 8, WIDE_U),
+    RECODE_ROW(STYPE_FR_MONT, 0, k_recode_wide, 8, WIDE_MONT),
+};
+#undef RECODE_ROW
+// The recode kernel of a narrow, native or wide plan.
 const void* recode_kernel(const Plan& pl) {
-  if (!pl.stype) return recode_narrow_kernel(pl.d);
-  if (stype_wide(pl.stype)) return pl.d.c > 16 ? recode_wide_fn<uint32_t>(pl.stype) : recode_wide_fn<uint16_t>(pl.stype);
-  return pl.d.c > 16 ? recode_native_fn<uint32_t>(pl.stype) : recode_native_fn<uint16_t>(pl.stype);
+  for (const RecodeRow& r : RECODE_TABLE)
+    if (r.stype == pl.stype && (pl.stype || r.sw == pl.d.sw)) return r.fn[pl.d.c > 16];
+  return nullptr;  // (make_plan admits no other type)
 }
 
 void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
@@ -205,6 +192,8 @@ void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* 
   hipLaunchKernelGGL(k_recode_hist<uint16_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint16_t*>(digits),
                      colsum);
 }
+// Every recode kernel: a replayed graph must not read the previous call's scalars, whatever their
+// format.
 bool is_recode_kernel(const void* f) {
   const void* ks[] = {reinterpret_cast<const void*>(&k_recode_hist<uint32_t>),
                       reinterpret_cast<const void*>(&k_recode_hist<uint16_t>),
@@ -220,14 +209,8 @@ bool is_recode_kernel(const void* f) {
                       reinterpret_cast<const void*>(&k_recode_fixed<12, 14, false>)};
   for (const void* k : ks)
     if (f == k) return true;
-  // the narrow recodes too: a replayed graph must not read the previous call's scalars
-  for (uint32_t sw = 1; sw <= 8; sw++)
-    if (f == recode_narrow_fn<uint16_t>(sw) || f == recode_narrow_fn<uint32_t>(sw)) return true;
-  // and every native one: the same trap
-  for (uint32_t ty : NATIVE_TYPES)
-    if (f == recode_native_fn<uint16_t>(ty) || f == recode_native_fn<uint32_t>(ty)) return true;
-  for (uint32_t ty : WIDE_TYPES)
-    if (f == recode_wide_fn<uint16_t>(ty) || f == recode_wide_fn<uint32_t>(ty)) return true;
+  for (const RecodeRow& r : RECODE_TABLE)
+    if (f == r.fn[0] || f == r.fn[1]) return true;
   return false;
 }
 

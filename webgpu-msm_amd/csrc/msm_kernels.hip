@@ -8,12 +8,15 @@
 //   k_recode_hist      signed c-bit digits per scalar (window-carry recoding, |d| <= 2^(c-1)),
 //                      written window-major (= first sort level: one contiguous array per window),
 //                      with the coarse-bin totals (LDS histogram, flushed with global atomics);
-//                      k_recode_narrow is the same for scalars of 1..8 words over the windows of
-//                      their own bits (msm_bases_compute* with MSM_FLAG_SCALAR_BITS), and
-//                      k_recode_native for the caller's own integer arrays (bit / 8 / 16 / 32 / 64-bit
-//                      elements, signed ones included: MSM_FLAG_SCALAR_TYPE), k_recode_wide for
-//                      little-endian 128- / 256-bit integers and Montgomery-form Fr (MSM_FLAG_SCALAR_FIELD;
-//                      k_recode_hist_le where a 256-bit integer takes the full-width geometry)
+//                      k_recode_fixed is the same with the common geometries at compile time.  Three
+//                      more recode over the windows of the scalars' own bits, each a load of its own
+//                      around one shared bias-add and window loop (bias_add, recode_windows):
+//                      k_recode_narrow for scalars of 1..8 words (MSM_FLAG_SCALAR_BITS), k_recode_native
+//                      for the caller's own integer arrays (bit / 8 / 16 / 32 / 64-bit elements, signed
+//                      ones included: MSM_FLAG_SCALAR_TYPE), k_recode_wide for little-endian 128- /
+//                      256-bit integers and Montgomery-form Fr (MSM_FLAG_SCALAR_FIELD; k_recode_hist_le,
+//                      k_recode_hist's body on little-endian words, where a 256-bit integer takes the
+//                      full-width geometry)
 //   k_part_scatter     digits -> coarse bins (each chunk reserves and writes one contiguous slice
 //                      per bin); its range / indexed variants map a subset launch's positions to
 //                      a handle's records (k_stage_indices checks a device caller's indices first)
@@ -846,10 +849,52 @@ __device__ __forceinline__ void flush_hist(uint32_t* lds_hist, const MsmDims& d,
   if (threadIdx.x < d.Wr && wt[threadIdx.x]) atomicAdd(&colsum[d.nbins + w0 + threadIdx.x], wt[threadIdx.x]);
 }
 
-// Pass 0+1 (fused), blockIdx.y = MSM of the batch: scalars from scalar_sets.p[y], digits into its
-// windows [y Wr, (y+1) Wr).  Carries only climb, so windows below the launch's range [d.w0, d.w0 +
-// d.Wr) are recoded for their carries (the generic loop stops at the range's top); only the range
-// is written and counted.  The generic form (`recode`) serves any geometry.
+// The frame every recode kernel shares.  recode_begin zeroes the LDS histogram [Wr][nbc] and the
+// window totals after it; recode_end reports a lane's out-of-range scalar (`bad`, the kernels that
+// take `err`) and flushes the histogram.  (k_recode_hist and k_recode_fixed spell the end out: a
+// phase probe stands between its barrier and its flush.)
+__device__ __forceinline__ void recode_begin(uint32_t* lds_hist, const MsmDims& d) {
+  for (uint32_t b = threadIdx.x; b < d.Wr * d.nbc + d.Wr; b += RC_THREADS) lds_hist[b] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void recode_end(uint32_t* lds_hist, const MsmDims& d, uint32_t w0,
+                                           uint32_t* __restrict__ colsum, bool bad = false,
+                                           uint32_t* __restrict__ err = nullptr) {
+  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  __syncthreads();
+  flush_hist(lds_hist, d, w0, colsum);
+}
+
+// One scalar of the carry recodes (k_recode_hist, k_recode_hist_le): s is scalar i's little-endian
+// words.  Carries only climb, so windows below the launch's range [d.w0, d.w0 + d.Wr) are recoded
+// for their carries (the generic loop stops at the range's top); only the range is written and
+// counted.  HALF: the range may end in half windows (never on the little-endian launch, and the
+// test cost it a third of its time).
+template <typename T, bool HALF>
+__device__ __forceinline__ void recode_carry(uint32_t s[8], uint32_t i, const MsmDims& d, uint32_t w0,
+                                             T* __restrict__ digits, uint32_t* lds_hist) {
+  recode(s, d, [&](uint32_t wa, int32_t digit) {
+    const uint32_t w = wa - d.w0;  // local window (wraps to >= Wr below the range)
+    if (w >= d.Wr) return;
+    uint32_t code = DigitCode<T>::ZERO;
+    if (digit != 0) {
+      const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+      // half windows at the range's ends: a bucket outside the kept half is another share's
+      const uint32_t hb = 1u << (win_bits(d, wa) - 2);
+      if (HALF && ((w == 0 && d.half_lo && mag < hb) || (w + 1 == d.Wr && d.half_hi && mag >= hb))) {
+        digits[(size_t)(w0 + w) * d.n + i] = (T)code;
+        return;
+      }
+      code = mag | (digit < 0 ? DigitCode<T>::SIGN : 0u);
+      atomicAdd(&lds_hist[w * d.nbc + (mag >> win_fb(d, wa))], 1u);
+    }
+    digits[(size_t)(w0 + w) * d.n + i] = (T)code;
+  });
+}
+
+// Pass 0+1 (fused), blockIdx.y = MSM of the batch: scalars from scalar_sets.p[y] (8 big-endian
+// words each), digits into its windows [y Wr, (y+1) Wr).  The generic form (`recode`, through
+// recode_carry) serves any geometry.
 template <typename T>
 __global__ void __launch_bounds__(RC_THREADS) k_recode_hist(BatchPtrs scalar_sets, MsmDims d,
                                                             T* __restrict__ digits, uint32_t* __restrict__ colsum) {
@@ -857,34 +902,16 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_hist(BatchPtrs scalar_set
   const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
   const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
   const uint32_t w0 = blockIdx.y * d.Wr;
-  const uint32_t nh = d.Wr * d.nbc;
   [[maybe_unused]] const uint32_t pwg = blockIdx.y * gridDim.x + blockIdx.x;
   PROBE(0, pwg, 0);
-  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
-  __syncthreads();
+  recode_begin(lds_hist, d);
   PROBE(0, pwg, 1);
   // (loading all of a lane's scalars before recoding any measured slower: 43 vs 37 us per
   // two-MSM 2^20 launch)
   for (uint32_t i = lo + threadIdx.x; i < hi; i += RC_THREADS) {
     uint32_t s[8];
     load_scalar(scalars, i, s);
-    recode(s, d, [&](uint32_t wa, int32_t digit) {
-      const uint32_t w = wa - d.w0;  // local window (wraps to >= Wr below the range)
-      if (w >= d.Wr) return;
-      uint32_t code = DigitCode<T>::ZERO;
-      if (digit != 0) {
-        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
-        // half windows at the range's ends: a bucket outside the kept half is another share's
-        const uint32_t hb = 1u << (win_bits(d, wa) - 2);
-        if ((w == 0 && d.half_lo && mag < hb) || (w + 1 == d.Wr && d.half_hi && mag >= hb)) {
-          digits[(size_t)(w0 + w) * d.n + i] = (T)code;
-          return;
-        }
-        code = mag | (digit < 0 ? DigitCode<T>::SIGN : 0u);
-        atomicAdd(&lds_hist[w * d.nbc + (mag >> win_fb(d, wa))], 1u);
-      }
-      digits[(size_t)(w0 + w) * d.n + i] = (T)code;
-    });
+    recode_carry<T, true>(s, i, d, w0, digits, lds_hist);
   }
   __syncthreads();
   PROBE(0, pwg, 2);
@@ -997,123 +1024,142 @@ __global__ void __launch_bounds__(RC_THREADS, 8) k_recode_fixed(BatchPtrs scalar
   PROBE(0, pwg, 7);
 }
 
+// A lane's run of LW adjacent words at p.  `vec`: as 16-B vector loads (8-B where LW is no multiple of
+// 4; a single word is one load either way) -- the caller vouches for the run's alignment; else word by
+// word, the first nw of them, zeros after.
+template <uint32_t LW>
+__device__ __forceinline__ void load_words(uint32_t (&raw)[LW], const uint32_t* p, bool vec, uint32_t nw) {
+  if (vec && LW % 4 == 0) {
+#pragma unroll
+    for (uint32_t k = 0; k < LW / 4; k++) {
+      const uint4 v = reinterpret_cast<const uint4*>(p)[k];
+      raw[4 * k] = v.x, raw[4 * k + 1] = v.y, raw[4 * k + 2] = v.z, raw[4 * k + 3] = v.w;
+    }
+  } else if (vec && LW % 2 == 0) {
+#pragma unroll
+    for (uint32_t k = 0; k < LW / 2; k++) {
+      const uint2 v = reinterpret_cast<const uint2*>(p)[k];
+      raw[2 * k] = v.x, raw[2 * k + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    // (from the top word down: in ascending order the compiler shares the first words' loads between
+    // the two paths and cuts the vector loads into words and 12-B pieces to do so)
+    for (uint32_t k = LW; k-- > 0;) raw[k] = k < nw ? p[k] : 0u;
+  }
+}
+
+// The biased recodes -- k_recode_narrow, k_recode_native, k_recode_wide -- are the bias-add form of
+// k_recode_fixed with the geometry at run time: the launch's own balanced windows [0, d.Wr) of q + 1 /
+// q bits that sum to T = max(sbits + 1, 4) bits, no overflow window.  Each kernel loads its format and
+// forms magnitudes of SW little-endian words below 2^sbits -- bits at or above sbits are masked off
+// and reported (MSM_DEV_ERR_SCALAR_RANGE in the slot's err word), so the digits stay inside their
+// windows and the launch runs to its end -- and a sign; the two helpers below do the rest.
+//
+// t = m + C (C from the host, NarrowBias) makes the windows independent, and since the widths sum to
+// more than sbits the top window's top bit is clear before the add, so t < 2^T and nothing carries
+// out.  t is SW + 1 words (T may be 32 SW + 1).
+template <uint32_t SW>
+__device__ __forceinline__ void bias_add(const uint32_t (&m)[SW], const NarrowBias& bias, uint32_t (&t)[SW + 1]) {
+  uint32_t cy = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < SW; k++) {
+    const uint64_t x = (uint64_t)m[k] + bias.v[k] + cy;
+    t[k] = (uint32_t)x;
+    cy = (uint32_t)(x >> 32);
+  }
+  t[SW] = cy;
+}
+// The windows of CH adjacent scalars, the first `cnt` of them live (cnt >= 1; more than CH is CH): t is
+// shifted down one window at a time -- SW funnel shifts by a uniform amount per window, which is what
+// a run-time geometry costs without indexing the register array dynamically (see `recode`).  The
+// histogram counts by magnitude; the scalar's sign is one XOR into the digit's: code sign =
+// (digit < 0) != neg[r].  `row` is the scalars' place in the launch's first window; 16-bit codes go out
+// in pairs as k_recode_fixed's do.
+template <typename T, uint32_t SW, uint32_t CH>
+__device__ __forceinline__ void recode_windows(uint32_t (&t)[CH][SW + 1], const bool (&neg)[CH], uint32_t cnt,
+                                               T* __restrict__ row, uint32_t* h, const MsmDims& d) {
+  using DC = DigitCode<T>;
+  static_assert(CH % 2 == 0, "codes are stored two at a time");
+  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;  // every row stays 4-B aligned
+  for (uint32_t w = 0; w < d.Wr; w++) {
+    const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
+    const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
+    const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
+    uint32_t code[CH];
+#pragma unroll
+    for (uint32_t r = 0; r < CH; r++) {
+      const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
+#pragma unroll
+      for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
+      t[r][SW] >>= b;
+      const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
+      const bool live = digit != 0 && r < cnt;
+      // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
+      atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
+      code[r] = live ? mag | ((digit < 0) != neg[r] ? DC::SIGN : 0u) : DC::ZERO;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < CH; r += 2) {
+      if (pair_store && r + 1 < cnt) {
+        *reinterpret_cast<uint32_t*>(row + r) = code[r] | code[r + 1] << 16;
+      } else {
+        if (r < cnt) row[r] = (T)code[r];
+        if (r + 1 < cnt) row[r + 1] = (T)code[r + 1];
+      }
+    }
+    row += d.n;
+    h += d.nbc;
+  }
+}
+
 // Narrow scalars (MsmDims::sw words of MsmDims::sbits bits each, big-endian words like the 8-word
-// format) over the launch's own balanced geometry: windows [0, d.Wr) of q + 1 / q bits that sum to
-// T = max(sbits + 1, 4) bits, no overflow window.  The bias-add form of k_recode_fixed with the
-// geometry at run time: t = s + C (C from the host, NarrowBias) makes the windows independent, and
-// since the widths sum to more than sbits the top window's top bit is clear before the add, so t
-// < 2^T and nothing carries out.  t is SW + 1 words (T may be 32 SW + 1) and is shifted down one
-// window at a time -- SW funnel shifts by a uniform amount per window, which is what a run-time
-// geometry costs without indexing the register array dynamically (see `recode`).
-// A lane takes R adjacent scalars (16 or 32 B at one or two words each, so a wave's loads are whole
-// cache lines; two scalars at three words and more) as vector loads where the MSM's scalar
-// pointer is 16-B aligned, and stores their 16-bit codes in pairs as k_recode_fixed does.
-// Bits at or above sbits are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE in the slot's err
-// word), so the digits stay inside their windows and the launch runs to its end.
+// format; no sign).  A lane takes R adjacent scalars (16 or 32 B at one or two words each, so a wave's
+// loads are whole cache lines; two scalars at three words and more) as vector loads where the MSM's
+// scalar pointer is 16-B aligned.  Only the most significant word can hold bits at or above sbits.
 template <typename T, uint32_t SW>
 __global__ void __launch_bounds__(RC_THREADS) k_recode_narrow(BatchPtrs scalar_sets, MsmDims d,
                                                               T* __restrict__ digits, uint32_t* __restrict__ colsum,
                                                               NarrowBias bias, uint32_t* __restrict__ err) {
-  using DC = DigitCode<T>;
   constexpr uint32_t R = SW <= 2 ? 4 : 2;  // scalars per lane
   constexpr uint32_t LW = R * SW;          // words per lane
   extern __shared__ uint32_t lds_hist[];   // [Wr][nbc]
   const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
   const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
   const uint32_t w0 = blockIdx.y * d.Wr;
-  const uint32_t nh = d.Wr * d.nbc;
-  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
   // value bits of the most significant word
   const uint32_t top_mask = (d.sbits & 31u) ? (1u << (d.sbits & 31u)) - 1u : 0xffffffffu;
   const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
-  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
+  const bool neg[R] = {};
   bool bad = false;
-  __syncthreads();
+  recode_begin(lds_hist, d);
   for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
     const uint32_t cnt = min(R, hi - i);
     uint32_t raw[LW];
-    const uint32_t* p = scalars + (size_t)i * SW;
-    if (cnt == R && vec) {
-      // lane runs are LW * 4 bytes apart: 16-B aligned when LW is a multiple of 4, else 8-B
-      if (LW % 4 == 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < LW / 4; k++) {
-          const uint4 v = reinterpret_cast<const uint4*>(p)[k];
-          raw[4 * k] = v.x, raw[4 * k + 1] = v.y, raw[4 * k + 2] = v.z, raw[4 * k + 3] = v.w;
-        }
-      } else {
-#pragma unroll
-        for (uint32_t k = 0; k < LW / 2; k++) {
-          const uint2 v = reinterpret_cast<const uint2*>(p)[k];
-          raw[2 * k] = v.x, raw[2 * k + 1] = v.y;
-        }
-      }
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < LW; k++) raw[k] = k < cnt * SW ? p[k] : 0u;
-    }
+    load_words(raw, scalars + (size_t)i * SW, cnt == R && vec, cnt * SW);
     uint32_t t[R][SW + 1];
 #pragma unroll
     for (uint32_t r = 0; r < R; r++) {
       bad = bad || (raw[r * SW] & ~top_mask) != 0;
       raw[r * SW] &= top_mask;
-      uint32_t cy = 0;
+      uint32_t m[SW];
 #pragma unroll
-      for (uint32_t k = 0; k < SW; k++) {  // big-endian words: raw[r SW] is the most significant
-        const uint64_t x = (uint64_t)raw[r * SW + SW - 1 - k] + bias.v[k] + cy;
-        t[r][k] = (uint32_t)x;
-        cy = (uint32_t)(x >> 32);
-      }
-      t[r][SW] = cy;
+      for (uint32_t k = 0; k < SW; k++) m[k] = raw[r * SW + SW - 1 - k];  // raw[r SW] is the most significant
+      bias_add(m, bias, t[r]);
     }
-    T* row = digits + (size_t)w0 * d.n + i;
-    uint32_t* h = lds_hist;
-    for (uint32_t w = 0; w < d.Wr; w++) {
-      const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
-      const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
-      const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
-      uint32_t code[R];
-#pragma unroll
-      for (uint32_t r = 0; r < R; r++) {
-        const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
-#pragma unroll
-        for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
-        t[r][SW] >>= b;
-        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
-        const bool live = digit != 0 && r < cnt;
-        // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
-        atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
-        code[r] = live ? mag | (digit < 0 ? DC::SIGN : 0u) : DC::ZERO;
-      }
-#pragma unroll
-      for (uint32_t r = 0; r < R; r += 2) {
-        if (pair_store && r + 1 < cnt) {
-          *reinterpret_cast<uint32_t*>(row + r) = code[r] | code[r + 1] << 16;
-        } else {
-          if (r < cnt) row[r] = (T)code[r];
-          if (r + 1 < cnt) row[r + 1] = (T)code[r + 1];
-        }
-      }
-      row += d.n;
-      h += d.nbc;
-    }
+    recode_windows<T, SW, R>(t, neg, cnt, digits + (size_t)w0 * d.n + i, lds_hist, d);
   }
-  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
-  __syncthreads();
-  flush_hist(lds_hist, d, w0, colsum);
+  recode_end(lds_hist, d, w0, colsum, bad, err);
 }
 
 // Native integer scalars (msm_opts_typed, MSM_FLAG_SCALAR_TYPE): the vector is the caller's own array
 // of E-bit elements -- E = 1: bit (i & 7) of byte (i >> 3); 8 / 16 / 32 / 64: little-endian integers,
-// two's complement when SIGNED -- over the narrow geometry of d.sbits = b <= E magnitude bits.
-// k_recode_narrow's bias-add and per-window shift on SW + 1 words (SW = 2 at 64 bits, else 1) of the
-// magnitude |v|, formed in unsigned arithmetic so that -2^(E-1) is 2^(E-1); the scalar's sign is one
-// XOR into the digit's: code sign = (digit < 0) != (v < 0).  The histogram counts by magnitude as ever.
+// two's complement when SIGNED -- of d.sbits = b <= E magnitude bits.  The magnitude |v| is SW words
+// (SW = 2 at 64 bits, else 1), formed in unsigned arithmetic so that -2^(E-1) is 2^(E-1).
 // A lane takes one 32-bit word of bit / 8 / 16-bit elements (32 / 4 / 2 scalars) or 16 B of 32 /
 // 64-bit ones (4 / 2 scalars; word by word where the vector is only 4-B aligned), so a wave reads
 // whole cache lines, and recodes them four at a time.  The lanes that hold the tail of the workgroup's
 // span or of the vector read element by element: nothing past byte ceil(n E / 8) is touched.
-// Magnitude bits at or above b are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE).
 template <uint32_t E>
 __device__ __forceinline__ uint64_t native_elem(const uint32_t* __restrict__ scalars, uint32_t i) {
   if (E == 1) return (reinterpret_cast<const uint8_t*>(scalars)[i >> 3] >> (i & 7u)) & 1u;
@@ -1126,7 +1172,6 @@ template <typename T, uint32_t E, bool SIGNED>
 __global__ void __launch_bounds__(RC_THREADS) k_recode_native(BatchPtrs scalar_sets, MsmDims d,
                                                               T* __restrict__ digits, uint32_t* __restrict__ colsum,
                                                               NarrowBias bias, uint32_t* __restrict__ err) {
-  using DC = DigitCode<T>;
   constexpr uint32_t SW = E == 64 ? 2 : 1;                     // words of a magnitude
   constexpr uint32_t R = E <= 16 ? 32 / E : E == 32 ? 4 : 2;   // scalars per lane
   constexpr uint32_t LW = E <= 16 ? 1 : 4;                     // words per lane
@@ -1137,26 +1182,15 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_native(BatchPtrs scalar_s
   const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
   const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
   const uint32_t w0 = blockIdx.y * d.Wr;
-  const uint32_t nh = d.Wr * d.nbc;
-  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
   const uint64_t mag_mask = d.sbits >= 64 ? ~0ull : (1ull << d.sbits) - 1ull;
   const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
-  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
   bool bad = false;
-  __syncthreads();
+  recode_begin(lds_hist, d);
   for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
     const uint32_t cnt = min(R, hi - i);
     uint32_t raw[LW] = {};
-    if (cnt == R) {  // (i is a multiple of R: the lane's words start at word i E / 32)
-      const uint32_t* p = scalars + ((size_t)i * E >> 5);
-      if (LW == 4 && vec) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        raw[0] = v.x, raw[1 % LW] = v.y, raw[2 % LW] = v.z, raw[3 % LW] = v.w;
-      } else {
-#pragma unroll
-        for (uint32_t k = 0; k < LW; k++) raw[k] = p[k];
-      }
-    }
+    // (i is a multiple of R: a whole lane's words start at word i E / 32)
+    if (cnt == R) load_words(raw, scalars + ((size_t)i * E >> 5), vec, LW);
     for (uint32_t g = 0; g < R; g += CH) {
       if (g >= cnt) break;
       uint32_t t[CH][SW + 1];
@@ -1178,70 +1212,31 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_native(BatchPtrs scalar_s
         if (neg[r]) v = (0ull - v) & (~0ull >> (64 - E));
         bad = bad || (v & ~mag_mask) != 0;
         v &= mag_mask;
-        uint32_t cy = 0;
+        uint32_t m[SW];
 #pragma unroll
-        for (uint32_t k = 0; k < SW; k++) {
-          const uint64_t x = (uint64_t)(uint32_t)(v >> (32 * k)) + bias.v[k] + cy;
-          t[r][k] = (uint32_t)x;
-          cy = (uint32_t)(x >> 32);
-        }
-        t[r][SW] = cy;
+        for (uint32_t k = 0; k < SW; k++) m[k] = (uint32_t)(v >> (32 * k));
+        bias_add(m, bias, t[r]);
       }
-      T* row = digits + (size_t)w0 * d.n + i + g;
-      uint32_t* h = lds_hist;
-      for (uint32_t w = 0; w < d.Wr; w++) {
-        const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
-        const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
-        const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
-        uint32_t code[CH];
-#pragma unroll
-        for (uint32_t r = 0; r < CH; r++) {
-          const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
-#pragma unroll
-          for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
-          t[r][SW] >>= b;
-          const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
-          const bool live = digit != 0 && g + r < cnt;
-          // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
-          atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
-          code[r] = live ? mag | ((digit < 0) != neg[r] ? DC::SIGN : 0u) : DC::ZERO;
-        }
-#pragma unroll
-        for (uint32_t r = 0; r < CH; r += 2) {
-          if (CH > 1 && pair_store && g + r + 1 < cnt) {
-            *reinterpret_cast<uint32_t*>(row + r) = code[r] | code[(r + 1) % CH] << 16;
-          } else {
-            if (g + r < cnt) row[r] = (T)code[r];
-            if (CH > 1 && g + r + 1 < cnt) row[r + 1] = (T)code[(r + 1) % CH];
-          }
-        }
-        row += d.n;
-        h += d.nbc;
-      }
+      recode_windows<T, SW, CH>(t, neg, cnt - g, digits + (size_t)w0 * d.n + i + g, lds_hist, d);
     }
   }
-  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
-  __syncthreads();
-  flush_hist(lds_hist, d, w0, colsum);
+  recode_end(lds_hist, d, w0, colsum, bad, err);
 }
 
 // Wide scalars (msm_opts_typed.scalar_field, MSM_FLAG_SCALAR_FIELD): elements of SW = 4 or 8 LITTLE-endian
-// words -- u128 / i128, u256 (arkworks BigInt<4>) and Fr in Montgomery form -- over the narrow geometry
-// of d.sbits = b <= 253 magnitude bits.  The body is k_recode_narrow's bias-add and per-window funnel
-// shift; what differs is the word order at the load (word 0 is the least significant), for WIDE_I the
-// magnitude and sign XOR of k_recode_native (|v| in 128-bit unsigned arithmetic, so -2^127 is 2^127), and
-// for WIDE_MONT fr_from_mont (fr.cuh: v = a 2^-256 mod r, 8 rounds of word REDC) ahead of the bias-add,
-// with a >= r reported.  A lane takes R = 2 adjacent scalars, 32 or 64 B, as 16-B vector loads where the
-// vector is 16-B aligned and word by word where it is only 4-B aligned; the lane that holds the odd
-// tail of the span reads only its own scalar's words, so nothing past byte n SW 4 is touched.
-// Magnitude bits at or above b are masked off and reported (MSM_DEV_ERR_SCALAR_RANGE); REDC's output is
-// below r whatever a was, and is masked like the rest, so every digit stays inside its window.
+// words -- u128 / i128, u256 (arkworks BigInt<4>) and Fr in Montgomery form -- of d.sbits = b <= 253
+// magnitude bits.  Word 0 is the least significant; WIDE_I takes the magnitude and sign as
+// k_recode_native does (|v| in 128-bit unsigned arithmetic, so -2^127 is 2^127), and WIDE_MONT runs
+// fr_from_mont (fr.cuh: v = a 2^-256 mod r, 8 rounds of word REDC) ahead of the bias-add, with a >= r
+// reported.  A lane takes R = 2 adjacent scalars, 32 or 64 B, as 16-B vector loads where the vector is
+// 16-B aligned and word by word where it is only 4-B aligned; the lane that holds the odd tail of the
+// span reads only its own scalar's words, so nothing past byte n SW 4 is touched.
+// REDC's output is below r whatever a was, and is masked like the rest.
 constexpr uint32_t WIDE_U = 0, WIDE_I = 1, WIDE_MONT = 2;
 template <typename T, uint32_t SW, uint32_t MODE>
 __global__ void __launch_bounds__(RC_THREADS) k_recode_wide(BatchPtrs scalar_sets, MsmDims d,
                                                             T* __restrict__ digits, uint32_t* __restrict__ colsum,
                                                             NarrowBias bias, uint32_t* __restrict__ err) {
-  using DC = DigitCode<T>;
   constexpr uint32_t R = 2;        // scalars per lane
   constexpr uint32_t LW = R * SW;  // words per lane
   static_assert(SW == 4 || SW == 8, "128- or 256-bit elements");
@@ -1250,31 +1245,19 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_wide(BatchPtrs scalar_set
   const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
   const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
   const uint32_t w0 = blockIdx.y * d.Wr;
-  const uint32_t nh = d.Wr * d.nbc;
-  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
   // value bits of every word (little-endian): all of it below b, none of it at and above
   uint32_t wmask[SW];
 #pragma unroll
   for (uint32_t k = 0; k < SW; k++)
     wmask[k] = d.sbits >= 32 * k + 32 ? 0xffffffffu : d.sbits > 32 * k ? (1u << (d.sbits - 32 * k)) - 1u : 0u;
   const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
-  const bool pair_store = sizeof(T) == 2 && (d.n & 1u) == 0;
   bool bad = false;
-  __syncthreads();
+  recode_begin(lds_hist, d);
   for (uint32_t i = lo + R * threadIdx.x; i < hi; i += R * RC_THREADS) {
     const uint32_t cnt = min(R, hi - i);
     uint32_t raw[LW];
-    const uint32_t* p = scalars + (size_t)i * SW;
-    if (cnt == R && vec) {  // (i is even and an element 16 or 32 B: the lane's run is 16-B aligned)
-#pragma unroll
-      for (uint32_t k = 0; k < LW / 4; k++) {
-        const uint4 v = reinterpret_cast<const uint4*>(p)[k];
-        raw[4 * k] = v.x, raw[4 * k + 1] = v.y, raw[4 * k + 2] = v.z, raw[4 * k + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < LW; k++) raw[k] = k < cnt * SW ? p[k] : 0u;
-    }
+    // (i is even and an element 16 or 32 B: a whole lane's run is 16-B aligned)
+    load_words(raw, scalars + (size_t)i * SW, cnt == R && vec, cnt * SW);
     uint32_t t[R][SW + 1];
     bool neg[R];
 #pragma unroll
@@ -1296,54 +1279,22 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_wide(BatchPtrs scalar_set
         bad = bad || !fr_is_canonical(m);
         fr_from_mont(m, m);
       }
-      uint32_t cy = 0;
 #pragma unroll
       for (uint32_t k = 0; k < SW; k++) {
         bad = bad || (m[k] & ~wmask[k]) != 0;
-        const uint64_t x = (uint64_t)(m[k] & wmask[k]) + bias.v[k] + cy;
-        t[r][k] = (uint32_t)x;
-        cy = (uint32_t)(x >> 32);
+        m[k] &= wmask[k];
       }
-      t[r][SW] = cy;
+      bias_add(m, bias, t[r]);
     }
-    T* row = digits + (size_t)w0 * d.n + i;
-    uint32_t* h = lds_hist;
-    for (uint32_t w = 0; w < d.Wr; w++) {
-      const uint32_t b = w < d.nhi ? d.q + 1 : d.q;
-      const uint32_t mask = (1u << b) - 1u, hb = (1u << (b - 1)) - 1u;
-      const uint32_t fbits = d.fb > d.c - b ? d.fb - (d.c - b) : 0u;  // win_fb
-      uint32_t code[R];
-#pragma unroll
-      for (uint32_t r = 0; r < R; r++) {
-        const int32_t digit = (int32_t)(t[r][0] & mask) - (int32_t)hb;
-#pragma unroll
-        for (uint32_t k = 0; k < SW; k++) t[r][k] = __builtin_amdgcn_alignbit(t[r][k + 1], t[r][k], b);
-        t[r][SW] >>= b;
-        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
-        const bool live = digit != 0 && r < cnt;
-        // every lane adds (0 for a zero digit): no divergent branch around the LDS atomic
-        atomicAdd(&h[live ? mag >> fbits : 0u], live ? 1u : 0u);
-        code[r] = live ? mag | ((digit < 0) != neg[r] ? DC::SIGN : 0u) : DC::ZERO;
-      }
-      if (pair_store && cnt == R) {
-        *reinterpret_cast<uint32_t*>(row) = code[0] | code[1] << 16;
-      } else {
-        row[0] = (T)code[0];
-        if (cnt == R) row[1] = (T)code[1];
-      }
-      row += d.n;
-      h += d.nbc;
-    }
+    recode_windows<T, SW, R>(t, neg, cnt, digits + (size_t)w0 * d.n + i, lds_hist, d);
   }
-  if (bad) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
-  __syncthreads();
-  flush_hist(lds_hist, d, w0, colsum);
+  recode_end(lds_hist, d, w0, colsum, bad, err);
 }
 
 // MSM_FIELD_U256 of 254..256 bits: k_recode_hist on little-endian words -- the full-width geometry,
-// overflow window included, on the caller's BigInt<4> array.  A kernel of its own, so that the 8-word
-// launches keep theirs as they are.  16-B vector loads where the vector is 16-B aligned, else word
-// by word.
+// overflow window included, on the caller's BigInt<4> array (the launch covers every window: w0 = 0,
+// no half windows).  A kernel of its own, so that the 8-word launches keep theirs as they are.  16-B
+// vector loads where the vector is 16-B aligned, else word by word.
 template <typename T>
 __global__ void __launch_bounds__(RC_THREADS) k_recode_hist_le(BatchPtrs scalar_sets, MsmDims d,
                                                                T* __restrict__ digits, uint32_t* __restrict__ colsum) {
@@ -1351,34 +1302,14 @@ __global__ void __launch_bounds__(RC_THREADS) k_recode_hist_le(BatchPtrs scalar_
   const uint32_t* __restrict__ scalars = scalar_sets.p[blockIdx.y];
   const uint32_t lo = blockIdx.x * RC_SPAN, hi = min(d.n, lo + RC_SPAN);
   const uint32_t w0 = blockIdx.y * d.Wr;
-  const uint32_t nh = d.Wr * d.nbc;
-  for (uint32_t b = threadIdx.x; b < nh + d.Wr; b += RC_THREADS) lds_hist[b] = 0;  // + the window totals
   const bool vec = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0;
-  __syncthreads();
+  recode_begin(lds_hist, d);
   for (uint32_t i = lo + threadIdx.x; i < hi; i += RC_THREADS) {
     uint32_t s[8];
-    const uint32_t* p = scalars + (size_t)i * 8;
-    if (vec) {
-      const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
-      s[0] = a.x, s[1] = a.y, s[2] = a.z, s[3] = a.w, s[4] = b.x, s[5] = b.y, s[6] = b.z, s[7] = b.w;
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < 8; k++) s[k] = p[k];
-    }
-    recode(s, d, [&](uint32_t wa, int32_t digit) {
-      const uint32_t w = wa - d.w0;  // local window (the launch covers every window: w0 = 0)
-      if (w >= d.Wr) return;
-      uint32_t code = DigitCode<T>::ZERO;
-      if (digit != 0) {
-        const uint32_t mag = (uint32_t)(digit < 0 ? -digit : digit) - 1u;
-        code = mag | (digit < 0 ? DigitCode<T>::SIGN : 0u);
-        atomicAdd(&lds_hist[w * d.nbc + (mag >> win_fb(d, wa))], 1u);
-      }
-      digits[(size_t)(w0 + w) * d.n + i] = (T)code;
-    });
+    load_words(s, scalars + (size_t)i * 8, vec, 8);
+    recode_carry<T, false>(s, i, d, w0, digits, lds_hist);
   }
-  __syncthreads();
-  flush_hist(lds_hist, d, w0, colsum);
+  recode_end(lds_hist, d, w0, colsum);
 }
 
 // k_fine_sort geometry
