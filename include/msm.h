@@ -509,6 +509,55 @@ int msm_bases_compute_subset_many_device(const msm_bases* bases, const msm_subse
                                          const uint32_t* const* d_scalars_be, size_t count, const msm_opts* opts,
                                          void* hip_stream, uint32_t* out_xy_be);
 
+/* Per-point scalar multiples of a handle's bases: Q_i = s_i * P_i, m points out where every entry
+ * above ends in one (ark-ec's batch_mul beside its VariableBaseMSM).  A commitment key is updated or
+ * blinded (P_i <- tau^i P_i, rho_i P_i), a folding argument halves its generators (x * G_(i+m)), many
+ * keys are derived from one base (s_i * G: an index vector of zeros) -- on the device, from the resident
+ * records, with one ladder per point (k_scale_points: fixed 2-bit windows over {P, 2P, 3P}, no
+ * data-dependent branch, one inversion per point; DESIGN.md §9 has the measured cost).
+ *
+ *   subset == NULL            Q_i = scalars[i] * P_i,               i < n (m = n)
+ *   range form                Q_i = scalars[i] * P_(first + i),     i < m
+ *   indexed form              Q_i = scalars[i] * P_(indices[0][i]), i < m
+ *
+ * The subset is msm_bases_compute_subset's (first + m <= n; indexed: first == 0, each index < n,
+ * repeats allowed, so m may exceed n; m < 2^30).  A handle of levels > 1 is read at level 0.
+ *
+ * Scalars: 8 big-endian words each, or ceil(b / 32) with MSM_FLAG_SCALAR_BITS and scalar_bits = b in
+ * 1..256 (MSM_ERR_INVALID_ARG outside).  The scalar is the integer it is and is not reduced mod r, so
+ * the result is also defined for the curve's torsion points; the ladder's length follows b, and a
+ * 64-bit scalar costs a quarter of a 256-bit one.  Only these word formats: MSM_FLAG_SCALAR_TYPE and
+ * MSM_FLAG_SCALAR_FIELD (native and wide scalars), MSM_FLAG_DEVICES, MSM_FLAG_WINDOWS and
+ * MSM_FLAG_HALF_WINDOWS give MSM_ERR_INVALID_ARG before any device work.  opts->device is -1 or the
+ * handle's own; run_length and MSM_FLAG_SERIAL are ignored.
+ *
+ * msm_bases_scale* write m wire records x | y | t = x y | z = 1, every coordinate canonical (< p);
+ * s = 0, and any multiple that is the identity, gives (0, 1, 0, 1).  Scaling by ones at scalar_bits = 1
+ * reads a handle's own points back -- those of a handle made from x-coordinates included.
+ * msm_bases_scale_create* keep the m points as a new handle, without their leaving the device: its
+ * level 0 is bit-identical to what msm_bases_create makes from the records msm_bases_scale returns;
+ * `levels` and opts->window_bits mean what they mean there, and so do the limits and the errors of a
+ * creation.  A failed creation leaves *out null and nothing allocated.  Results are specified for
+ * on-curve bases.  m = 0: the scale entries return MSM_OK and write nothing, the create entries
+ * return an empty handle.
+ *
+ * A scalar bit at or above b, or an index >= n, gives MSM_ERR_INVALID_ARG: from the host entries
+ * before anything is uploaded or enqueued; from the device entries after the launch, which masks the
+ * bit or reads base 0 instead, runs to its end and never reads out of range (the output is then
+ * unspecified, a creation leaves nothing allocated, and the source handle stays usable).
+ * Device pointers: d_points_be and 8-word scalars 16-byte aligned, narrow scalars and indices 4-byte
+ * aligned (MSM_ERR_INVALID_ARG, decided from the pointer value before anything is enqueued); output
+ * and scalars must not overlap.  The device entries are ordered after the work queued on hip_stream
+ * and return when the result is complete.  A stale handle or a null argument: MSM_ERR_INVALID_ARG. */
+int msm_bases_scale(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* scalars_be,
+                    const msm_opts* opts, uint32_t* points_be /* [m][32] wire records */);
+int msm_bases_scale_device(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* d_scalars_be,
+                           const msm_opts* opts, void* hip_stream, uint32_t* d_points_be);
+int msm_bases_scale_create(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* scalars_be,
+                           const msm_opts* opts, uint32_t levels, msm_bases** out);
+int msm_bases_scale_create_device(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* d_scalars_be,
+                                  const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out);
+
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,
  * 7M mixed adds into per-thread bucket tables.  window_bits 0 = auto, n_threads <= 0 = all

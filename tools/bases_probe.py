@@ -85,6 +85,18 @@ same points, same run -- the wire creations from host records (128 n bytes up) a
 ones.  Each creation is timed with its msm_bases_destroy; one MSM on the compressed handle is checked
 against the closed form, and the decompressed records against the generator's.
 
+With --scale the pass is the per-point scalar-multiple sweep of DESIGN.md §9 (msm_bases_scale*): for m in
+--scale-sizes (log2; default 12..20) on a levels-1 handle of m points, and for b in --scale-bits (default
+64,128,253,256), one line per form
+
+  {"entry": "scale", "m", "bits", "form": "device_range" | "device_indexed" | "host", "ms", "ns_per_point"}
+
+the awaited device-to-device call over the range, over a random index list, and the host entry (scalars
+up, wire records back); six sampled points of each are checked against the oracle's scalar multiplication.
+Then, in the same process, what the library offered for the same result before: m one-term MSMs through
+compute_subset_many_device, at m in --scale-msm-sizes (default 2^10 and 2^12), as a row of its own
+("form": "one_term_msms"), checked against the scale call.  All sizes run in one child process.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -676,6 +688,78 @@ def compressed_pass(a):
     return 0
 
 
+def scale_pass(a):
+    """--scale: every size of the sweep in this one process (one context, one torch import)."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from oracle import oracle as O
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def affine(rec):
+        return (O.be_words_to_int(rec[:8]), O.be_words_to_int(rec[8:16]))
+
+    bad = 0
+    rng = np.random.default_rng(2024)
+    for lg in a.scale_sizes:
+        m = 1 << lg
+        pts = M.gen_points(m, k0=3, step=5)
+        idx = rng.integers(0, m, size=m, dtype=np.uint32)
+        d_idx = dev(idx)
+        d_out = torch.zeros((m, 32), dtype=torch.int32, device="cuda")
+        with M.Bases.from_wire(pts, levels=1) as b:
+            for bits in a.scale_bits:
+                sw = (bits + 31) // 32
+                sc = rng.integers(0, 1 << 32, size=(m, sw), dtype=np.uint64).astype(np.uint32)
+                if bits % 32:
+                    sc[:, 0] &= (1 << (bits % 32)) - 1
+                d_sc = dev(sc)
+                kw = {} if bits == 256 else {"scalar_bits": bits}
+                torch.cuda.synchronize()
+                rows = {}
+                rows["device_range"] = timed(lambda: b.scale_device(d_sc, d_out, **kw), a.runs)
+                got = d_out.cpu().numpy().view(np.uint32)
+                sample = [0, m - 1] + [int(i) for i in rng.integers(0, m, size=4)]
+                correct = all(affine(got[i]) == O.c_scalar_mul(affine(pts[i]), O.be_words_to_int(sc[i])) and
+                              got[i][31] == 1 for i in sample)
+                rows["device_indexed"] = timed(lambda: b.scale_device(d_sc, d_out, indices=d_idx, **kw), a.runs)
+                got = d_out.cpu().numpy().view(np.uint32)
+                correct = correct and all(
+                    affine(got[i]) == O.c_scalar_mul(affine(pts[idx[i]]), O.be_words_to_int(sc[i])) for i in sample)
+                rows["host"] = timed(lambda: b.scale(sc, **kw), a.runs)
+                correct = correct and bool(np.array_equal(rows["host"][2][sample], b.scale(sc[sample], indices=np.array(
+                    sample, np.uint32), **kw)))
+                for form, (ms, runs, _) in rows.items():
+                    emit({"entry": "scale", "m": m, "bits": bits, "form": form, "ms": round(ms, 4),
+                          "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs, "correct": bool(correct)})
+                bad += not correct
+    # what the library offered before, in the same run: m one-term MSMs, one launch group per point
+    for lg in a.scale_msm_sizes:
+        m = 1 << lg
+        with M.Bases.from_wire(M.gen_points(m, k0=3, step=5), levels=1) as b:
+            sc = rng.integers(0, 1 << 32, size=(m, 8), dtype=np.uint64).astype(np.uint32)
+            d_sc = dev(sc)
+            d_ar = dev(np.arange(m, dtype=np.uint32))
+            s_list = [d_sc[i:i + 1] for i in range(m)]
+            i_list = [d_ar[i:i + 1] for i in range(m)]
+            torch.cuda.synchronize()
+            ms, runs, res = timed(lambda: b.compute_subset_many_device(s_list, indices=i_list, m=1), a.runs)
+            correct = bool(np.array_equal(res, b.scale(sc)[:, :16]))
+            emit({"entry": "scale", "m": m, "bits": 256, "form": "one_term_msms", "ms": round(ms, 4),
+                  "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs, "correct": correct})
+            bad += not correct
+    return 1 if bad else 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -732,12 +816,28 @@ def main():
     ap.add_argument("--native", action="store_true", help="the native-type sweep (MSM_FLAG_SCALAR_TYPE) instead")
     ap.add_argument("--native-types", default="bit,u8,i8,u16,i16,i32,i64,u64", help="types of the native sweep")
     ap.add_argument("--compressed", action="store_true", help="the compressed-creation sweep (MSM_POINTS_X_*) instead")
+    ap.add_argument("--scale", action="store_true", help="the per-point scalar-multiple sweep (msm_bases_scale*) instead")
+    ap.add_argument("--scale-sizes", default="12,13,14,15,16,17,18,19,20", help="log2 point counts m of the scale sweep")
+    ap.add_argument("--scale-bits", default="64,128,253,256", help="scalar widths b of the scale sweep")
+    ap.add_argument("--scale-msm-sizes", default="10,12", help="log2 m at which the one-term-MSM route is timed too")
+    ap.add_argument("--scale-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
     a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
     if a.dense:
         return dense_sweep(a)
+    if a.scale:
+        a.scale_bits = [int(x) for x in str(a.scale_bits).split(",") if x]
+        a.scale_msm_sizes = [int(x) for x in str(a.scale_msm_sizes).split(",") if x]
+        a.scale_sizes = sorted(int(x) for x in str(a.scale_sizes).split(",") if x)
+        if a.scale_child:
+            return scale_pass(a)
+        cmd = ["timeout", "-k", "10", str(a.step_timeout * 3), sys.executable, os.path.abspath(__file__), "--scale",
+               "--scale-child", "--scale-sizes", ",".join(map(str, a.scale_sizes)), "--scale-bits",
+               ",".join(map(str, a.scale_bits)), "--scale-msm-sizes", ",".join(map(str, a.scale_msm_sizes)),
+               "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
+        return subprocess.run(cmd).returncode
     if a.compressed:
         if a.n:
             return compressed_pass(a)

@@ -52,18 +52,12 @@ void launch_decompress(const uint32_t* d_xs, uint32_t* dst, uint32_t n, uint32_t
                      err);
 }
 
-// `form` 0: `points` are wire records; MSM_POINTS_X_*: compressed points, decompressed into the slot's
-// dx_pts as x|y and prepared from there, so the records are those of the wire creation of the same points.
-int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, const msm_opts* opts, uint32_t levels,
-                 hipStream_t user_stream, msm_bases** out) {
-  if (!out) return MSM_ERR_INVALID_ARG;
-  *out = nullptr;
-  if ((!points && n) || levels > 8 || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
-  if (form && (!points_form_ok(form) || (!host && !aligned16(points)))) return MSM_ERR_INVALID_ARG;
-  const uint32_t wb = opts ? opts->window_bits : 0;
+// A creation's argument rules that need no device: the levels (0 = the library's choice for n), the
+// window width and the geometry of the shifted levels, and levels * n inside the record limit.
+int bases_shape(Bases* b, size_t n, uint32_t levels, uint32_t wb) {
+  if (levels > 8) return MSM_ERR_INVALID_ARG;
   if (wb && (wb < 4 || wb > 20)) return MSM_ERR_UNSUPPORTED_WINDOW;
   if (!levels) levels = bases_auto_levels(n);
-  auto b = std::make_shared<Bases>();
   b->n = n;
   b->levels = levels;
   if (levels > 1) {
@@ -71,21 +65,63 @@ int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, con
     if (!bases_geometry(b->window_bits, levels, &b->geo)) return MSM_ERR_INVALID_ARG;
   }
   if ((uint64_t)levels * n >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  return MSM_OK;
+}
+
+// The launch plan of one MSM on a handle's records must exist (finish_plan's Mmax limit).
+int bases_plan_exists(DevCtx* c, const Bases& b, uint32_t wb) {
+  msm_opts op{};
+  op.window_bits = b.levels > 1 ? b.window_bits : wb;
+  if (b.levels > 1) {
+    op.flags = MSM_FLAG_WINDOWS;
+    op.window_hi = b.geo.Wc;
+  }
+  Plan pl;
+  return make_plan(b.n * b.levels, &op, c->shape, &pl, false, 1, true);
+}
+
+// Level j of a handle's records from level j - 1, for every shifted level (k_shift_bases).
+void launch_shift_levels(const Bases& b, uint32_t nt, hipStream_t s) {
+  uint32_t* rec = b.rec.as<uint32_t>();
+  for (uint32_t j = 1; j < b.levels; j++)
+    hipLaunchKernelGGL(k_shift_bases, dim3(grid_for(b.n, PP_THREADS)), dim3(PP_THREADS), 0, s,
+                       rec + (size_t)(j - 1) * b.n * PRE_WORDS, rec + (size_t)j * b.n * PRE_WORDS, (uint32_t)b.n,
+                       b.geo.S, nt);
+}
+
+// A finished creation into the registry: *out is the new handle's token.
+int register_bases(const std::shared_ptr<Bases>& b, msm_bases** out) {
+  b->alive = true;  // n = 0: nothing allocated
+  std::lock_guard<std::mutex> lk(g_mu);
+  // msm_shutdown may have run since the records were made (it frees only registered handles)
+  if (b->n && ((int)g_ctx.size() <= b->device || !g_ctx[b->device])) {
+    b->rec.release();
+    return MSM_ERR_INVALID_ARG;
+  }
+  const uintptr_t id = g_bases_next++;
+  g_bases[id] = b;
+  *out = reinterpret_cast<msm_bases*>(id);
+  return MSM_OK;
+}
+
+// `form` 0: `points` are wire records; MSM_POINTS_X_*: compressed points, decompressed into the slot's
+// dx_pts as x|y and prepared from there, so the records are those of the wire creation of the same points.
+int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, const msm_opts* opts, uint32_t levels,
+                 hipStream_t user_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  *out = nullptr;
+  if ((!points && n) || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  if (form && (!points_form_ok(form) || (!host && !aligned16(points)))) return MSM_ERR_INVALID_ARG;
+  const uint32_t wb = opts ? opts->window_bits : 0;
+  auto b = std::make_shared<Bases>();
+  if (int src = bases_shape(b.get(), n, levels, wb)) return src;
+  levels = b->levels;
   msm_opts od{};
   od.device = opts ? opts->device : -1;
   int rc = on_device(&od, [&](DevCtx* c) -> int {
     b->device = c->device;
     if (!n) return MSM_OK;
-    {  // the launch plan of one MSM on these records must exist (finish_plan's Mmax limit)
-      msm_opts op{};
-      op.window_bits = levels > 1 ? b->window_bits : wb;
-      if (levels > 1) {
-        op.flags = MSM_FLAG_WINDOWS;
-        op.window_hi = b->geo.Wc;
-      }
-      Plan pl;
-      if (int prc = make_plan(n * levels, &op, c->shape, &pl, false, 1, true)) return prc;
-    }
+    if (int prc = bases_plan_exists(c, *b, wb)) return prc;
     Slot& s0 = c->slot[0];
     Buf errb;  // the preparation's error word
     int r = errb.ensure(16);
@@ -127,10 +163,7 @@ int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, con
     } else {
       launch_prepare(points, rec, (uint32_t)n, errp, nt, s0.stream);
     }
-    for (uint32_t j = 1; j < levels; j++)
-      hipLaunchKernelGGL(k_shift_bases, dim3(grid_for(n, PP_THREADS)), dim3(PP_THREADS), 0, s0.stream,
-                         rec + (size_t)(j - 1) * n * PRE_WORDS, rec + (size_t)j * n * PRE_WORDS, (uint32_t)n,
-                         b->geo.S, nt);
+    launch_shift_levels(*b, nt, s0.stream);
     if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
     uint32_t e[4] = {};
     if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
@@ -141,17 +174,7 @@ int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, con
     return done(MSM_OK);
   });
   if (rc != MSM_OK) return rc;
-  b->alive = true;  // n = 0: nothing allocated
-  std::lock_guard<std::mutex> lk(g_mu);
-  // msm_shutdown may have run since the records were made (it frees only registered handles)
-  if (n && ((int)g_ctx.size() <= b->device || !g_ctx[b->device])) {
-    b->rec.release();
-    return MSM_ERR_INVALID_ARG;
-  }
-  const uintptr_t id = g_bases_next++;
-  g_bases[id] = b;
-  *out = reinterpret_cast<msm_bases*>(id);
-  return MSM_OK;
+  return register_bases(b, out);
 }
 
 // msm_decompress_points*: n compressed points to wire records, host to host (through the slot's wire
@@ -223,6 +246,119 @@ int compress_points(const uint32_t* xy, size_t n, uint32_t form, uint32_t* xs) {
     if (form == MSM_POINTS_X_YSIGN && big) xs[8 * i] |= 0x80000000u;
   }
   return MSM_OK;
+}
+
+// msm_bases_scale*: Q_i = s_i P_i for the m bases of `sub` (null: all n) of a handle's level 0, one
+// k_scale_points launch on slot 0's stream.  With `created` the points become a new handle: the x|y
+// output goes through the preparation, as a compressed creation's does, so level 0 is what
+// msm_bases_create makes from the wire records.  Else they are written to `points` as wire records
+// (host entries: through the slot's dx_pts).  Host scalars (and indices) go up into the slot's wire_pts
+// (and sub_idx) after every one of them was checked.
+int bases_scale(const msm_bases* h, const msm_subset_t* sub, const uint32_t* scalars, bool host, const msm_opts* opts,
+                hipStream_t user_stream, uint32_t* points, uint32_t levels, msm_bases** created) {
+  if (created) *created = nullptr;
+  if (!h || !bases_flags_ok(opts) || typed_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  const uint32_t bits = opts && (opts->flags & MSM_FLAG_SCALAR_BITS) ? opts->scalar_bits : 256u;
+  if (bits < 1 || bits > 256) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b) return MSM_ERR_INVALID_ARG;
+  if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
+  const uint32_t* indices = sub && sub->indices ? sub->indices[0] : nullptr;
+  const size_t m = sub ? (size_t)sub->m : b->n, first = sub ? (size_t)sub->first : 0;
+  if (sub) {
+    if (int rc = subset_check(b->n, 1, sub->first, sub->m, sub->indices != nullptr)) return rc;
+    if (sub->indices && !indices && m) return MSM_ERR_INVALID_ARG;
+  }
+  if (m && (!scalars || (!created && !points))) return MSM_ERR_INVALID_ARG;
+  const uint32_t wb = opts ? opts->window_bits : 0;
+  auto nb = std::make_shared<Bases>();
+  if (created)
+    if (int rc = bases_shape(nb.get(), m, levels, wb)) return rc;
+  const size_t sw = (bits + 31) / 32;
+  if (!host && m) {  // alignment and overlap, from the pointer values
+    const uintptr_t sp = reinterpret_cast<uintptr_t>(scalars), pp = reinterpret_cast<uintptr_t>(points);
+    if ((sp & (sw == 8 ? 15u : 3u)) || (reinterpret_cast<uintptr_t>(indices) & 3u)) return MSM_ERR_INVALID_ARG;
+    if (!created && ((pp & 15u) || (pp < sp + m * sw * 4 && sp < pp + m * 128))) return MSM_ERR_INVALID_ARG;
+  }
+  if (host) {  // every scalar and every index, before anything is uploaded or enqueued
+    if (bits & 31u) {
+      const uint32_t excess = ~((1u << (bits & 31u)) - 1u);
+      uint32_t any = 0;
+      for (size_t i = 0; i < m; i++) any |= scalars[i * sw];
+      if (any & excess) return MSM_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; indices && i < m; i++)
+      if (indices[i] >= b->n) return MSM_ERR_INVALID_ARG;
+  }
+  msm_opts od{};
+  od.device = b->device;
+  int rc = on_device(&od, [&](DevCtx* c) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    nb->device = c->device;
+    if (!m) return MSM_OK;
+    if (created)
+      if (int prc = bases_plan_exists(c, *nb, wb)) return prc;
+    Slot& s0 = c->slot[0];
+    Buf errb;
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if (created && (r = nb->rec.ensure((size_t)nb->levels * m * PRE_WORDS * 4)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    auto done = [&](int code) {  // as create_bases'
+      drain_streams(c, 1, code);
+      if (errb.base) {
+        std::lock_guard<std::mutex> gl(g_guard_mu);
+        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+      }
+      errb.release();
+      if (code != MSM_OK) nb->rec.release();
+      return code;
+    };
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    const uint32_t* d_sc = scalars;
+    const uint32_t* d_ix = indices;
+    uint32_t* d_out = points;
+    if (host) {
+      if ((r = s0.ws.wire_pts.ensure(m * sw * 4)) != MSM_OK || (indices && (r = s0.ws.sub_idx.ensure(m * 4)) != MSM_OK))
+        return done(r);
+      auto whole = [](size_t, size_t) { return MSM_OK; };
+      if ((r = upload(c, s0.ws.wire_pts.p, scalars, m * sw * 4, m * sw * 4, whole)) != MSM_OK) return done(r);
+      if (indices && (r = upload(c, s0.ws.sub_idx.p, indices, m * 4, m * 4, whole)) != MSM_OK) return done(r);
+      if (hipEventRecord(c->ev_chunk[0], c->copy_stream) != hipSuccess ||
+          hipStreamWaitEvent(s0.stream, c->ev_chunk[0], 0) != hipSuccess)
+        return done(MSM_ERR_HIP);
+      d_sc = s0.ws.wire_pts.as<uint32_t>();
+      if (indices) d_ix = s0.ws.sub_idx.as<uint32_t>();
+    }
+    if (host || created) {
+      if ((r = s0.ws.dx_pts.ensure(m * (created ? 64 : 128))) != MSM_OK) return done(r);
+      d_out = s0.ws.dx_pts.as<uint32_t>();
+    }
+    hipLaunchKernelGGL(k_scale_points, dim3(grid_for(m, SC_THREADS)), dim3(SC_THREADS), 0, s0.stream,
+                       b->rec.as<uint32_t>(), (uint32_t)b->n, (uint32_t)first, d_ix, d_sc, (uint32_t)sw, bits, d_out,
+                       (uint32_t)m, created ? 0u : 1u, errp);
+    if (created) {
+      const uint32_t nt = prep_nt((size_t)nb->levels * m);
+      launch_prepare(d_out, nb->rec.as<uint32_t>(), (uint32_t)m, errp, nt, s0.stream, PT_FMT_XY);
+      launch_shift_levels(*nb, nt, s0.stream);
+    }
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if ((host && !created && hipMemcpyAsync(points, d_out, m * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
+        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & (MSM_DEV_ERR_BAD_INDEX | MSM_DEV_ERR_SCALAR_RANGE)) return done(MSM_ERR_INVALID_ARG);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+  if (rc != MSM_OK || !created) return rc;
+  return register_bases(nb, created);
 }
 
 // `count` MSMs over a handle's records: run_many's pipelined path with the records in the place

@@ -368,6 +368,16 @@ int msm_test_decompress_constants(uint32_t out[28]) {
   return MSM_OK;
 }
 
+// k_scale_points' own digit function on the host (msm_kernels.hip scale_digit, scale_windows): the
+// windows of one b-bit scalar of sw big-endian words, least significant first, and their count -- the
+// ladder's trip count (256 / w at b = 256 for windows of w bits).  digits holds 256 entries.
+int msm_test_scale_digits(const uint32_t* scalar_be, uint32_t sw, uint32_t b, uint32_t* digits, uint32_t* count) {
+  if (!scalar_be || !digits || !count || b < 1 || b > 256 || sw != (b + 31) / 32) return MSM_ERR_INVALID_ARG;
+  *count = scale_windows(b);
+  for (uint32_t j = 0; j < *count; j++) digits[j] = scale_digit(scalar_be, sw, b, j);
+  return MSM_OK;
+}
+
 // out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
 // msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
 int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {

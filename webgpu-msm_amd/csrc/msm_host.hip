@@ -359,6 +359,28 @@ int msm_bases_compute_many_device(const msm_bases* h, const uint32_t* const* d_s
   return bases_compute(h, d_scalars_be, false, count, opts, hip_stream, out_xy_be);
 }
 
+int msm_bases_scale(const msm_bases* h, const msm_subset_t* sub, const uint32_t* scalars_be, const msm_opts* opts,
+                    uint32_t* points_be) {
+  return bases_scale(h, sub, scalars_be, true, opts, nullptr, points_be, 0, nullptr);
+}
+
+int msm_bases_scale_device(const msm_bases* h, const msm_subset_t* sub, const uint32_t* d_scalars_be,
+                           const msm_opts* opts, void* hip_stream, uint32_t* d_points_be) {
+  return bases_scale(h, sub, d_scalars_be, false, opts, (hipStream_t)hip_stream, d_points_be, 0, nullptr);
+}
+
+int msm_bases_scale_create(const msm_bases* h, const msm_subset_t* sub, const uint32_t* scalars_be,
+                           const msm_opts* opts, uint32_t levels, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return bases_scale(h, sub, scalars_be, true, opts, nullptr, nullptr, levels, out);
+}
+
+int msm_bases_scale_create_device(const msm_bases* h, const msm_subset_t* sub, const uint32_t* d_scalars_be,
+                                  const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return bases_scale(h, sub, d_scalars_be, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
+}
+
 int msm_combine_partials(const uint32_t* partials_xyzt_be, size_t count, uint32_t out_xy_be[16]) {
   if ((!partials_xyzt_be && count) || !out_xy_be) return MSM_ERR_INVALID_ARG;
   Pt acc = pt_identity();

@@ -570,6 +570,150 @@ extern "C" __global__ void __launch_bounds__(DX_THREADS, 2) k_decompress_x(const
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// per-point scalar multiples of a handle's bases (msm_bases_scale*): Q_i = s_i P_i
+// ---------------------------------------------------------------------------------------------
+// The ladder reads the scalar in fixed windows of SC_W bits, most significant first.  SC_W divides 32,
+// so no window straddles a word.  Both functions run on the host too (msm_test_scale_digits), so the
+// test of the window index -> digit mapping exercises the very code the kernel runs.
+constexpr uint32_t SC_W = 2;
+static_assert(SC_W == 2, "k_scale_points' table holds P, 2P, 3P");
+// The ladder's trip count for b-bit scalars: wave-uniform, from the kernel argument alone.
+__host__ __device__ constexpr uint32_t scale_windows(uint32_t b) { return (b + SC_W - 1) / SC_W; }
+// Window j (j < scale_windows(b)) of a b-bit scalar held as sw = ceil(b / 32) big-endian words: bits
+// [SC_W j, SC_W j + SC_W) of the integer.  The top window keeps only the bits below b, so a stray bit
+// at or above b (flagged by the kernel) never reaches the ladder.
+__host__ __device__ inline uint32_t scale_digit(const uint32_t* s_be, uint32_t sw, uint32_t b, uint32_t j) {
+  const uint32_t bit = j * SC_W;
+  const uint32_t d = (s_be[sw - 1 - (bit >> 5)] >> (bit & 31u)) & ((1u << SC_W) - 1u);
+  return b - bit < SC_W ? d & ((1u << (b - bit)) - 1u) : d;
+}
+
+// Q_i = s_i P_(first + i) (indices == nullptr) or s_i P_(indices[i]) for i < m, over the n prepared
+// records `recs` of a handle's level 0.  One lane per output point, one wave per workgroup, two waves
+// per SIMD as k_decompress_x (225 VGPRs, no scratch: the table and the accumulator are 144 of them).
+// The plain double-and-add with a selected add was measured beside this ladder and lost by a quarter
+// (DESIGN.md §9).
+//   records  range form: the workgroup's 8 KiB arrive coalesced through LDS, as k_shift_bases reads
+//            them; indexed form: a 128-byte gather per lane.  An index >= n is replaced by 0 and
+//            raises MSM_DEV_ERR_BAD_INDEX.  The extended point is rebuilt as k_shift_bases rebuilds
+//            it: every coordinate an fe_mul output, which pt_dbl's and pt_add's bound proofs take.
+//   scalars  sw big-endian words each (the full integer: nothing is reduced mod r), the workgroup's
+//            64 sw words staged in LDS with 16-byte loads where the vector is 16-byte aligned, word by
+//            word where it is not.  A bit at or above b is masked (scale_digit) and raises
+//            MSM_DEV_ERR_SCALAR_RANGE.
+//   ladder   scale_windows(b) rounds of SC_W doublings and one addition of {O, P, 2P, 3P}[digit],
+//            chosen with pt_sel: no lane takes a branch of its own, and the unified addition is
+//            complete, so the identity, the torsion points and P + P need none either.
+//   output   one fe_inv per lane, canonical standard form, x | y | t = x y | z = 1 (wire = 1: 128-byte
+//            records) or x | y (wire = 0: what k_prepare_points(PT_FMT_XY) reads), through LDS as
+//            k_decompress_x writes them.  The identity comes out as (0 : Z : 0 : Z) and is written
+//            (0, 1, 0, 1).  Results are specified for on-curve bases (Z is then never 0).
+constexpr uint32_t SC_THREADS = 64;
+extern "C" __global__ void __launch_bounds__(SC_THREADS, 2) k_scale_points(
+    const uint32_t* __restrict__ recs, uint32_t n, uint32_t first, const uint32_t* __restrict__ indices,
+    const uint32_t* __restrict__ scalars, uint32_t sw, uint32_t b, uint32_t* __restrict__ out, uint32_t m,
+    uint32_t wire, uint32_t* __restrict__ err) {
+  __shared__ uint4 st[SC_THREADS * 8];
+  __shared__ uint4 ssc4[SC_THREADS * 2];
+  uint32_t* ssc = reinterpret_cast<uint32_t*>(ssc4);
+  const uint32_t p0 = blockIdx.x * SC_THREADS;
+  const uint32_t np = min(SC_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  {  // the workgroup's np * sw scalar words; p0 * sw * 4 is a multiple of 256 bytes
+    const uint32_t* sp = scalars + (size_t)p0 * sw;
+    const uint32_t total = np * sw;
+    const uint32_t nv = (reinterpret_cast<uintptr_t>(scalars) & 15u) ? 0u : total >> 2;
+    for (uint32_t g = i; g < nv; g += SC_THREADS) ssc4[g] = reinterpret_cast<const uint4*>(sp)[g];
+    for (uint32_t g = (nv << 2) + i; g < total; g += SC_THREADS) ssc[g] = sp[g];
+  }
+  uint32_t rec[32];
+  if (indices) {
+    uint32_t idx = live ? indices[p0 + i] : 0u;
+    if (idx >= n) {
+      idx = 0;
+      atomicOr(err, MSM_DEV_ERR_BAD_INDEX);
+    }
+    const uint4* in = reinterpret_cast<const uint4*>(recs) + (size_t)idx * 8;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+      const uint4 v = live ? in[q] : make_uint4(0u, 0u, 0u, 0u);
+      rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+    }
+    __syncthreads();
+  } else {
+    const uint4* in = reinterpret_cast<const uint4*>(recs) + ((size_t)first + p0) * 8;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+      const uint32_t g = j * SC_THREADS + threadIdx.x;
+      if (g < np * 8) st[pp_slot(g >> 3, g & 7)] = in[g];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+      // lanes past the block's last point work on zeros, as k_shift_bases', and write nothing
+      const uint4 v = live ? st[pp_slot(i, q)] : make_uint4(0u, 0u, 0u, 0u);
+      rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+    }
+  }
+  const uint32_t* my = ssc + i * sw;
+  const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
+  if (live && (my[0] & ~top_mask)) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  fe ymx, ypx;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    ymx.v[k] = rec[k];
+    ypx.v[k] = rec[PRE_HALF + k];
+  }
+  // (X : Y : T : Z) = (x : y : x y : 1) from the halved record, limb forms as in k_shift_bases
+  const fe one = fe_one();
+  const fe a = fe_mul(ymx, one);   // (y-x)/2, N_MUL
+  const fe xs = fe_sub(ypx, a);    // x + 8p: normalised, < 12p
+  const fe ys = fe_add_n(ypx, a);  // y: normalised, < 6p
+  xyzt p1;
+  p1.X = fe_mul(xs, one);
+  p1.Y = fe_mul(ys, one);
+  p1.T = fe_mul(xs, ys);
+  p1.Z = one;
+  xyzt acc = pt_identity();
+  const xyzt p2 = pt_dbl(p1);
+  const xyzt p3 = pt_add(p2, p1);
+  const xyzt p0i = pt_identity();
+#pragma unroll 1
+  for (uint32_t j = scale_windows(b); j-- > 0;) {
+    acc = pt_dbl(pt_dbl(acc));
+    const uint32_t d = live ? scale_digit(my, sw, b, j) : 0u;
+    const bool hi = (d & 2u) != 0;
+    acc = pt_add(acc, pt_sel((d & 1u) != 0, pt_sel(hi, p0i, p2), pt_sel(hi, p1, p3)));
+  }
+  const fe zi = fe_inv(acc.Z);
+  const fe x = fe_mul(acc.X, zi);
+  const fe y = fe_mul(acc.Y, zi);
+  uint32_t xw[8], yw[8], tw[8];
+  fe_to_words_le(fe_to_std(x), xw);
+  fe_to_words_le(fe_to_std(y), yw);
+  fe_to_words_le(fe_to_std(fe_mul(x, y)), tw);
+  __syncthreads();
+  // big-endian word order: word 0 is the most significant 32 bits
+  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
+  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
+  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
+  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
+  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
+  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
+  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
+  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+  __syncthreads();
+  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
+  uint4* dst = reinterpret_cast<uint4*>(out) + ((size_t)p0 << sh);
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * SC_THREADS + threadIdx.x;
+    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
+  }
+}
+
 // The virtual scalars of a folded launch (levels = k > 1): out[m][j n + i] = bits [j S, (j+1) S)
 // of scalar i of MSM m, wire layout (32 B, big-endian words, upper bits zero).  blockIdx.y = level
 // j, blockIdx.z = MSM of the batch (its wire scalars from scalar_sets.p[z], its k n virtual

@@ -31,6 +31,8 @@
 //   computeMsmPrepared(id, scalars: Uint32Array(8m), first?: number, indices?: Uint32Array(m),
 //                      scalarBits?: number)   (scalarBits = b: ceil(b / 32) words per scalar)
 //       over a subset of the bases: the range [first, first + m), or bases indices[0..m)
+//   scaleBases(id, scalars: Uint32Array(8m), first?, indices?, scalarBits?, asBases?, levels?, windowSize?)
+//       -> Uint32Array(32m), the wire points s_i * P_i, or with asBases the object of a new handle
 //   releaseBases(id) -> number (0 ok, -1 for a handle already released)
 //   Handles left open are freed by the cleanup hook's msm_shutdown.
 #include <node_api.h>
@@ -578,6 +580,8 @@ const msm_bases* get_handle(napi_env env, napi_value v) {
   return reinterpret_cast<const msm_bases*>((uintptr_t)id);
 }
 
+napi_value bases_object(napi_env env, msm_bases* h);
+
 // prepareBases(points, levels?, windowSize?, form?): with `form` (MSM_POINTS_X_*) the array holds
 // compressed points, 8 words each, and y is recovered on the device (msm_bases_create_compressed).
 napi_value PrepareBases(napi_env env, napi_callback_info info) {
@@ -601,8 +605,13 @@ napi_value PrepareBases(napi_env env, napi_callback_info info) {
   int rc = form ? msm_bases_create_compressed(pts, plen / 8, form, &o, levels, &h)
                 : msm_bases_create(pts, plen / 32, &o, levels, &h);
   if (rc != MSM_OK) return throw_rc(env, rc);
+  return bases_object(env, h);
+}
+
+// The object prepareBases and scaleBases hand out for a new handle: its id and what msm_bases_info says.
+napi_value bases_object(napi_env env, msm_bases* h) {
   msm_bases_info_t inf;
-  rc = msm_bases_info(h, &inf);
+  int rc = msm_bases_info(h, &inf);
   if (rc != MSM_OK) return throw_rc(env, rc);
   napi_value obj, v;
   NAPI_OK(napi_create_object(env, &obj));
@@ -636,6 +645,67 @@ napi_value DecompressPoints(napi_env env, napi_callback_info info) {
   int rc = msm_decompress_points(xs, n, get_window(env, argv[1]), nullptr, out.data());
   if (rc != MSM_OK) return throw_rc(env, rc);
   return make_u32(env, out.data(), n * 32);
+}
+
+// scaleBases(id, scalars, first?, indices?, scalarBits?, asBases?, levels?, windowSize?): the per-point
+// multiples s_i * P_i of a handle's bases (msm_bases_scale; synchronous, as prepareBases is) -- all of
+// them, the range from `first`, or bases indices[i]; the scalar array gives m.  A Uint32Array of m x 32
+// wire words, or with `asBases` the object of a new handle (msm_bases_scale_create).
+napi_value ScaleBases(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  const bool has_first = given(2), has_idx = given(3), has_bits = given(4);
+  const uint32_t* sc;
+  const uint32_t* ix = nullptr;
+  size_t slen, ilen = 0;
+  double first = 0, bits = 0;
+  bool as_bases = false;
+  if (argc < 2 || !h || !get_u32_array(env, argv[1], &sc, &slen) ||
+      (has_first && (napi_get_value_double(env, argv[2], &first) != napi_ok || !(first >= 0) ||
+                     first > 9007199254740992.0 || first != (double)(uint64_t)first)) ||
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen)) ||
+      (has_bits && (napi_get_value_double(env, argv[4], &bits) != napi_ok || bits != (double)(uint32_t)bits)) ||
+      (given(5) && napi_get_value_bool(env, argv[5], &as_bases) != napi_ok)) {
+    napi_throw_type_error(env, nullptr,
+                          "scaleBases(id: number, scalars: Uint32Array, first?: number, indices?: Uint32Array, "
+                          "scalarBits?: number, asBases?: boolean, levels?: number, windowSize?: number)");
+    return nullptr;
+  }
+  if (has_bits && (bits < 1 || bits > 256)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  const size_t sw = has_bits ? ((size_t)bits + 31) / 32 : 8;  // words per scalar
+  const size_t m = slen / sw;
+  if (has_idx && ilen != m) {
+    napi_throw_range_error(env, nullptr, "one index per scalar");
+    return nullptr;
+  }
+  msm_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = -1;
+  o.window_bits = given(7) ? get_window(env, argv[7]) : 0;
+  if (has_bits) {
+    o.flags |= MSM_FLAG_SCALAR_BITS;
+    o.scalar_bits = (uint32_t)bits;
+  }
+  msm_subset_t sub;
+  sub.first = (uint64_t)first;
+  sub.m = m;
+  sub.indices = has_idx ? &ix : nullptr;
+  if (as_bases) {
+    msm_bases* nh = nullptr;
+    int rc = msm_bases_scale_create(h, &sub, sc, &o, given(6) ? get_window(env, argv[6]) : 0, &nh);
+    if (rc != MSM_OK) return throw_rc(env, rc);
+    return bases_object(env, nh);
+  }
+  std::vector<uint32_t> out(m * 32 + 1);
+  int rc = msm_bases_scale(h, &sub, sc, &o, out.data());
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  return make_u32(env, out.data(), m * 32);
 }
 
 // computeMsmPrepared(id, scalars[, first, indices]): with `first` (a number) or `indices` (a
@@ -879,6 +949,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"computeMsmPrepared", nullptr, ComputeMsmPrepared, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"releaseBases", nullptr, ReleaseBases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decompressPoints", nullptr, DecompressPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"scaleBases", nullptr, ScaleBases, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

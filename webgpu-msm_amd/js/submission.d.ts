@@ -59,6 +59,19 @@ export declare const compute_msm_prepared: (
   scalars: bigint[] | Uint32Array[] | Uint32Array | NativeScalars,
   subset?: BasesSubset
 ) => Promise<{ x: bigint; y: bigint }>;
+// Per-point multiples s_i * P_i of a handle's bases (all of them, the range from `first`, or bases
+// indices[i]): m x 32 wire words, or with asBases a new handle of those points.  Synchronous.
+export type ScaleOptions = { first?: number; indices?: Uint32Array; scalarBits?: number; levels?: number; windowSize?: number };
+export declare function scale_bases_prepared(
+  handle: BasesHandle,
+  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  options?: ScaleOptions & { asBases?: false }
+): Uint32Array;
+export declare function scale_bases_prepared(
+  handle: BasesHandle,
+  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  options: ScaleOptions & { asBases: true }
+): BasesHandle;
 export declare function release_bases(handle: BasesHandle): number;
 
 export declare function getBestWindowSize(n: number): number;

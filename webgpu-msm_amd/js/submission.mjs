@@ -316,6 +316,24 @@ export const compute_msm_prepared = async (handle, scalars, subset) => {
   return { x, y };
 };
 
+// The per-point multiples s_i * P_i of a handle's bases (msm_bases_scale*): a flat Uint32Array of
+// m x 32 wire words (x|y|t|z, z = 1), m = the number of scalars, over all the bases, the range
+// { first } or the bases { indices } (repeats allowed: zeros give s_i * P_0).  Scalars are bigint[] or
+// Uint32Array as in compute_msm_prepared, narrow with { scalarBits }; the integer is not reduced mod
+// r.  { asBases: true } keeps the points on the GPU and returns a new handle instead ({ levels,
+// windowSize } as in prepare_bases), which compute_msm_prepared and release_bases accept.
+// Synchronous, as prepare_bases is.
+export function scale_bases_prepared(handle, scalars, options) {
+  if (!handle || typeof handle.id !== "number") throw new TypeError("scale_bases_prepared(handle, scalars): not a handle");
+  const { first, indices, scalarBits, asBases, levels } = options || {};
+  if (scalarBits !== undefined && !(Number.isInteger(scalarBits) && scalarBits >= 1 && scalarBits <= 256))
+    throw new RangeError("options.scalarBits: an integer in 1..256");
+  if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("options.indices: a Uint32Array");
+  if (first !== undefined && !(Number.isSafeInteger(first) && first >= 0)) throw new RangeError("options.first: a non-negative integer");
+  return addon.scaleBases(handle.id, scalarWords(scalars, scalarBits), first === undefined ? 0 : first, indices, scalarBits,
+                          !!asBases, levels ? levels | 0 : 0, windowFrom(options));
+}
+
 export function release_bases(handle) {
   if (!handle || typeof handle.id !== "number") throw new TypeError("release_bases(handle): not a handle");
   return addon.releaseBases(handle.id);

@@ -192,6 +192,13 @@ def load() -> ctypes.CDLL:
         "msm_bases_compute_subset_device": ([vp, ctypes.POINTER(Subset), vp, optp, vp, u32p], ctypes.c_int),
         "msm_bases_compute_subset_many": ([vp, ctypes.POINTER(Subset), vp, sz, optp, u32p], ctypes.c_int),
         "msm_bases_compute_subset_many_device": ([vp, ctypes.POINTER(Subset), vp, sz, optp, vp, u32p], ctypes.c_int),
+        "msm_bases_scale": ([vp, ctypes.POINTER(Subset), vp, optp, vp], ctypes.c_int),
+        "msm_bases_scale_device": ([vp, ctypes.POINTER(Subset), vp, optp, vp, vp], ctypes.c_int),
+        "msm_bases_scale_create": ([vp, ctypes.POINTER(Subset), vp, optp, ctypes.c_uint32, ctypes.POINTER(vp)],
+                                   ctypes.c_int),
+        "msm_bases_scale_create_device": ([vp, ctypes.POINTER(Subset), vp, optp, ctypes.c_uint32, vp,
+                                           ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_test_scale_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
         "msm_test_subset_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -1080,6 +1087,77 @@ class Bases:
                "msm_bases_compute_subset_many_device")
         return o[:16 * count].reshape(count, 16)
 
+    # ---- per-point scalar multiples (include/msm.h msm_bases_scale*) ----
+    # Q_i = s_i * P_i over all the bases, the range [first, first + m) or bases indices[i] (repeats
+    # allowed: zeros give the fixed-base batch s_i * P_0).  Scalars are wire words, or narrow ones with
+    # `scalar_bits`; the integer is not reduced mod r.
+
+    def _scale_subset(self, m: int, first: int, indices, host: bool):
+        """The msm_subset_t of a scale call by reference (None: all the bases), and what it keeps alive."""
+        if indices is None and not first and m == self.info["n"]:
+            return None, None
+        if indices is None:
+            return ctypes.byref(self._subset(first, m, None)), None
+        if host:
+            keep, ptrs = self._host_indices(indices, m, 1)
+        else:
+            keep, ptrs = indices, self._device_indices(indices, 1)
+        sub = self._subset(first, m, ptrs)
+        return ctypes.byref(sub), (keep, sub)
+
+    def scale(self, scalars, first: int = 0, indices=None, scalar_bits: Optional[int] = None) -> np.ndarray:
+        """s_i * P_i for host scalars: wire records [m, 32] (x | y | t | z = 1, canonical)."""
+        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
+        m = sc.shape[0]
+        sub, keep = self._scale_subset(m, first, indices, True)
+        out = np.zeros((m, 32), dtype=np.uint32)
+        _check(load().msm_bases_scale(self._h or None, sub, _ptr(sc), _opts(None, scalar_bits=scalar_bits), _ptr(out)),
+               "msm_bases_scale")
+        return out
+
+    def scale_device(self, d_scalars, d_out, m: Optional[int] = None, first: int = 0, indices=None,
+                     scalar_bits: Optional[int] = None, stream: int = 0) -> None:
+        """The same between device buffers (torch tensors, or raw pointers with `m`): d_out takes m x 32
+        words (16-byte aligned, not overlapping the scalars); complete on return."""
+        m = len(d_scalars) if m is None else int(m)
+        sub, keep = self._scale_subset(m, first, indices, False)
+        _check(load().msm_bases_scale_device(self._h or None, sub, _dev_ptr(d_scalars),
+                                             _opts(None, scalar_bits=scalar_bits),
+                                             _stream(stream, d_scalars, indices, d_out), _dev_ptr(d_out)),
+               "msm_bases_scale_device")
+
+    def scaled(self, scalars, first: int = 0, indices=None, scalar_bits: Optional[int] = None, levels: int = 0,
+               window_size: Optional[int] = None) -> "Bases":
+        """A new handle of the points s_i * P_i, which never leave the device: the handle
+        Bases.from_wire(self.scale(...)) makes."""
+        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
+        sub, keep = self._scale_subset(sc.shape[0], first, indices, True)
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_scale_create(self._h or None, sub, _ptr(sc),
+                                             _opts(window_size, scalar_bits=scalar_bits), int(levels),
+                                             ctypes.byref(h)), "msm_bases_scale_create")
+        return Bases(h.value or 0)
+
+    def scaled_device(self, d_scalars, m: Optional[int] = None, first: int = 0, indices=None,
+                      scalar_bits: Optional[int] = None, levels: int = 0, window_size: Optional[int] = None,
+                      stream: int = 0) -> "Bases":
+        """The same with device-resident scalars (and indices)."""
+        m = len(d_scalars) if m is None else int(m)
+        sub, keep = self._scale_subset(m, first, indices, False)
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_scale_create_device(self._h or None, sub, _dev_ptr(d_scalars),
+                                                    _opts(window_size, scalar_bits=scalar_bits), int(levels),
+                                                    _stream(stream, d_scalars, indices), ctypes.byref(h)),
+               "msm_bases_scale_create_device")
+        return Bases(h.value or 0)
+
+    def points(self, first: int = 0, m: Optional[int] = None, indices=None) -> np.ndarray:
+        """The wire records [m, 32] of the handle's own points (all, a range or an index list): scale by
+        ones at scalar_bits = 1.  A handle made from x-coordinates has no other copy of its y."""
+        if m is None:
+            m = len(indices) if indices is not None else self.info["n"] - int(first)
+        return self.scale(np.ones((max(int(m), 0), 1), dtype=np.uint32), first, indices, scalar_bits=1)
+
     def close(self) -> None:
         """Free the records.  Closing twice is harmless."""
         h, self._h = self._h, 0
@@ -1299,6 +1377,19 @@ def _test_decompress_constants() -> dict:
     le = lambda w: sum(int(v) << (32 * i) for i, v in enumerate(w))  # noqa: E731
     return {"two_adicity": int(o[0]), "exp_words": int(o[1]), "order_bits": int(o[2]), "exp": le(o[3:11]),
             "order": le(o[11:19]), "omega_mont_limbs": [int(v) for v in o[19:28]]}
+
+
+def _test_scale_digits(value: int, scalar_bits: int) -> list:
+    """The scale ladder's windows of one `scalar_bits`-bit value, least significant first, by the
+    kernel's own digit function run on the host (msm_test_scale_digits); their number is the ladder's
+    trip count.  Needs no device."""
+    sc = scalars_to_wire([int(value)], scalar_bits)
+    digits = np.zeros(256, dtype=np.uint32)
+    count = ctypes.c_uint32()
+    _check(load().msm_test_scale_digits(_ptr(sc), sc.shape[1], int(scalar_bits),
+                                        digits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(count)),
+           "msm_test_scale_digits")
+    return [int(d) for d in digits[:count.value]]
 
 
 def _test_limb_op(name: str, a, b=None, neg=None) -> np.ndarray:
