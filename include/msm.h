@@ -558,6 +558,78 @@ int msm_bases_scale_create(const msm_bases* bases, const msm_subset_t* subset, c
 int msm_bases_scale_create_device(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* d_scalars_be,
                                   const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out);
 
+/* Fixed-base tables: Q_i = sum_(j<k) s_ij * B_j for m rows of scalars over the same k bases (ark-ec's
+ * FixedBase::msm / batch_mul on a generator, beside the two above): powers-of-tau and SRS generation
+ * ([tau^i] G), batches of public keys or nonces (k_i * G), of Pedersen commitments (v_i * G + r_i * H),
+ * the s * G legs of a folding step.  msm_bases_scale with an all-zero index vector computes the k = 1
+ * case with a whole ladder per output; a table turns an output into one mixed addition per window and
+ * base with no doubling, and one inversion shared by eight outputs (k_fixed_eval, k_fixed_normalise;
+ * DESIGN.md §9 has the measured cost).
+ *
+ * msm_fixed_create builds the table of k bases, 1 <= k <= 8, taken from level 0 of a handle with a
+ * msm_subset_t as msm_bases_scale reads it: NULL (all n bases, so n <= 8), the range
+ * [first, first + m), or indices[0][0..m) (host array, first == 0, repeats allowed); k = m.  A handle
+ * made from x-coordinates, or from points with z != 1, serves as any other.  window_bits = w is 2..16,
+ * or 0 for the library's choice (12); scalar_bits = b is 1..256, or 0 for 256: the widest scalar the
+ * table serves.  The table holds, for every base and every window win < W = ceil((b + 1) / w), the
+ * multiples d * 2^(w win) * B_j, d = 1 .. 2^(w-1), as prepared records -- entry (j, win, d) at
+ * (j W + win) 2^(w-1) + d - 1, exactly the records msm_bases_create makes of those affine points --
+ * k W 2^(w-1) 128 bytes in all (5.5 MiB per base at w = 12, b = 256; 528 KiB at w = 8).  The build
+ * stages the points in the device context's workspace at half the table's size, which the context
+ * keeps until msm_shutdown.  A table above 256 MiB, k outside 1..8, w or b outside their ranges:
+ * MSM_ERR_INVALID_ARG before any allocation.  opts: device -1 or
+ * the handle's own; MSM_FLAG_DEVICES, _WINDOWS, _HALF_WINDOWS, _SCALAR_BITS, _SCALAR_TYPE and
+ * _SCALAR_FIELD give MSM_ERR_INVALID_ARG; NULL is fine.  The table owns its records: the source handle
+ * may be destroyed at once.  msm_fixed_destroy frees a table, msm_shutdown every live one; a table is a
+ * registry token as a handle is, and a stale one gives MSM_ERR_INVALID_ARG.  A failed creation leaves
+ * *out null and nothing allocated.
+ *
+ * Scalars: scalars_be[(i k + j) sw ..] is s_ij, sw = 8 big-endian words, or ceil(b' / 32) with
+ * MSM_FLAG_SCALAR_BITS and scalar_bits = b' in 1..b (a call wider than its table: MSM_ERR_INVALID_ARG).
+ * The scalar is the integer it is and is not reduced mod r.  An 8-word call on a table of b < 256 is
+ * read at the table's width.  The cost follows the call's width: ceil((b' + 1) / w) additions per
+ * scalar.  MSM_FLAG_SCALAR_TYPE, _SCALAR_FIELD, _DEVICES, _WINDOWS and _HALF_WINDOWS give
+ * MSM_ERR_INVALID_ARG before any device work; opts->device is -1 or the table's own; m < 2^30.
+ *
+ * msm_fixed_mul* write m wire records x | y | t = x y | z = 1, word for word what msm_bases_scale
+ * writes for the same point (the identity: (0, 1, 0, 1)).  msm_fixed_mul_create* keep the m points as
+ * a new msm_bases handle, without their leaving the device: its level 0 is bit-identical to what
+ * msm_bases_create makes from the records msm_fixed_mul returns; `levels` and opts->window_bits mean
+ * what they mean there, and so do the limits and the errors of a creation.  m = 0: the mul entries
+ * return MSM_OK and write nothing, the create entries return an empty handle.  Results are specified
+ * for on-curve bases.
+ *
+ * A scalar bit at or above the call's width gives MSM_ERR_INVALID_ARG: from the host entries before
+ * anything is uploaded or enqueued; from the device entries after the launch, which masks the bit and
+ * runs to its end (the output is then unspecified, a creation leaves nothing allocated, and the table
+ * stays usable).  Device pointers: d_points_be and 8-word scalars 16-byte aligned, narrow scalars
+ * 4-byte aligned (MSM_ERR_INVALID_ARG, decided from the pointer value before anything is enqueued);
+ * output and scalars must not overlap.  The device entries are ordered after the work queued on
+ * hip_stream and return when the result is complete.  A null argument: MSM_ERR_INVALID_ARG. */
+typedef struct msm_fixed msm_fixed;
+typedef struct msm_fixed_info_t {
+  uint32_t bases;       /* k                                                            */
+  uint32_t window_bits; /* w                                                            */
+  uint32_t scalar_bits; /* b: the widest scalar served                                  */
+  uint32_t windows;     /* W = ceil((b + 1) / w), windows per base                      */
+  uint64_t records;     /* k * W * 2^(w-1)                                              */
+  uint64_t bytes;       /* device memory of the records: records * 128                  */
+  int32_t device;       /* HIP ordinal the records live on                              */
+  uint32_t reserved;    /* 0 */
+} msm_fixed_info_t;
+int msm_fixed_create(const msm_bases* bases, const msm_subset_t* subset, uint32_t window_bits, uint32_t scalar_bits,
+                     const msm_opts* opts, msm_fixed** out);
+int msm_fixed_destroy(msm_fixed* table);
+int msm_fixed_info(const msm_fixed* table, msm_fixed_info_t* out);
+int msm_fixed_mul(const msm_fixed* table, const uint32_t* scalars_be /* [m][k][sw] */, size_t m, const msm_opts* opts,
+                  uint32_t* points_be /* [m][32] wire records */);
+int msm_fixed_mul_device(const msm_fixed* table, const uint32_t* d_scalars_be, size_t m, const msm_opts* opts,
+                         void* hip_stream, uint32_t* d_points_be);
+int msm_fixed_mul_create(const msm_fixed* table, const uint32_t* scalars_be, size_t m, const msm_opts* opts,
+                         uint32_t levels, msm_bases** out);
+int msm_fixed_mul_create_device(const msm_fixed* table, const uint32_t* d_scalars_be, size_t m, const msm_opts* opts,
+                                uint32_t levels, void* hip_stream, msm_bases** out);
+
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,
  * 7M mixed adds into per-thread bucket tables.  window_bits 0 = auto, n_threads <= 0 = all

@@ -97,6 +97,18 @@ Then, in the same process, what the library offered for the same result before: 
 compute_subset_many_device, at m in --scale-msm-sizes (default 2^10 and 2^12), as a row of its own
 ("form": "one_term_msms"), checked against the scale call.  All sizes run in one child process.
 
+With --fixed the pass is the fixed-base table sweep of DESIGN.md §9 (msm_fixed_*): for b in --fixed-bits
+(default 64,128,253,256), first the baseline in the same process on the same scalars -- Bases.scale_device
+with an all-zero index vector, m in --fixed-sizes (log2; default 12..20), "form": "scale_zero_indices" --
+then for w in --fixed-widths (default 6,8,10,12) and k in --fixed-bases (default 1,2) the table's build
+("form": "table_build", timed with its destroy) and per m
+
+  {"entry": "fixed", "m", "bits", "w", "k", "form": "device" | "host", "ms", "ns_per_point", "ratio_to_scale"}
+
+the awaited device-to-device call and the host entry (scalars up, wire records back); four sampled rows are
+checked against the oracle's scalar multiplication and the host result against the device one.
+ratio_to_scale (k = 1, device) is the baseline's median over this row's.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -760,6 +772,83 @@ def scale_pass(a):
     return 1 if bad else 0
 
 
+def fixed_pass(a):
+    """--fixed: every size of the fixed-base sweep in this one process (one context, one torch import)."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from oracle import oracle as O
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def affine(rec):
+        return (O.be_words_to_int(rec[:8]), O.be_words_to_int(rec[8:16]))
+
+    bad = 0
+    rng = np.random.default_rng(2025)
+    pts = M.gen_points(2, k0=3, step=5)
+    aff = [affine(p) for p in pts]
+    mmax = 1 << a.fixed_sizes[-1]
+    d_out = torch.zeros((mmax, 32), dtype=torch.int32, device="cuda")
+    d_zero = dev(np.zeros(mmax, np.uint32))
+    with M.Bases.from_wire(pts, levels=1) as b:
+        for bits in a.fixed_bits:
+            sw = (bits + 31) // 32
+            kw = {} if bits == 256 else {"scalar_bits": bits}
+            sc_all = rng.integers(0, 1 << 32, size=(mmax, 2, sw), dtype=np.uint64).astype(np.uint32)
+            if bits % 32:
+                sc_all[:, :, 0] &= (1 << (bits % 32)) - 1
+            # the baseline, same process and same scalars: the ladder on base 0 (an index vector of zeros)
+            base_ms = {}
+            for lg in a.fixed_sizes:
+                m = 1 << lg
+                d_sc = dev(sc_all[:m, 0])
+                torch.cuda.synchronize()
+                ms, runs, _ = timed(lambda: b.scale_device(d_sc, d_out[:m], indices=d_zero[:m], **kw), a.runs)
+                base_ms[m] = ms
+                emit({"entry": "fixed", "m": m, "bits": bits, "k": 1, "form": "scale_zero_indices", "ms": round(ms, 4),
+                      "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs})
+            for w in a.fixed_widths:
+                for k in a.fixed_bases:
+                    ms, runs, t = timed(lambda: b.fixed_table(first=0, count=k, window_bits=w, scalar_bits=bits), a.runs)
+                    emit({"entry": "fixed", "bits": bits, "w": w, "k": k, "form": "table_build", "ms": round(ms, 4),
+                          "bytes": t.info["bytes"], "runs_ms": runs})
+                    with t:
+                        for lg in a.fixed_sizes:
+                            m = 1 << lg
+                            sc = np.ascontiguousarray(sc_all[:m, :k])
+                            d_sc = dev(sc)
+                            torch.cuda.synchronize()
+                            rows = {"device": timed(lambda: t.mul_device(d_sc, d_out[:m], **kw), a.runs)}
+                            got = d_out[:m].cpu().numpy().view(np.uint32)
+                            sample = [0, m - 1] + [int(i) for i in rng.integers(0, m, size=2)]
+                            correct = True
+                            for i in sample:
+                                acc = (0, 1)
+                                for j in range(k):
+                                    acc = M.point_add_affine(acc, O.c_scalar_mul(aff[j], O.be_words_to_int(sc[i, j])))
+                                correct = correct and affine(got[i]) == acc and got[i][31] == 1
+                            rows["host"] = timed(lambda: t.mul(sc, **kw), a.runs)
+                            correct = correct and bool(np.array_equal(rows["host"][2], got))
+                            for form, (ms, runs, _) in rows.items():
+                                d = {"entry": "fixed", "m": m, "bits": bits, "w": w, "k": k, "form": form,
+                                     "ms": round(ms, 4), "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs,
+                                     "correct": bool(correct)}
+                                if form == "device" and k == 1:
+                                    d["ratio_to_scale"] = round(base_ms[m] / ms, 2)
+                                emit(d)
+                            bad += not correct
+    return 1 if bad else 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -821,12 +910,30 @@ def main():
     ap.add_argument("--scale-bits", default="64,128,253,256", help="scalar widths b of the scale sweep")
     ap.add_argument("--scale-msm-sizes", default="10,12", help="log2 m at which the one-term-MSM route is timed too")
     ap.add_argument("--scale-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--fixed", action="store_true", help="the fixed-base table sweep (msm_fixed_*) instead")
+    ap.add_argument("--fixed-sizes", default="12,13,14,15,16,17,18,19,20", help="log2 row counts m of the fixed sweep")
+    ap.add_argument("--fixed-bits", default="64,128,253,256", help="scalar widths b of the fixed sweep")
+    ap.add_argument("--fixed-widths", default="6,8,10,12", help="window widths w of the fixed sweep")
+    ap.add_argument("--fixed-bases", default="1,2", help="base counts k of the fixed sweep")
+    ap.add_argument("--fixed-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
     a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
     if a.dense:
         return dense_sweep(a)
+    if a.fixed:
+        lists = {"--fixed-sizes": "fixed_sizes", "--fixed-bits": "fixed_bits", "--fixed-widths": "fixed_widths",
+                 "--fixed-bases": "fixed_bases"}
+        for name in lists.values():
+            setattr(a, name, sorted(int(x) for x in str(getattr(a, name)).split(",") if x))
+        if a.fixed_child:
+            return fixed_pass(a)
+        cmd = ["timeout", "-k", "10", str(a.step_timeout * 3), sys.executable, os.path.abspath(__file__), "--fixed",
+               "--fixed-child", "--runs", str(a.runs)] + (["--out", a.out] if a.out else [])
+        for flag, name in lists.items():
+            cmd += [flag, ",".join(map(str, getattr(a, name)))]
+        return subprocess.run(cmd).returncode
     if a.scale:
         a.scale_bits = [int(x) for x in str(a.scale_bits).split(",") if x]
         a.scale_msm_sizes = [int(x) for x in str(a.scale_msm_sizes).split(",") if x]

@@ -175,6 +175,7 @@ struct Workspace {
   Buf sub_idx;             // base indices [nm][m] of an indexed subset launch (msm_bases_compute_subset*)
   Buf seg_base, unit_key, partials;  // the dense-bucket accumulation's segment map and per-unit sums (Plan::dense)
   Buf dx_pts;              // k_decompress_x's output: x|y of a compressed creation, wire records of msm_decompress_points
+  Buf fx_proj;             // k_fixed_eval's points (X : Y : Z) in blocks of 64, read by k_fixed_normalise (msm_fixed_mul*)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
@@ -188,7 +189,7 @@ struct Workspace {
     WS_BUF(lead_val), WS_BUF(lead_open), WS_BUF(cross_key), WS_BUF(lead_flag), WS_BUF(skew_list);
     WS_BUF(g_head), WS_BUF(g_hkey), WS_BUF(g_tkey), WS_BUF(red_U), WS_BUF(red_T);
     WS_BUF(wire_pts), WS_BUF(wire_sc), WS_BUF(red_G), WS_BUF(split_sc), WS_BUF(sub_idx);
-    WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials), WS_BUF(dx_pts);
+    WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials), WS_BUF(dx_pts), WS_BUF(fx_proj);
 #ifdef MSM_DUMMY_ALLOC
     WS_BUF(dummy_tiles), WS_BUF(dummy_cursor);
 #endif
@@ -269,6 +270,7 @@ class PackPool;
 struct DevCtx;
 void ctx_drop_pools(DevCtx* c);     // host_tail.h: stops and deletes the context's three pools
 void release_bases_on(int device);  // host_bases.h: frees the records of every handle on the device
+void release_fixed_on(int device);  // host_fixed.h: and of every fixed-base table
 using clk = std::chrono::steady_clock;
 
 // Pinned staging buffers of the packed host upload (run_host_split with host_pack()): the
@@ -389,6 +391,7 @@ struct DevCtx {
     for (Slot& sl : slot) hipStreamSynchronize(sl.stream);
     each_buf([](const char*, Buf& b) { b.release(); });
     release_bases_on(device);
+    release_fixed_on(device);
     for (Slot& sl : slot) {
       sl.ws.release();
       for (Segment& sg : sl.seg) sg.drop();

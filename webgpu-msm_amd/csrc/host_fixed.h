@@ -1,0 +1,252 @@
+// Layer 12, fixed-base tables (msm_fixed_*): the table registry, the table build, and the evaluation
+// entries' common path.  Depends on the layers above it (knobs .. bases).
+#pragma once
+// A table's state, kept as a handle's is (host_bases.h Bases): the caller's msm_fixed* is a registry
+// token out of the handles' own counter, so no token names both a handle and a table; `rec` is freed,
+// and `alive` cleared, under the owning device context's lock.
+struct Fixed {
+  int device = -1;
+  uint32_t k = 0;   // bases
+  uint32_t w = 0;   // window width
+  uint32_t b = 0;   // widest scalar the table serves
+  uint32_t Wn = 0;  // windows per base: fixed_windows(b, w)
+  Buf rec;          // k Wn 2^(w-1) records, entry (j, win, d) at (j Wn + win) 2^(w-1) + d - 1
+  bool alive = false;
+  size_t records() const { return ((size_t)k * Wn) << (w - 1); }
+  template <typename F>
+  void each_buf(F&& f) {  // as Workspace::each_buf; the guard reports name a table's records as a handle's
+    f("bases_rec", rec);
+  }
+};
+std::map<uintptr_t, std::shared_ptr<Fixed>> g_fixed;  // under g_mu
+
+std::shared_ptr<Fixed> find_fixed(const msm_fixed* h) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_fixed.find(reinterpret_cast<uintptr_t>(h));
+  return it == g_fixed.end() ? nullptr : it->second;
+}
+
+// Every live table's records on `device` (DevCtx::destroy, under g_mu and the context's lock).
+void release_fixed_on(int device) {
+  for (auto& kv : g_fixed)
+    if (kv.second->device == device) {
+      kv.second->alive = false;
+      kv.second->each_buf([](const char*, Buf& b) { b.release(); });
+    }
+}
+
+// The shape of a table of k bases: window width (0: FX_AUTO_W, the width DESIGN.md §9's sweep chose),
+// scalar width (0: 256), windows and records, inside the limits msm.h states.  Needs no device.
+constexpr uint32_t FX_AUTO_W = 12;
+constexpr uint64_t FX_MAX_BYTES = 256ull << 20;
+struct FixedPlan {
+  uint32_t w, b, Wn;
+  uint64_t records, bytes;
+};
+int fixed_plan(uint64_t k, uint32_t w, uint32_t b, FixedPlan* out) {
+  if (k < 1 || k > FX_MAX_BASES) return MSM_ERR_INVALID_ARG;
+  if (!w) w = FX_AUTO_W;
+  if (!b) b = 256;
+  if (w < 2 || w > 16 || b > 256) return MSM_ERR_INVALID_ARG;
+  out->w = w;
+  out->b = b;
+  out->Wn = fixed_windows(b, w);
+  out->records = (k * out->Wn) << (w - 1);
+  out->bytes = out->records * PRE_WORDS * 4;
+  return out->bytes > FX_MAX_BYTES ? MSM_ERR_INVALID_ARG : MSM_OK;
+}
+
+// msm_fixed_create: the table of the k bases `sub` selects from a handle's level 0 (null: all of them),
+// built on slot 0's stream -- k_fixed_build writes every entry's x|y into the slot's dx_pts, and the
+// preparation makes the records from there, as a compressed creation's does.
+int fixed_create(const msm_bases* h, const msm_subset_t* sub, uint32_t w, uint32_t bits, const msm_opts* opts,
+                 msm_fixed** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!h || !bases_flags_ok(opts) || narrow_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Bases> b = find_bases(h);
+  if (!b) return MSM_ERR_INVALID_ARG;
+  if (opts && opts->device >= 0 && opts->device != b->device) return MSM_ERR_INVALID_ARG;
+  const uint32_t* indices = sub && sub->indices ? sub->indices[0] : nullptr;
+  const uint64_t k = sub ? sub->m : b->n, first = sub ? sub->first : 0;
+  FixedPlan fp;
+  if (int rc = fixed_plan(k, w, bits, &fp)) return rc;
+  if (sub) {
+    if (int rc = subset_check(b->n, 1, sub->first, sub->m, sub->indices != nullptr)) return rc;
+    if (sub->indices && !indices) return MSM_ERR_INVALID_ARG;
+  }
+  FixedBaseIdx bi{};
+  for (uint32_t j = 0; j < k; j++) {
+    bi.v[j] = indices ? indices[j] : (uint32_t)(first + j);
+    if (bi.v[j] >= b->n) return MSM_ERR_INVALID_ARG;
+  }
+  auto t = std::make_shared<Fixed>();
+  t->k = (uint32_t)k;
+  t->w = fp.w;
+  t->b = fp.b;
+  t->Wn = fp.Wn;
+  msm_opts od{};
+  od.device = b->device;
+  int rc = on_device(&od, [&](DevCtx* c) -> int {
+    if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    t->device = c->device;
+    Slot& s0 = c->slot[0];
+    Buf errb;  // the preparation's error word
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if ((r = t->rec.ensure(fp.bytes)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    auto done = [&](int code) {  // as create_bases'
+      drain_streams(c, 1, code);
+      if (errb.base) {
+        std::lock_guard<std::mutex> gl(g_guard_mu);
+        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+      }
+      errb.release();
+      if (code != MSM_OK) t->rec.release();
+      return code;
+    };
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = s0.ws.dx_pts.ensure(fp.records * 64)) != MSM_OK) return done(r);
+    uint32_t* xy = s0.ws.dx_pts.as<uint32_t>();
+    hipLaunchKernelGGL(k_fixed_build, dim3(grid_for(fp.records, FX_THREADS)), dim3(FX_THREADS), 0, s0.stream,
+                       b->rec.as<uint32_t>(), bi, fp.w, fp.Wn, xy, (uint32_t)fp.records);
+    launch_prepare(xy, t->rec.as<uint32_t>(), (uint32_t)fp.records, errp, 0u, s0.stream, PT_FMT_XY);
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+  if (rc != MSM_OK) return rc;
+  t->alive = true;
+  std::lock_guard<std::mutex> lk(g_mu);
+  // msm_shutdown may have run since the records were made (it frees only registered tables)
+  if ((int)g_ctx.size() <= t->device || !g_ctx[t->device]) {
+    t->rec.release();
+    return MSM_ERR_INVALID_ARG;
+  }
+  const uintptr_t id = g_bases_next++;
+  g_fixed[id] = t;
+  *out = reinterpret_cast<msm_fixed*>(id);
+  return MSM_OK;
+}
+
+// The device buffer k_fixed_eval leaves its points in: whole blocks of 64.
+size_t fixed_proj_bytes(size_t m) { return (size_t)grid_for(m, FX_THREADS) * FX_THREADS * FX_PROJ_WORDS * 4; }
+
+// msm_fixed_mul*: Q_i = sum_j s_ij B_j for i < m, k_fixed_eval into the slot's fx_proj and
+// k_fixed_normalise out of it, on slot 0's stream.  With `created` the points become a new handle: the
+// x|y output goes through the preparation, as msm_bases_scale_create's does.  Else they are written to
+// `points` as wire records (host entries: through the slot's dx_pts).  Host scalars go up into the
+// slot's wire_pts after every one of them was checked.
+int fixed_mul(const msm_fixed* h, const uint32_t* scalars, size_t m, bool host, const msm_opts* opts,
+              hipStream_t user_stream, uint32_t* points, uint32_t levels, msm_bases** created) {
+  if (created) *created = nullptr;
+  if (!h || !bases_flags_ok(opts) || typed_flagged(opts)) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Fixed> t = find_fixed(h);
+  if (!t) return MSM_ERR_INVALID_ARG;
+  const uint32_t bits = opts && (opts->flags & MSM_FLAG_SCALAR_BITS) ? opts->scalar_bits : 256u;
+  if (bits < 1 || bits > 256) return MSM_ERR_INVALID_ARG;
+  const size_t sw = (bits + 31) / 32;
+  // a narrow call may be no wider than the table; the 8-word call is read at the table's width
+  if (opts && (opts->flags & MSM_FLAG_SCALAR_BITS) && bits > t->b) return MSM_ERR_INVALID_ARG;
+  const uint32_t width = std::min(bits, t->b);
+  if (opts && opts->device >= 0 && opts->device != t->device) return MSM_ERR_INVALID_ARG;
+  if (m >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  if (m && (!scalars || (!created && !points))) return MSM_ERR_INVALID_ARG;
+  const uint32_t wb = opts ? opts->window_bits : 0;
+  auto nb = std::make_shared<Bases>();
+  if (created)
+    if (int rc = bases_shape(nb.get(), m, levels, wb)) return rc;
+  const size_t ksw = t->k * sw;
+  if (!host && m) {  // alignment and overlap, from the pointer values
+    const uintptr_t sp = reinterpret_cast<uintptr_t>(scalars), pp = reinterpret_cast<uintptr_t>(points);
+    if (sp & (sw == 8 ? 15u : 3u)) return MSM_ERR_INVALID_ARG;
+    if (!created && ((pp & 15u) || (pp < sp + m * ksw * 4 && sp < pp + m * 128))) return MSM_ERR_INVALID_ARG;
+  }
+  if (host && width < 32 * sw) {  // every scalar, before anything is uploaded or enqueued
+    const size_t wi = sw - 1 - ((width - 1) >> 5);  // the word that holds bit width - 1
+    const uint32_t excess = (width & 31u) ? ~((1u << (width & 31u)) - 1u) : 0u;
+    uint32_t any = 0;
+    for (size_t i = 0; i < m * t->k; i++) {
+      for (size_t q = 0; q < wi; q++) any |= scalars[i * sw + q];
+      any |= scalars[i * sw + wi] & excess;
+    }
+    if (any) return MSM_ERR_INVALID_ARG;
+  }
+  msm_opts od{};
+  od.device = t->device;
+  int rc = on_device(&od, [&](DevCtx* c) -> int {
+    if (!t->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
+    nb->device = c->device;
+    if (!m) return MSM_OK;
+    if (created)
+      if (int prc = bases_plan_exists(c, *nb, wb)) return prc;
+    Slot& s0 = c->slot[0];
+    Buf errb;
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if (created && (r = nb->rec.ensure((size_t)nb->levels * m * PRE_WORDS * 4)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    auto done = [&](int code) {  // as create_bases'
+      drain_streams(c, 1, code);
+      if (errb.base) {
+        std::lock_guard<std::mutex> gl(g_guard_mu);
+        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+      }
+      errb.release();
+      if (code != MSM_OK) nb->rec.release();
+      return code;
+    };
+    uint32_t* errp = errb.as<uint32_t>();
+    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
+    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    const uint32_t* d_sc = scalars;
+    uint32_t* d_out = points;
+    if (host) {
+      if ((r = s0.ws.wire_pts.ensure(m * ksw * 4)) != MSM_OK) return done(r);
+      auto whole = [](size_t, size_t) { return MSM_OK; };
+      if ((r = upload(c, s0.ws.wire_pts.p, scalars, m * ksw * 4, m * ksw * 4, whole)) != MSM_OK) return done(r);
+      if (hipEventRecord(c->ev_chunk[0], c->copy_stream) != hipSuccess ||
+          hipStreamWaitEvent(s0.stream, c->ev_chunk[0], 0) != hipSuccess)
+        return done(MSM_ERR_HIP);
+      d_sc = s0.ws.wire_pts.as<uint32_t>();
+    }
+    if (host || created) {
+      if ((r = s0.ws.dx_pts.ensure(m * (created ? 64 : 128))) != MSM_OK) return done(r);
+      d_out = s0.ws.dx_pts.as<uint32_t>();
+    }
+    if ((r = s0.ws.fx_proj.ensure(fixed_proj_bytes(m))) != MSM_OK) return done(r);
+    uint32_t* proj = s0.ws.fx_proj.as<uint32_t>();
+    hipLaunchKernelGGL(k_fixed_eval, dim3(grid_for(m, FX_THREADS)), dim3(FX_THREADS), FX_THREADS * ksw * 4, s0.stream,
+                       t->rec.as<uint32_t>(), t->k, t->w, t->Wn, d_sc, (uint32_t)sw, width, proj, (uint32_t)m, errp);
+    hipLaunchKernelGGL(k_fixed_normalise, dim3(grid_for(m, FX_THREADS * FX_NORM_E)), dim3(FX_THREADS), 0, s0.stream,
+                       proj, d_out, (uint32_t)m, created ? 0u : 1u);
+    if (created) {
+      const uint32_t nt = prep_nt((size_t)nb->levels * m);
+      launch_prepare(d_out, nb->rec.as<uint32_t>(), (uint32_t)m, errp, nt, s0.stream, PT_FMT_XY);
+      launch_shift_levels(*nb, nt, s0.stream);
+    }
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if ((host && !created && hipMemcpyAsync(points, d_out, m * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
+        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
+        hipStreamSynchronize(s0.stream) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    if (e[0] & MSM_DEV_ERR_SCALAR_RANGE) return done(MSM_ERR_INVALID_ARG);
+    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
+    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
+    return done(MSM_OK);
+  });
+  if (rc != MSM_OK || !created) return rc;
+  return register_bases(nb, created);
+}

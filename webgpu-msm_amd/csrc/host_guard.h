@@ -17,7 +17,8 @@ struct GuardHit {
 };
 
 // Names by buffer index: a slot's workspace in Workspace::each_buf order, its h_out, the context's own
-// buffers in DevCtx::each_buf order, then a handle's records and its preparation's error word.
+// buffers in DevCtx::each_buf order, then a handle's records (a fixed-base table's go by the same name)
+// and its preparation's error word.
 const std::vector<const char*>& guard_names() {
   static const std::vector<const char*> names = [] {
     std::vector<const char*> v;

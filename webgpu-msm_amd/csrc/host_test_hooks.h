@@ -378,6 +378,37 @@ int msm_test_scale_digits(const uint32_t* scalar_be, uint32_t sw, uint32_t b, ui
   return MSM_OK;
 }
 
+// k_fixed_eval's own digit function on the host (msm_kernels.hip fixed_digit, fixed_windows): the
+// signed digits of one b-bit scalar of sw big-endian words for windows of w bits, least significant
+// first, their count, and the carry out of the last one (always 0).  digits holds 257 entries.
+int msm_test_fixed_digits(const uint32_t* scalar_be, uint32_t sw, uint32_t b, uint32_t w, int32_t* digits,
+                          uint32_t* count, uint32_t* carry_out) {
+  if (!scalar_be || !digits || !count || !carry_out || b < 1 || b > 256 || sw != (b + 31) / 32 || w < 2 || w > 16)
+    return MSM_ERR_INVALID_ARG;
+  *count = fixed_windows(b, w);
+  uint32_t carry = 0;
+  for (uint32_t j = 0; j < *count; j++) digits[j] = fixed_digit(scalar_be, sw, b, w, j, carry);
+  *carry_out = carry;
+  return MSM_OK;
+}
+
+// The shape msm_fixed_create gives a table of k bases (host_fixed.h fixed_plan): out = window width,
+// scalar width, windows per base, then records and bytes as two words each (low, high).  Its
+// refusals are the creation's.  Needs no device.
+int msm_test_fixed_plan(uint32_t k, uint32_t w, uint32_t b, uint32_t out[7]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  FixedPlan fp;
+  if (int rc = fixed_plan(k, w, b, &fp)) return rc;
+  out[0] = fp.w;
+  out[1] = fp.b;
+  out[2] = fp.Wn;
+  out[3] = (uint32_t)fp.records;
+  out[4] = (uint32_t)(fp.records >> 32);
+  out[5] = (uint32_t)fp.bytes;
+  out[6] = (uint32_t)(fp.bytes >> 32);
+  return MSM_OK;
+}
+
 // out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
 // msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
 int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {
@@ -632,6 +663,31 @@ int msm_test_bases_records(const msm_bases* h, uint32_t level, uint32_t* records
   });
 }
 
+// A fixed-base table's records as a handle of levels = 1 (a device-to-device copy the caller destroys):
+// msm_test_bases_records then reads the records, and scaling by ones the points they hold.
+int msm_test_fixed_bases(const msm_fixed* h, msm_bases** out) {
+  if (!h || !out) return MSM_ERR_INVALID_ARG;
+  *out = nullptr;
+  std::shared_ptr<Fixed> t = find_fixed(h);
+  if (!t) return MSM_ERR_INVALID_ARG;
+  auto nb = std::make_shared<Bases>();
+  if (int rc = bases_shape(nb.get(), t->records(), 1, 0)) return rc;
+  msm_opts o{};
+  o.device = t->device;
+  int rc = on_device(&o, [&](DevCtx* c) -> int {
+    if (!t->alive) return MSM_ERR_INVALID_ARG;
+    nb->device = c->device;
+    const size_t bytes = t->records() * PRE_WORDS * 4;
+    if (int r = nb->rec.ensure(bytes)) return r;
+    if (hipMemcpy(nb->rec.p, t->rec.p, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+      nb->rec.release();
+      return MSM_ERR_HIP;
+    }
+    return MSM_OK;
+  });
+  return rc != MSM_OK ? rc : register_bases(nb, out);
+}
+
 // k_split_scalars on n wire scalars: out = the k * n virtual scalars of S bits (8 words each,
 // element j n + i).
 int msm_test_split_scalars(const uint32_t* scalars, size_t n, uint32_t k, uint32_t S, uint32_t* out) {
@@ -876,6 +932,7 @@ int msm_test_guard(int on) {
     }
   }
   for (auto& kv : g_bases) kv.second->each_buf(seen);
+  for (auto& kv : g_fixed) kv.second->each_buf(seen);
   if (held) return MSM_ERR_INVALID_ARG;
   g_guard.store(on != 0);
   return prev ? 1 : 0;
@@ -934,6 +991,11 @@ int msm_test_guard_check(int device, GuardHit* report, size_t cap, size_t* count
       if (r == MSM_OK) r = guard_scan(b, guard_id(n), dev, -1, &hits);
     });
     for (auto& kv : g_bases)
+      if (kv.second->device == dev)
+        kv.second->each_buf([&](const char* n, Buf& b) {
+          if (r == MSM_OK) r = guard_scan(b, guard_id(n), dev, -1, &hits);
+        });
+    for (auto& kv : g_fixed)
       if (kv.second->device == dev)
         kv.second->each_buf([&](const char* n, Buf& b) {
           if (r == MSM_OK) r = guard_scan(b, guard_id(n), dev, -1, &hits);

@@ -56,6 +56,7 @@ namespace {
 #include "host_split.h"
 #include "host_multi.h"
 #include "host_bases.h"
+#include "host_fixed.h"
 }  // namespace
 #include "host_test_hooks.h"
 
@@ -78,6 +79,7 @@ void msm_shutdown(void) {
     c = nullptr;
   }
   g_bases.clear();  // every handle was freed with its device context above
+  g_fixed.clear();  // and every fixed-base table
   std::lock_guard<std::mutex> lk3(g_test_mu);
   g_test_pools.stop();
 }
@@ -379,6 +381,66 @@ int msm_bases_scale_create_device(const msm_bases* h, const msm_subset_t* sub, c
                                   const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out) {
   if (!out) return MSM_ERR_INVALID_ARG;
   return bases_scale(h, sub, d_scalars_be, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
+}
+
+int msm_fixed_create(const msm_bases* h, const msm_subset_t* sub, uint32_t window_bits, uint32_t scalar_bits,
+                     const msm_opts* opts, msm_fixed** out) {
+  return fixed_create(h, sub, window_bits, scalar_bits, opts, out);
+}
+
+int msm_fixed_destroy(msm_fixed* h) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_fixed.find(reinterpret_cast<uintptr_t>(h));
+  if (!h || it == g_fixed.end()) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Fixed> t = it->second;
+  g_fixed.erase(it);
+  // under the device context's lock, as msm_bases_destroy
+  DevCtx* c = t->device >= 0 && t->device < (int)g_ctx.size() ? g_ctx[t->device] : nullptr;
+  if (c) {
+    std::lock_guard<std::mutex> lk2(c->mu);
+    DeviceGuard g(c->device);
+    t->alive = false;
+    t->rec.release();
+  } else {
+    t->alive = false;
+  }
+  return MSM_OK;
+}
+
+int msm_fixed_info(const msm_fixed* h, msm_fixed_info_t* out) {
+  if (!h || !out) return MSM_ERR_INVALID_ARG;
+  std::shared_ptr<Fixed> t = find_fixed(h);
+  if (!t) return MSM_ERR_INVALID_ARG;
+  *out = msm_fixed_info_t{};
+  out->bases = t->k;
+  out->window_bits = t->w;
+  out->scalar_bits = t->b;
+  out->windows = t->Wn;
+  out->records = t->records();
+  out->bytes = (uint64_t)t->records() * PRE_WORDS * 4;
+  out->device = t->device;
+  return MSM_OK;
+}
+
+int msm_fixed_mul(const msm_fixed* h, const uint32_t* scalars_be, size_t m, const msm_opts* opts, uint32_t* points_be) {
+  return fixed_mul(h, scalars_be, m, true, opts, nullptr, points_be, 0, nullptr);
+}
+
+int msm_fixed_mul_device(const msm_fixed* h, const uint32_t* d_scalars_be, size_t m, const msm_opts* opts,
+                         void* hip_stream, uint32_t* d_points_be) {
+  return fixed_mul(h, d_scalars_be, m, false, opts, (hipStream_t)hip_stream, d_points_be, 0, nullptr);
+}
+
+int msm_fixed_mul_create(const msm_fixed* h, const uint32_t* scalars_be, size_t m, const msm_opts* opts,
+                         uint32_t levels, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return fixed_mul(h, scalars_be, m, true, opts, nullptr, nullptr, levels, out);
+}
+
+int msm_fixed_mul_create_device(const msm_fixed* h, const uint32_t* d_scalars_be, size_t m, const msm_opts* opts,
+                                uint32_t levels, void* hip_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return fixed_mul(h, d_scalars_be, m, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
 }
 
 int msm_combine_partials(const uint32_t* partials_xyzt_be, size_t count, uint32_t out_xy_be[16]) {

@@ -777,6 +777,287 @@ __device__ __forceinline__ pre load_pre_signed(const uint32_t* __restrict__ pts,
 }
 
 // ---------------------------------------------------------------------------------------------
+// fixed-base tables (msm_fixed_*): Q_i = sum_j s_ij B_j from windowed tables, no doubling
+// ---------------------------------------------------------------------------------------------
+// A table of k bases for windows of w bits and scalars below 2^b holds, for every base j and every
+// window win < Wn = fixed_windows(b, w), the 2^(w-1) multiples d 2^(w win) B_j, d = 1 .. 2^(w-1), as
+// ordinary prepared records: entry (j, win, d) is record (j Wn + win) 2^(w-1) + d - 1.  A scalar is
+// read as Wn signed digits, so an output is one mixed addition per window and base.
+// Both digit functions run on the host too (msm_test_fixed_digits), as scale_digit does.
+__host__ __device__ constexpr uint32_t fixed_windows(uint32_t b, uint32_t w) { return (b + w) / w; }  // ceil((b + 1) / w)
+// Bits [w win, w win + w) of a b-bit scalar held as sw = ceil(b / 32) big-endian words (w <= 16: at
+// most two words).  Bits at or above b read as zero, so a stray bit there (flagged by the kernel)
+// never reaches a digit, and windows past the scalar's words are zero.
+__host__ __device__ inline uint32_t fixed_window_bits(const uint32_t* s_be, uint32_t sw, uint32_t b, uint32_t w,
+                                                      uint32_t win) {
+  const uint32_t bit = win * w;
+  if (bit >= b) return 0u;
+  const uint32_t wi = bit >> 5, sh = bit & 31u;
+  uint32_t v = s_be[sw - 1 - wi] >> sh;
+  if (sh + w > 32u && wi + 1 < sw) v |= s_be[sw - 2 - wi] << (32u - sh);
+  const uint32_t keep = b - bit < w ? b - bit : w;
+  return v & ((1u << keep) - 1u);
+}
+// Signed digit `win` of the scalar, in [-(2^(w-1) - 1), 2^(w-1)], with sum_win d_win 2^(w win) the
+// scalar itself as an integer.  `carry` (0 before window 0) goes from each window to the next one up.
+// The top bit of window fixed_windows(b, w) - 1 lies at or above b, so that window's value is at most
+// 2^(w-1) - 1 + carry and nothing carries out of it.
+__host__ __device__ inline int32_t fixed_digit(const uint32_t* s_be, uint32_t sw, uint32_t b, uint32_t w, uint32_t win,
+                                               uint32_t& carry) {
+  const uint32_t v = fixed_window_bits(s_be, sw, b, w, win) + carry;  // 0 .. 2^w
+  carry = v > (1u << (w - 1)) ? 1u : 0u;
+  return (int32_t)v - (int32_t)(carry << w);
+}
+
+constexpr uint32_t FX_THREADS = 64;       // one wave per workgroup, as k_scale_points
+constexpr uint32_t FX_MAX_BASES = 8;
+constexpr uint32_t FX_PROJ_WORDS = 3 * NL;  // (X : Y : Z) of one evaluated point
+constexpr uint32_t FX_NO_ENTRY = 0xffffffffu;
+struct FixedBaseIdx {  // the table's bases as records of the source handle (kernel argument, by value)
+  uint32_t v[FX_MAX_BASES];
+};
+
+// The extended point (x : y : x y : 1) of a halved record, every coordinate an fe_mul output: what
+// k_shift_bases and k_scale_points rebuild, limb forms as there.
+__device__ __forceinline__ xyzt pt_from_record(const uint32_t (&rec)[32]) {
+  fe ymx, ypx;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    ymx.v[k] = rec[k];
+    ypx.v[k] = rec[PRE_HALF + k];
+  }
+  const fe one = fe_one();
+  const fe a = fe_mul(ymx, one);   // (y-x)/2, N_MUL
+  const fe xs = fe_sub(ypx, a);    // x + 8p: normalised, < 12p
+  const fe ys = fe_add_n(ypx, a);  // y: normalised, < 6p
+  xyzt p;
+  p.X = fe_mul(xs, one);
+  p.Y = fe_mul(ys, one);
+  p.T = fe_mul(xs, ys);
+  p.Z = one;
+  return p;
+}
+
+// Lane i's affine point (Montgomery x, y) as the canonical big-endian record x | y | t = x y | z = 1 in
+// the swizzled slots of `st`, and a staged block's first np points out to `out` (wire = 1: 128-byte
+// records; wire = 0: x | y, what k_prepare_points(PT_FMT_XY) reads) with coalesced 16-byte stores:
+// k_scale_points' output path.
+__device__ __forceinline__ void fx_stage_affine(uint4* st, uint32_t i, const fe& x, const fe& y) {
+  uint32_t xw[8], yw[8], tw[8];
+  fe_to_words_le(fe_to_std(x), xw);
+  fe_to_words_le(fe_to_std(y), yw);
+  fe_to_words_le(fe_to_std(fe_mul(x, y)), tw);
+  // big-endian word order: word 0 is the most significant 32 bits
+  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
+  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
+  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
+  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
+  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
+  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
+  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
+  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+}
+__device__ __forceinline__ void fx_flush_staged(const uint4* st, uint32_t* __restrict__ out, size_t p0, uint32_t np,
+                                                uint32_t wire) {
+  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
+  uint4* dst = reinterpret_cast<uint4*>(out) + (p0 << sh);
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * FX_THREADS + threadIdx.x;
+    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
+  }
+}
+
+// The table's points, one lane per entry e < total = k Wn 2^(w-1): e = (j Wn + win) 2^(w-1) + d - 1
+// gives d 2^(w win) B_j, B_j record bases.v[j] of `recs` (a handle's level 0; every index was checked
+// on the host).  The lane rebuilds the extended point, doubles it w win times, takes the multiple d
+// with a w-round double-and-add whose addition is selected (pt_sel, complete formulas: no branch for
+// the identity or the torsion points), and normalises with its own fe_inv -- the table is built once.
+// Output: x | y canonical, through LDS as k_scale_points writes them; k_prepare_points(PT_FMT_XY)
+// makes the records, so they are msm_bases_create's records of these points.
+extern "C" __global__ void __launch_bounds__(FX_THREADS, 2) k_fixed_build(const uint32_t* __restrict__ recs,
+                                                                        FixedBaseIdx bases, uint32_t w, uint32_t Wn,
+                                                                        uint32_t* __restrict__ out_xy,
+                                                                        uint32_t total) {
+  __shared__ uint4 st[FX_THREADS * 8];
+  const uint32_t p0 = blockIdx.x * FX_THREADS;
+  const uint32_t np = min(FX_THREADS, total - p0);
+  const uint32_t i = threadIdx.x;
+  // lanes past the last entry repeat it and write nothing
+  const uint32_t e = min(p0 + i, total - 1u);
+  const uint32_t d = (e & ((1u << (w - 1)) - 1u)) + 1u;
+  const uint32_t t = e >> (w - 1);
+  const uint32_t win = t % Wn, j = t / Wn;
+  uint32_t base = bases.v[0];
+#pragma unroll
+  for (uint32_t q = 1; q < FX_MAX_BASES; q++) base = j == q ? bases.v[q] : base;
+  uint32_t rec[32];
+  const uint4* in = reinterpret_cast<const uint4*>(recs) + (size_t)base * 8;
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) {
+    const uint4 v = in[q];
+    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+  }
+  xyzt p = pt_from_record(rec);
+#pragma unroll 1
+  for (uint32_t s = w * win; s > 0; s--) p = pt_dbl(p);
+  xyzt acc = pt_identity();
+#pragma unroll 1
+  for (uint32_t bit = w; bit-- > 0;) {
+    acc = pt_dbl(acc);
+    acc = pt_sel(((d >> bit) & 1u) != 0, acc, pt_add(acc, p));  // (c ? b : a)
+  }
+  const fe zi = fe_inv(acc.Z);
+  fx_stage_affine(st, i, fe_mul(acc.X, zi), fe_mul(acc.Y, zi));
+  __syncthreads();
+  fx_flush_staged(st, out_xy, p0, np, 0u);
+}
+
+// The evaluation: Q_i = sum_j s_ij B_j for i < m as (X : Y : Z).  One lane per output, one wave per
+// workgroup, four waves per SIMD (k_dense_units' budget and loop: the next entry is worked out beside
+// the current addition).
+//   scalars  [m][k][sw] big-endian words (the full integers: nothing is reduced mod r), the
+//            workgroup's 64 k sw words staged in LDS as k_scale_points stages them: 16-byte loads where
+//            the vector is 16-byte aligned, word by word where it is not.  A bit at or above b is
+//            masked (fixed_window_bits) and raises MSM_DEV_ERR_SCALAR_RANGE.
+//   digits   fixed_windows(b, w) signed digits per scalar, least significant window first (no
+//            doubling orders them); b is the call's width, at most the table's, so the windows read are
+//            the table's first ones.  Digit d != 0 of base j, window win, is record
+//            (j Wn + win) 2^(w-1) + |d| - 1, gathered with its sign (load_pre_signed) and added with
+//            pt_madd; digit 0 adds nothing and reads nothing.
+//   output   proj[(g FX_PROJ_WORDS + q) 64 + l] = limb q of X | Y | Z of point 64 g + l: every store and
+//            k_fixed_normalise's every load is one coalesced 256-byte row.  Lanes past m store the
+//            identity, so the buffer holds whole blocks of 64 and its reader needs no bound.
+extern "C" __global__ void __launch_bounds__(FX_THREADS, 4) k_fixed_eval(const uint32_t* __restrict__ table, uint32_t k,
+                                                                       uint32_t w, uint32_t Wn,
+                                                                       const uint32_t* __restrict__ scalars,
+                                                                       uint32_t sw, uint32_t b,
+                                                                       uint32_t* __restrict__ proj, uint32_t m,
+                                                                       uint32_t* __restrict__ err) {
+  extern __shared__ uint4 fx_sc4[];  // FX_THREADS k sw words
+  uint32_t* ssc = reinterpret_cast<uint32_t*>(fx_sc4);
+  const uint32_t p0 = blockIdx.x * FX_THREADS;
+  const uint32_t np = min(FX_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  const uint32_t ksw = k * sw;
+  {  // the workgroup's np k sw scalar words; p0 k sw 4 is a multiple of 256 bytes
+    const uint32_t* sp = scalars + (size_t)p0 * ksw;
+    const uint32_t total = np * ksw;
+    const uint32_t nv = (reinterpret_cast<uintptr_t>(scalars) & 15u) ? 0u : total >> 2;
+    for (uint32_t g = i; g < nv; g += FX_THREADS) fx_sc4[g] = reinterpret_cast<const uint4*>(sp)[g];
+    for (uint32_t g = (nv << 2) + i; g < total; g += FX_THREADS) ssc[g] = sp[g];
+  }
+  __syncthreads();
+  const uint32_t* my = ssc + (live ? i : 0u) * ksw;
+  const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
+  const uint32_t hw = sw - 1u - ((b - 1u) >> 5);  // the word that holds bit b - 1 (0 unless an 8-word call meets a narrower table)
+  const uint32_t wn = fixed_windows(b, w);
+  uint32_t j = 0, win = 0, carry = 0;
+  // the entry (record << 1 | sign) of the digit at (j, win), FX_NO_ENTRY for digit 0; steps (j, win) on
+  auto next_entry = [&]() -> uint32_t {
+    if (win == 0) {
+      uint32_t stray = my[j * sw + hw] & ~top_mask;
+      for (uint32_t q = 0; q < hw; q++) stray |= my[j * sw + q];
+      if (live && stray) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+    }
+    const int32_t d = fixed_digit(my + j * sw, sw, b, w, win, carry);
+    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+    const uint32_t ent = d && live ? ((((j * Wn + win) << (w - 1)) + mag - 1u) << 1) | (d < 0 ? 1u : 0u) : FX_NO_ENTRY;
+    if (++win == wn) {
+      win = 0;
+      carry = 0;
+      j++;
+    }
+    return ent;
+  };
+  xyzt acc = pt_identity();
+  const uint32_t steps = k * wn;
+  uint32_t ent = next_entry();
+#pragma unroll 1
+  for (uint32_t s = 1; s <= steps; s++) {
+    const uint32_t cur = ent;
+    if (s < steps) ent = next_entry();  // the next digit beside this one's add
+    if (cur != FX_NO_ENTRY) acc = pt_madd(acc, load_pre_signed(table, cur));
+  }
+  uint32_t* dst = proj + (size_t)blockIdx.x * FX_PROJ_WORDS * FX_THREADS + i;
+#pragma unroll
+  for (int q = 0; q < NL; q++) {
+    dst[q * FX_THREADS] = acc.X.v[q];
+    dst[(NL + q) * FX_THREADS] = acc.Y.v[q];
+    dst[(2 * NL + q) * FX_THREADS] = acc.Z.v[q];
+  }
+}
+
+// The affine output of k_fixed_eval's points with one inversion per E of them (Montgomery's trick
+// down a lane, not across the wave: lanes of one SIMD invert in the same issue slots whether one or
+// all of them do).  A workgroup takes E consecutive blocks of 64 points, lane l point l of each: the
+// prefix products Z_0 .. Z_0 ... Z_(E-1) stay in registers, the last one is inverted, and the walk
+// back gives 1 / Z_e = inv prefix_(e-1), inv <- inv Z_e.  3 (E - 1) / E multiplies per point for the
+// trick, 3 for x, y and t = x y, 3 for the canonical forms, and fe_inv's ~380 / E: ~56 at E = 8.
+// Blocks past the last one are skipped (wave-uniform); the lanes past m in the last block hold the
+// identity (Z = 1) and write nothing.  Output as k_scale_points': wire = 1 canonical wire records,
+// the identity (0, 1, 0, 1); wire = 0 x | y.  Results are specified for on-curve bases (no Z is 0).
+#ifndef MSM_FX_NORM_E
+#define MSM_FX_NORM_E 8
+#endif
+constexpr uint32_t FX_NORM_E = MSM_FX_NORM_E;
+__device__ __forceinline__ fe fx_load_coord(const uint32_t* __restrict__ blk, uint32_t c) {
+  fe r;
+#pragma unroll
+  for (int q = 0; q < NL; q++) r.v[q] = blk[(c * NL + q) * FX_THREADS];
+  return r;
+}
+// The two walks over a workgroup's E blocks, unrolled by recursion over the block's number so that the
+// prefix products stay in registers (the unroller gives up on loops of this size).  Forward: the prefix
+// product through block E0; blocks past the last one (wave-uniform) repeat the one before.
+template <uint32_t E0>
+__device__ __forceinline__ void fx_norm_prefix(fe (&prefix)[FX_NORM_E], const uint32_t* __restrict__ mine, uint32_t g0,
+                                               uint32_t nblk) {
+  if constexpr (E0 < FX_NORM_E) {
+    prefix[E0] = prefix[E0 - 1];
+    if (g0 + E0 < nblk)
+      prefix[E0] = fe_mul(prefix[E0 - 1], fx_load_coord(mine + (size_t)E0 * FX_PROJ_WORDS * FX_THREADS, 2));
+    fx_norm_prefix<E0 + 1>(prefix, mine, g0, nblk);
+  }
+}
+// Backward from block E0: 1 / Z of the block's point out of `inv` = 1 / (Z_0 ... Z_E0), the affine
+// point staged and stored, and `inv` handed down without Z_E0.
+template <uint32_t E0>
+__device__ __forceinline__ void fx_norm_emit(const fe (&prefix)[FX_NORM_E], fe inv, const uint32_t* __restrict__ mine,
+                                             uint32_t g0, uint32_t nblk, uint4* st, uint32_t* __restrict__ out,
+                                             uint32_t m, uint32_t wire) {
+  if (g0 + E0 < nblk) {  // wave-uniform
+    const uint32_t* blk = mine + (size_t)E0 * FX_PROJ_WORDS * FX_THREADS;
+    fe zi = inv;
+    if constexpr (E0 > 0) {
+      zi = fe_mul(inv, prefix[E0 - 1]);
+      inv = fe_mul(inv, fx_load_coord(blk, 2));
+    }
+    const fe x = fe_mul(fx_load_coord(blk, 0), zi);
+    const fe y = fe_mul(fx_load_coord(blk, 1), zi);
+    __syncthreads();  // the previous block's stores have read st
+    fx_stage_affine(st, threadIdx.x, x, y);
+    __syncthreads();
+    const uint32_t pb = (g0 + E0) * FX_THREADS;
+    fx_flush_staged(st, out, pb, min(FX_THREADS, m - pb), wire);
+  }
+  if constexpr (E0 > 0) fx_norm_emit<E0 - 1>(prefix, inv, mine, g0, nblk, st, out, m, wire);
+}
+extern "C" __global__ void __launch_bounds__(FX_THREADS) k_fixed_normalise(const uint32_t* __restrict__ proj,
+                                                                          uint32_t* __restrict__ out, uint32_t m,
+                                                                          uint32_t wire) {
+  __shared__ uint4 st[FX_THREADS * 8];
+  const uint32_t nblk = (m + FX_THREADS - 1) / FX_THREADS;
+  const uint32_t g0 = blockIdx.x * FX_NORM_E;
+  const uint32_t* mine = proj + (size_t)g0 * FX_PROJ_WORDS * FX_THREADS + threadIdx.x;
+  fe prefix[FX_NORM_E];
+  prefix[0] = fx_load_coord(mine, 2);
+  fx_norm_prefix<1>(prefix, mine, g0, nblk);
+  fx_norm_emit<FX_NORM_E - 1>(prefix, fe_inv(prefix[FX_NORM_E - 1]), mine, g0, nblk, st, out, m, wire);
+}
+
+// ---------------------------------------------------------------------------------------------
 // scalar recoding
 // ---------------------------------------------------------------------------------------------
 // Signed recoding of one scalar (little-endian words, consumed in place).  Calls f(window,

@@ -34,7 +34,13 @@
 //   scaleBases(id, scalars: Uint32Array(8m), first?, indices?, scalarBits?, asBases?, levels?, windowSize?)
 //       -> Uint32Array(32m), the wire points s_i * P_i, or with asBases the object of a new handle
 //   releaseBases(id) -> number (0 ok, -1 for a handle already released)
-//   Handles left open are freed by the cleanup hook's msm_shutdown.
+// Fixed-base tables (msm_fixed_*; not enumerable either):
+//   prepareFixedBase(id, first?, count?, indices?, windowBits?, scalarBits?)
+//       -> { id, bases, windowBits, scalarBits, windows, records, bytes }
+//   fixedBaseMul(id, scalars: Uint32Array(8 m bases), scalarBits?, asBases?, levels?, windowSize?)
+//       -> Uint32Array(32m), the wire points sum_j s_ij * B_j, or with asBases the object of a new handle
+//   releaseFixedBase(id) -> number (0 ok, -1 for a table already released)
+//   Handles and tables left open are freed by the cleanup hook's msm_shutdown.
 #include <node_api.h>
 
 #include <algorithm>
@@ -876,6 +882,130 @@ napi_value ReleaseBases(napi_env env, napi_callback_info info) {
   return r;
 }
 
+// ---- fixed-base tables (msm_fixed_*) --------------------------------------------------------------
+// prepareFixedBase(id, first?, count?, indices?, windowBits?, scalarBits?): the table of k <= 8 bases of
+// handle `id` -- all of them, the range [first, first + count), or bases indices[j] -- as an object of
+// its token and what msm_fixed_info says.  Synchronous, as prepareBases is.
+napi_value PrepareFixedBase(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  const bool has_range = given(1) || given(2), has_idx = given(3);
+  const uint32_t* ix = nullptr;
+  size_t ilen = 0;
+  double first = 0, count = 0;
+  auto whole = [](double v) { return v >= 0 && v <= 9007199254740992.0 && v == (double)(uint64_t)v; };
+  if (!h || (given(1) && (napi_get_value_double(env, argv[1], &first) != napi_ok || !whole(first))) ||
+      (given(2) && (napi_get_value_double(env, argv[2], &count) != napi_ok || !whole(count))) ||
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen))) {
+    napi_throw_type_error(env, nullptr,
+                          "prepareFixedBase(id: number, first?: number, count?: number, indices?: Uint32Array, "
+                          "windowBits?: number, scalarBits?: number)");
+    return nullptr;
+  }
+  msm_subset_t sub;
+  sub.first = (uint64_t)first;
+  sub.m = has_idx ? ilen : (uint64_t)count;
+  sub.indices = has_idx ? &ix : nullptr;
+  if (has_range && !given(2)) {  // from `first` to the handle's end
+    msm_bases_info_t inf;
+    int rc = msm_bases_info(h, &inf);
+    if (rc != MSM_OK) return throw_rc(env, rc);
+    sub.m = inf.n > sub.first ? inf.n - sub.first : 0;
+  }
+  msm_fixed* t = nullptr;
+  int rc = msm_fixed_create(h, has_range || has_idx ? &sub : nullptr, given(4) ? get_window(env, argv[4]) : 0,
+                            given(5) ? get_window(env, argv[5]) : 0, nullptr, &t);
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  msm_fixed_info_t inf;
+  if ((rc = msm_fixed_info(t, &inf)) != MSM_OK) return throw_rc(env, rc);
+  napi_value obj, v;
+  NAPI_OK(napi_create_object(env, &obj));
+  const struct {
+    const char* name;
+    double val;
+  } fields[] = {{"id", (double)reinterpret_cast<uintptr_t>(t)}, {"bases", (double)inf.bases},
+                {"windowBits", (double)inf.window_bits}, {"scalarBits", (double)inf.scalar_bits},
+                {"windows", (double)inf.windows}, {"records", (double)inf.records}, {"bytes", (double)inf.bytes}};
+  for (const auto& f : fields) {
+    NAPI_OK(napi_create_double(env, f.val, &v));
+    NAPI_OK(napi_set_named_property(env, obj, f.name, v));
+  }
+  return obj;
+}
+
+// fixedBaseMul(id, scalars, scalarBits?, asBases?, levels?, windowSize?): sum_j s_ij * B_j for the m
+// rows of one scalar per base of the table (msm_fixed_info) in the array (msm_fixed_mul; synchronous): a Uint32Array of m x 32 wire
+// words, or with `asBases` the object of a new handle (msm_fixed_mul_create).
+napi_value FixedBaseMul(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  const msm_fixed* t = argc > 0 ? reinterpret_cast<const msm_fixed*>(get_handle(env, argv[0])) : nullptr;
+  const bool has_bits = given(2);
+  const uint32_t* sc;
+  size_t slen;
+  double bits = 0;
+  bool as_bases = false;
+  if (argc < 2 || !t || !get_u32_array(env, argv[1], &sc, &slen) ||
+      (has_bits && (napi_get_value_double(env, argv[2], &bits) != napi_ok || bits != (double)(uint32_t)bits)) ||
+      (given(3) && napi_get_value_bool(env, argv[3], &as_bases) != napi_ok)) {
+    napi_throw_type_error(env, nullptr,
+                          "fixedBaseMul(id: number, scalars: Uint32Array, scalarBits?: number, asBases?: boolean, "
+                          "levels?: number, windowSize?: number)");
+    return nullptr;
+  }
+  if (has_bits && (bits < 1 || bits > 256)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  // the row length is the table's own base count: the library reads m * k * sw words
+  msm_fixed_info_t inf;
+  if (int irc = msm_fixed_info(t, &inf)) return throw_rc(env, irc);  // released, or never a table
+  const size_t sw = has_bits ? ((size_t)bits + 31) / 32 : 8;  // words per scalar
+  const size_t row = sw * inf.bases;
+  if (slen % row) {
+    napi_throw_range_error(env, nullptr, "the scalars are no whole rows of one per base");
+    return nullptr;
+  }
+  const size_t m = slen / row;
+  msm_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = -1;
+  o.window_bits = given(5) ? get_window(env, argv[5]) : 0;
+  if (has_bits) {
+    o.flags |= MSM_FLAG_SCALAR_BITS;
+    o.scalar_bits = (uint32_t)bits;
+  }
+  if (as_bases) {
+    msm_bases* nh = nullptr;
+    int rc = msm_fixed_mul_create(t, sc, m, &o, given(4) ? get_window(env, argv[4]) : 0, &nh);
+    if (rc != MSM_OK) return throw_rc(env, rc);
+    return bases_object(env, nh);
+  }
+  std::vector<uint32_t> out(m * 32 + 1);
+  int rc = msm_fixed_mul(t, sc, m, &o, out.data());
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  return make_u32(env, out.data(), m * 32);
+}
+
+napi_value ReleaseFixedBase(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  napi_value r;
+  NAPI_OK(napi_create_int32(
+      env, h ? msm_fixed_destroy(reinterpret_cast<msm_fixed*>(const_cast<msm_bases*>(h))) : MSM_ERR_INVALID_ARG, &r));
+  return r;
+}
+
 napi_value BestWindowSize(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1];
@@ -950,6 +1080,9 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"releaseBases", nullptr, ReleaseBases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decompressPoints", nullptr, DecompressPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"scaleBases", nullptr, ScaleBases, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"prepareFixedBase", nullptr, PrepareFixedBase, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"fixedBaseMul", nullptr, FixedBaseMul, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"releaseFixedBase", nullptr, ReleaseFixedBase, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -72,6 +72,28 @@ export declare function scale_bases_prepared(
   scalars: bigint[] | Uint32Array[] | Uint32Array,
   options: ScaleOptions & { asBases: true }
 ): BasesHandle;
+// Fixed-base tables: the windowed table of k <= 8 of a handle's bases (all, the range from `first` of
+// `count`, or bases indices[j]), then sum_j s_ij * B_j for m rows of k scalars (row after row): m x 32
+// wire words, or with asBases a new handle of those points.  Synchronous.
+export type FixedBaseTable = {
+  id: number; bases: number; windowBits: number; scalarBits: number; windows: number; records: number; bytes: number;
+};
+export declare function prepare_fixed_base(
+  handle: BasesHandle,
+  options?: { first?: number; count?: number; indices?: Uint32Array; windowBits?: number; scalarBits?: number }
+): FixedBaseTable;
+export type FixedMulOptions = { scalarBits?: number; levels?: number; windowSize?: number };
+export declare function fixed_base_mul(
+  table: FixedBaseTable,
+  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  options?: FixedMulOptions & { asBases?: false }
+): Uint32Array;
+export declare function fixed_base_mul(
+  table: FixedBaseTable,
+  scalars: bigint[] | Uint32Array[] | Uint32Array,
+  options: FixedMulOptions & { asBases: true }
+): BasesHandle;
+export declare function release_fixed_base(table: FixedBaseTable): number;
 export declare function release_bases(handle: BasesHandle): number;
 
 export declare function getBestWindowSize(n: number): number;

@@ -334,6 +334,39 @@ export function scale_bases_prepared(handle, scalars, options) {
                           !!asBases, levels ? levels | 0 : 0, windowFrom(options));
 }
 
+// Fixed-base tables (msm_fixed_*): prepare_fixed_base builds the windowed table of k <= 8 of a handle's
+// bases -- all of them, the range { first, count } or the bases { indices } (repeats allowed) -- with
+// { windowBits } (2..16, default the library's 12) and { scalarBits } (the widest scalar served, default
+// 256).  fixed_base_mul then computes sum_j s_ij * B_j for m rows of k scalars, row after row in
+// `scalars` (bigint[] or Uint32Array as in scale_bases_prepared, narrow with { scalarBits } no wider
+// than the table's; the integer is not reduced mod r): a flat Uint32Array of m x 32 wire words, or
+// with { asBases: true } a new handle ({ levels, windowSize } as in prepare_bases).  The table keeps
+// its own records, so the handle may be released at once; release_fixed_base frees the table.
+// Synchronous, as prepare_bases is.
+export function prepare_fixed_base(handle, options) {
+  if (!handle || typeof handle.id !== "number") throw new TypeError("prepare_fixed_base(handle): not a handle");
+  const { first, count, indices, windowBits, scalarBits } = options || {};
+  if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("options.indices: a Uint32Array");
+  for (const [name, v] of [["first", first], ["count", count], ["windowBits", windowBits], ["scalarBits", scalarBits]])
+    if (v !== undefined && !(Number.isSafeInteger(v) && v >= 0)) throw new RangeError(`options.${name}: a non-negative integer`);
+  return addon.prepareFixedBase(handle.id, first, count, indices, windowBits, scalarBits);
+}
+
+export function fixed_base_mul(table, scalars, options) {
+  if (!table || typeof table.id !== "number")
+    throw new TypeError("fixed_base_mul(table, scalars): not a table");
+  const { scalarBits, asBases, levels } = options || {};
+  if (scalarBits !== undefined && !(Number.isInteger(scalarBits) && scalarBits >= 1 && scalarBits <= 256))
+    throw new RangeError("options.scalarBits: an integer in 1..256");
+  return addon.fixedBaseMul(table.id, scalarWords(scalars, scalarBits), scalarBits, !!asBases,
+                            levels ? levels | 0 : 0, windowFrom(options));
+}
+
+export function release_fixed_base(table) {
+  if (!table || typeof table.id !== "number") throw new TypeError("release_fixed_base(table): not a table");
+  return addon.releaseFixedBase(table.id);
+}
+
 export function release_bases(handle) {
   if (!handle || typeof handle.id !== "number") throw new TypeError("release_bases(handle): not a handle");
   return addon.releaseBases(handle.id);

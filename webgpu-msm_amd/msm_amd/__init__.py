@@ -79,6 +79,13 @@ class BasesInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
 
 
+class FixedInfo(ctypes.Structure):
+    """include/msm.h msm_fixed_info_t."""
+    _fields_ = [("bases", ctypes.c_uint32), ("window_bits", ctypes.c_uint32), ("scalar_bits", ctypes.c_uint32),
+                ("windows", ctypes.c_uint32), ("records", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("device", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
 class GuardHit(ctypes.Structure):
     """csrc/host_guard.h GuardHit: one finding of msm_test_guard_check."""
     _fields_ = [("buffer", ctypes.c_uint32), ("device", ctypes.c_int32), ("slot", ctypes.c_int32),
@@ -199,6 +206,18 @@ def load() -> ctypes.CDLL:
         "msm_bases_scale_create_device": ([vp, ctypes.POINTER(Subset), vp, optp, ctypes.c_uint32, vp,
                                            ctypes.POINTER(vp)], ctypes.c_int),
         "msm_test_scale_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
+        "msm_fixed_create": ([vp, ctypes.POINTER(Subset), ctypes.c_uint32, ctypes.c_uint32, optp, ctypes.POINTER(vp)],
+                             ctypes.c_int),
+        "msm_fixed_destroy": ([vp], ctypes.c_int),
+        "msm_fixed_info": ([vp, ctypes.POINTER(FixedInfo)], ctypes.c_int),
+        "msm_fixed_mul": ([vp, vp, sz, optp, vp], ctypes.c_int),
+        "msm_fixed_mul_device": ([vp, vp, sz, optp, vp, vp], ctypes.c_int),
+        "msm_fixed_mul_create": ([vp, vp, sz, optp, ctypes.c_uint32, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_fixed_mul_create_device": ([vp, vp, sz, optp, ctypes.c_uint32, vp, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_test_fixed_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.c_int32), u32p, u32p], ctypes.c_int),
+        "msm_test_fixed_plan": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_fixed_bases": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
         "msm_test_subset_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -1158,6 +1177,25 @@ class Bases:
             m = len(indices) if indices is not None else self.info["n"] - int(first)
         return self.scale(np.ones((max(int(m), 0), 1), dtype=np.uint32), first, indices, scalar_bits=1)
 
+    def fixed_table(self, indices=None, first: Optional[int] = None, count: Optional[int] = None,
+                    window_bits: int = 0, scalar_bits: int = 0) -> "FixedBase":
+        """A fixed-base table (include/msm.h msm_fixed_create) of k <= 8 of the handle's bases: all of
+        them, the range [first, first + count), or `indices` (repeats allowed).  window_bits 0 is the
+        library's choice, scalar_bits 0 means 256.  The table keeps its own records: the handle may be
+        closed at once."""
+        if indices is not None:
+            keep = np.ascontiguousarray(np.asarray(indices).astype(np.uint32, copy=False).reshape(-1))
+            sub = ctypes.byref(self._subset(0, keep.shape[0], [keep.ctypes.data]))
+        elif first is not None or count is not None:
+            f = int(first or 0)
+            sub = ctypes.byref(self._subset(f, self.info["n"] - f if count is None else int(count), None))
+        else:
+            sub = None
+        h = ctypes.c_void_p()
+        _check(load().msm_fixed_create(self._h or None, sub, int(window_bits), int(scalar_bits), None, ctypes.byref(h)),
+               "msm_fixed_create")
+        return FixedBase(h.value or 0)
+
     def close(self) -> None:
         """Free the records.  Closing twice is harmless."""
         h, self._h = self._h, 0
@@ -1165,6 +1203,108 @@ class Bases:
             _lib.msm_bases_destroy(h)  # -1 when msm_shutdown already freed it
 
     def __enter__(self) -> "Bases":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter teardown: the module's globals may be gone
+            pass
+
+
+class FixedBase:
+    """A fixed-base table of k bases B_0 .. B_(k-1) (include/msm.h msm_fixed_*), made by
+    Bases.fixed_table: every call computes Q_i = sum_j s_ij * B_j for m rows of k scalars, one mixed
+    addition per window and base.
+
+        with bases.fixed_table(indices=[0]) as g:
+            keys = g.mul(secrets)                      # wire records [m, 32]
+
+    Scalars are wire words [m, k, 8] (or [m * k, 8], row i's k scalars together), or narrow ones with
+    `scalar_bits` no wider than the table's; Python ints are taken in the same order.  The integer is
+    not reduced mod r.  Use after close() -- or after the library shut down -- raises MsmError(-1)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def info(self) -> dict:
+        inf = FixedInfo()
+        _check(load().msm_fixed_info(self._h or None, ctypes.byref(inf)), "msm_fixed_info")
+        return {name: int(getattr(inf, name)) for name, _ in FixedInfo._fields_ if name != "reserved"}
+
+    def _rows(self, scalars, scalar_bits: Optional[int]) -> Tuple[np.ndarray, int]:
+        """Host scalars as [m * k, sw] words, and m."""
+        if not isinstance(scalars, np.ndarray):
+            scalars = list(scalars)
+            if scalars and isinstance(scalars[0], (list, tuple)):
+                scalars = [s for row in scalars for s in row]
+        sc = np.ascontiguousarray(scalars_to_wire(scalars, scalar_bits))
+        k = self.info["bases"]
+        if sc.shape[0] % k:
+            raise ValueError(f"{sc.shape[0]} scalars are no whole rows of {k}")
+        return sc, sc.shape[0] // k
+
+    def mul(self, scalars, scalar_bits: Optional[int] = None) -> np.ndarray:
+        """sum_j s_ij * B_j for host scalars: wire records [m, 32] (x | y | t | z = 1, canonical)."""
+        sc, m = self._rows(scalars, scalar_bits)
+        out = np.zeros((m, 32), dtype=np.uint32)
+        _check(load().msm_fixed_mul(self._h or None, _ptr(sc), m, _opts(None, scalar_bits=scalar_bits), _ptr(out)),
+               "msm_fixed_mul")
+        return out
+
+    def mul_device(self, d_scalars, d_out, m: Optional[int] = None, scalar_bits: Optional[int] = None,
+                   stream: int = 0) -> None:
+        """The same between device buffers (torch tensors, or raw pointers with `m`): d_scalars holds
+        m rows of k scalars, d_out takes m x 32 words (16-byte aligned, not overlapping the scalars);
+        complete on return."""
+        m = len(d_out) if m is None else int(m)
+        _check(load().msm_fixed_mul_device(self._h or None, _dev_ptr(d_scalars), m,
+                                           _opts(None, scalar_bits=scalar_bits), _stream(stream, d_scalars, d_out),
+                                           _dev_ptr(d_out)), "msm_fixed_mul_device")
+
+    def mul_bases(self, scalars, scalar_bits: Optional[int] = None, levels: int = 0,
+                  window_size: Optional[int] = None) -> Bases:
+        """A new handle of the m points, which never leave the device: the handle
+        Bases.from_wire(self.mul(...)) makes."""
+        sc, m = self._rows(scalars, scalar_bits)
+        h = ctypes.c_void_p()
+        _check(load().msm_fixed_mul_create(self._h or None, _ptr(sc), m, _opts(window_size, scalar_bits=scalar_bits),
+                                           int(levels), ctypes.byref(h)), "msm_fixed_mul_create")
+        return Bases(h.value or 0)
+
+    def mul_bases_device(self, d_scalars, m: int, scalar_bits: Optional[int] = None, levels: int = 0,
+                         window_size: Optional[int] = None, stream: int = 0) -> Bases:
+        """The same with device-resident scalars (m rows of k)."""
+        h = ctypes.c_void_p()
+        _check(load().msm_fixed_mul_create_device(self._h or None, _dev_ptr(d_scalars), int(m),
+                                                  _opts(window_size, scalar_bits=scalar_bits), int(levels),
+                                                  _stream(stream, d_scalars), ctypes.byref(h)),
+               "msm_fixed_mul_create_device")
+        return Bases(h.value or 0)
+
+    def _records_handle(self) -> Bases:
+        """The table's records copied into a handle of their own (msm_test_fixed_bases)."""
+        h = ctypes.c_void_p()
+        _check(load().msm_test_fixed_bases(self._h or None, ctypes.byref(h)), "msm_test_fixed_bases")
+        return Bases(h.value or 0)
+
+    def points(self) -> np.ndarray:
+        """The table's points as wire records [records, 32]: entry (j, win, d), d = 1 .. 2^(w-1), at
+        (j * windows + win) * 2^(w-1) + d - 1 holds d * 2^(w * win) * B_j."""
+        with self._records_handle() as b:
+            return b.points()
+
+    def close(self) -> None:
+        """Free the table.  Closing twice is harmless."""
+        h, self._h = self._h, 0
+        if h and _lib is not None:
+            _lib.msm_fixed_destroy(h)  # -1 when msm_shutdown already freed it
+
+    def __enter__(self) -> "FixedBase":
         return self
 
     def __exit__(self, *exc) -> None:
@@ -1390,6 +1530,28 @@ def _test_scale_digits(value: int, scalar_bits: int) -> list:
                                         digits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(count)),
            "msm_test_scale_digits")
     return [int(d) for d in digits[:count.value]]
+
+
+def _test_fixed_digits(value: int, scalar_bits: int, window_bits: int) -> Tuple[list, int]:
+    """The fixed-base evaluation's signed digits of one `scalar_bits`-bit value for windows of
+    `window_bits` bits, least significant first, by the kernel's own digit function run on the host
+    (msm_test_fixed_digits), and the carry out of the top window.  Needs no device."""
+    sc = scalars_to_wire([int(value)], scalar_bits)
+    digits = np.zeros(257, dtype=np.int32)
+    count, carry = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().msm_test_fixed_digits(_ptr(sc), sc.shape[1], int(scalar_bits), int(window_bits),
+                                        digits.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(count),
+                                        ctypes.byref(carry)), "msm_test_fixed_digits")
+    return [int(d) for d in digits[:count.value]], int(carry.value)
+
+
+def _test_fixed_plan(bases: int, window_bits: int = 0, scalar_bits: int = 0) -> dict:
+    """The shape msm_fixed_create gives a table (msm_test_fixed_plan): window and scalar widths, windows
+    per base, records and bytes.  The creation's refusals apply (MsmError -1).  Needs no device."""
+    o, op_ = _out(7)
+    _check(load().msm_test_fixed_plan(int(bases), int(window_bits), int(scalar_bits), op_), "msm_test_fixed_plan")
+    return {"window_bits": int(o[0]), "scalar_bits": int(o[1]), "windows": int(o[2]),
+            "records": int(o[3]) | int(o[4]) << 32, "bytes": int(o[5]) | int(o[6]) << 32}
 
 
 def _test_limb_op(name: str, a, b=None, neg=None) -> np.ndarray:
