@@ -435,8 +435,11 @@ def prepare_record(inp, fmt, masks=DEFAULT_MASKS):
         zh = fe_mul(zi, HALF29, masks)
         x = fe_mul(fe_to_mont(fe_from_words_le(xw), masks), zh, masks)
         y = fe_mul(fe_to_mont(fe_from_words_le(yw), masks), zh, masks)
-    kt = fe_mul_d_limbs(fe_mul(fe_add(x, x), fe_add(y, y), masks))
-    ymx, ypx = fe_sub(y, x), fe_add_n(y, x)
+    return halved_record(x, y, masks), err
+
+
+def pack_record(ymx, ypx, kt):
+    """The 32 words of a record (msm_dev.h PRE_WORDS) from its three limb vectors."""
     rec = [0] * PRE_WORDS
     rec[0:NL] = ymx
     rec[PRE_HALF:PRE_HALF + NL] = ypx
@@ -444,7 +447,14 @@ def prepare_record(inp, fmt, masks=DEFAULT_MASKS):
     rec[NL] = rec[PRE_HALF + NL] = kt[NL - 1]
     rec[NL + 1] = ypx[NL - 1]
     rec[PRE_HALF + NL + 1] = ymx[NL - 1]
-    return rec, err
+    return rec
+
+
+def halved_record(x, y, masks=DEFAULT_MASKS):
+    """The record k_prepare_points and k_shift_bases write for the halved affine (x / 2, y / 2) they
+    hold as fe_mul outputs: (y-x)/2 = fe_sub, (y+x)/2 = fe_add_n, d t = fe_mul_d(2x 2y)."""
+    kt = fe_mul_d_limbs(fe_mul(fe_add(x, x), fe_add(y, y), masks))
+    return pack_record(fe_sub(y, x), fe_add_n(y, x), kt)
 
 
 def load_pre_signed(records, ent):
@@ -456,3 +466,119 @@ def load_pre_signed(records, ent):
     bv = list(h1[:NL - 1]) + [h0[NL + 1]]
     kv = list(rec[PRE_KT:PRE_KT + NL - 1]) + [h0[NL]]
     return (av, bv, kt_neg_if(kv, sgn != 0))
+
+
+# ---- the per-lane point kernels (msm_kernels.hip k_shift_bases, k_decompress_x, k_scale_points, ----
+# ---- k_fixed_build, k_fixed_eval) -------------------------------------------------------------------
+def fe_sqr(a, masks=DEFAULT_MASKS):
+    return fe_mul(a, a, masks)
+
+
+ONE_P29 = fe_add_n(ONE29, P29)  # fe_sqrt_ts' one_p: the other limb pattern of 1 below 2p
+
+
+def fe_eq_limbs(a, b):
+    return all(x == y for x, y in zip(a, b))
+
+
+def fe_mul_out_is_one(t):
+    return fe_eq_limbs(t, ONE29) or fe_eq_limbs(t, ONE_P29)
+
+
+def fe_std_neg(a):
+    """p - a on canonical standard-form limbs (0 stays 0): int32 differences with a running borrow."""
+    r, borrow, any_ = [0] * NL, 0, 0
+    for i in range(NL):
+        assert 0 <= a[i] < 1 << 31, "fe_std_neg: limb leaves int32"
+        t = P29[i] - a[i] + borrow
+        borrow = -1 if t < 0 else 0
+        r[i] = t & MASK
+        any_ |= a[i]
+    assert borrow == 0 or not any_, "fe_std_neg: a > p"
+    return r if any_ else list(a)
+
+
+TWO_ADICITY = 47
+Q_ODD = (P - 1) >> TWO_ADICITY
+SQRT_EXP, SQRT_EXP_BITS = (Q_ODD - 1) // 2, 7 * 32  # dx_exp_word: DX_EXP_WORDS words, every bit walked
+OMEGA = pow(11, Q_ODD, P)                            # 11 is the least non-residue
+OMEGA29 = limbs_of(OMEGA * R % P)                    # dx_omega_limb
+R_ORDER = 2111115437357092606062206234695386632838870926408408195193685246394721360383
+ORDER_BITS = 251
+
+
+def fe_sqrt_ts(u, masks=DEFAULT_MASKS, trace=None):
+    """msm_kernels.hip fe_sqrt_ts on limbs; `trace` collects every round's i."""
+    w = list(ONE29)
+    for bit in range(SQRT_EXP_BITS - 1, -1, -1):
+        w = fe_sqr(w, masks)
+        if (SQRT_EXP >> bit) & 1:
+            w = fe_mul(w, u, masks)
+    r = fe_mul(u, w, masks)
+    t = fe_mul(r, w, masks)
+    c = list(OMEGA29)
+    m = TWO_ADICITY
+    while not fe_mul_out_is_one(t):
+        i, t2 = 0, t
+        while True:
+            t2 = fe_sqr(t2, masks)
+            i += 1
+            if not (i < m and not fe_mul_out_is_one(t2)):
+                break
+        if i >= m:
+            break
+        b = c
+        for _ in range(i + 1, m):
+            b = fe_sqr(b, masks)
+        c = fe_sqr(b, masks)
+        t = fe_mul(t, c, masks)
+        r = fe_mul(r, b, masks)
+        m = i
+        if trace is not None:
+            trace.append(i)
+    return r
+
+
+def pt_mul_order(p, masks=DEFAULT_MASKS):
+    acc = pt_identity()
+    for k in range(ORDER_BITS - 1, -1, -1):
+        acc = pt_dbl(acc, masks)
+        if (R_ORDER >> k) & 1:
+            acc = pt_add(acc, p, masks)
+    return acc
+
+
+def pt_from_record(rec, masks=DEFAULT_MASKS):
+    """The extended point (x : y : x y : 1) of a halved record, as k_shift_bases, k_scale_points and
+    pt_from_record rebuild it."""
+    ymx, ypx = list(rec[0:NL]), list(rec[PRE_HALF:PRE_HALF + NL])
+    one = list(ONE29)
+    a = fe_mul(ymx, one, masks)
+    xs = fe_sub(ypx, a)
+    ys = fe_add_n(ypx, a)
+    return (fe_mul(xs, one, masks), fe_mul(ys, one, masks), fe_mul(xs, ys, masks), one)
+
+
+def shift_lane(rec, S, masks=DEFAULT_MASKS):
+    """One lane of k_shift_bases: the record of 2^S Q from the record of Q."""
+    p = pt_from_record(rec, masks)
+    for _ in range(S):
+        p = pt_dbl(p, masks)
+    zh = fe_mul(fe_inv(p[3], masks), HALF29, masks)
+    return halved_record(fe_mul(p[0], zh, masks), fe_mul(p[1], zh, masks), masks)
+
+
+def fixed_entry(j, win, d, w, Wn):
+    """k_fixed_eval's entry (record << 1 | sign) of digit d != 0 of base j, window win."""
+    return ((((j * Wn + win) << (w - 1)) + abs(d) - 1) << 1) | (1 if d < 0 else 0)
+
+
+def fixed_eval_chain(records, digits, w, Wn, masks=DEFAULT_MASKS):
+    """k_fixed_eval's accumulator after one row: digits[j][win] the signed digits of base j's scalar,
+    added base-major, windows ascending, zero digits skipped."""
+    acc = pt_identity()
+    for j, ds in enumerate(digits):
+        for win, d in enumerate(ds):
+            if d:
+                acc = pt_madd(acc, load_pre_signed(records, fixed_entry(j, win, d, w, Wn)), masks)
+    return acc

@@ -119,6 +119,13 @@ def test_records_of_every_level(n):
             vals, limbs = decode_record(lv[j][i])
             assert vals == expected_record_values(cur[i]), (j, i)
             check_record_bounds(limbs)
+    # every limb of a level's record, from the record below it through k_shift_bases' lane model: the
+    # first and last lanes of a wave, of a workgroup, and of the ragged last workgroup
+    masks = M._test_wide_masks()
+    for j in (1, 2):
+        for i in sorted({i for i in (0, 1, 63, 64, 254, 255, n - 1) if i < n}):
+            model = F.shift_lane([int(x) for x in lv[j - 1][i]], S, masks)
+            assert lv[j][i].tolist() == model, (j, i, lv[j - 1][i].tolist(), lv[j][i].tolist(), model)
     if n >= 16:  # the small-order points reach the identity after two doublings: its record
         assert all(decode_record(lv[1][i])[0] == expected_record_values((0, 1)) for i in (1, 2, 3, 4))
 

@@ -173,9 +173,12 @@ def fe_mul_sd(a: SB, b: SB, wide: int = WIDE_ALL) -> B:
 
 def test_madd_bounds():
     # halved record from k_prepare_points: ymx = fe_sub (normalised), ypx = fe_add_n, kt = fe_mul
-    ymx = fe_sub(N_MUL, N_MUL)
-    ypx = fe_norm(fe_add(N_MUL, N_MUL))
-    kt = N_MUL
+    madd_bounds(fe_sub(N_MUL, N_MUL), fe_norm(fe_add(N_MUL, N_MUL)), N_MUL)
+
+
+def madd_bounds(ymx: B, ypx: B, kt: B):
+    """pt_madd(acc, q) for acc an fe_mul-output point (or the identity) and q a record of these forms,
+    gathered with either sign."""
     for neg in (False, True):
         # the gather swaps the halves of a negated point (load_pre_signed); kt_neg_if negates d t
         q_ymx, q_ypx = (ypx, ymx) if neg else (ymx, ypx)
@@ -278,7 +281,11 @@ def padd_operands():
 
 
 def test_padd_bounds():
-    p = q = PT
+    padd_bounds(PT, PT)
+
+
+def padd_bounds(p, q):
+    """ec.cuh pt_add on two points of these coordinate forms; the sum's coordinates (fe_mul outputs)."""
     A = fe_mul(fe_sub_v(p["Y"], p["X"]), fe_sub_v(q["Y"], q["X"]), WIDE_EF)
     Bv = fe_mul(fe_add(p["Y"], p["X"]), fe_add(q["Y"], q["X"]))
     C = fe_mul_2d(fe_mul(p["T"], q["T"]))
@@ -288,10 +295,7 @@ def test_padd_bounds():
     F = fe_sub(D, C)
     G = fe_add(D, C)
     H = fe_add(Bv, A)
-    fe_mul(E, F)
-    fe_mul(G, H, WIDE_GH)
-    fe_mul(E, H)
-    fe_mul(F, G)
+    return dict(X=fe_mul(E, F), Y=fe_mul(G, H, WIDE_GH), T=fe_mul(E, H), Z=fe_mul(F, G))
 
 
 def test_mul_2d_exact_and_bounded():
@@ -389,7 +393,11 @@ def test_fe_mul_exact_model():
 
 
 def test_pdbl_bounds():
-    p = PT
+    pdbl_bounds(PT)
+
+
+def pdbl_bounds(p):
+    """ec.cuh pt_dbl on a point of these coordinate forms; the double's coordinates (fe_mul outputs)."""
     A = fe_mul(p["X"], p["X"])
     Bv = fe_mul(p["Y"], p["Y"])
     Z2 = fe_mul(p["Z"], p["Z"])
@@ -400,10 +408,7 @@ def test_pdbl_bounds():
     F = fe_sub(G, C)
     AB = fe_norm(fe_add(A, Bv))
     H = fe_norm(fe_sub_u(B([0] * NL, 0), AB))
-    fe_mul(E, F)
-    fe_mul(G, H)
-    fe_mul(E, H)
-    fe_mul(F, G)
+    return dict(X=fe_mul(E, F), Y=fe_mul(G, H), T=fe_mul(E, H), Z=fe_mul(F, G))
 
 
 def test_model_matches_header_constants():
@@ -472,21 +477,63 @@ REVIEWED = {
     ("fp29.cuh", "R256_29"): "d4cab8ce33c9709c",
     ("msm_kernels.hip", "k_prepare_points"): "931ef0feb027c2bc",
     ("msm_kernels.hip", "load_pre_signed"): "05db1a9e570b7dcc",
+    # the per-lane point kernels: mirrored by the proofs at the end of this file, by the limb-exact
+    # models of tests/_fp29_model.py (compared with the device by tests/test_gpu_lanes.py), or both
+    ("msm_kernels.hip", "pt_from_record"): "65c79ec907d4f2d4",
+    ("msm_kernels.hip", "fe_sqrt_ts"): "ccf73a991a94e3af",
+    ("msm_kernels.hip", "pt_mul_order"): "600edd33b364daaf",
+    ("msm_kernels.hip", "fe_std_neg"): "9e7074f7530e4424",
+    ("msm_kernels.hip", "fe_mul_out_is_one"): "d0b82e8a0a18d7de",
+    ("msm_kernels.hip", "fe_eq_limbs"): "3692a860963bb15f",
+    ("msm_kernels.hip", "fx_stage_affine"): "269d0c51e61e6955",
+    ("msm_kernels.hip", "fx_norm_prefix"): "6b51be8e8612ca6d",
+    ("msm_kernels.hip", "fx_norm_emit"): "99061a86909c099a",
+    ("msm_kernels.hip", "k_shift_bases"): "e5a8f1ad8f4395b1",
+    ("msm_kernels.hip", "k_decompress_x"): "f36e85518183137b",
+    ("msm_kernels.hip", "k_scale_points"): "7a84fc5274034f84",
+    ("msm_kernels.hip", "k_fixed_build"): "3800ab7a970e09cc",
+    ("msm_kernels.hip", "k_fixed_eval"): "76d61ec0169d6a38",
+    ("msm_kernels.hip", "k_fixed_normalise"): "d1986b0a91989aff",
+    ("msm_kernels.hip", "dx_omega_limb"): "b1639a51b5be8512",
+    ("msm_kernels.hip", "dx_exp_word"): "0551f4741ef8d48c",
+    ("msm_kernels.hip", "dx_order_word"): "d22ee440cc326040",
 }
 
 
-def _body(fname, name):
+def _source(fname):
     src = open(os.path.join(_CSRC, fname)).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
-    m = re.search(r"[^\n;{}]*\b" + re.escape(name) + r"\b\s*(\[[^\]]*\])?\s*(\([^)]*\))?\s*(=\s*)?\{", src)
-    assert m, f"{name} not found in {fname}"
-    i, depth = m.end() - 1, 0
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def _closing(src, i):
+    """Index of the bracket that closes the one at src[i]."""
+    pair = {"(": ")", "{": "}", "[": "]"}[src[i]]
+    depth = 0
     for j in range(i, len(src)):
-        depth += {"{": 1, "}": -1}.get(src[j], 0)
+        depth += 1 if src[j] == src[i] else -1 if src[j] == pair else 0
         if depth == 0:
-            return " ".join((src[m.start():j + 1]).split())
-    raise AssertionError(f"unbalanced braces after {name} in {fname}")
+            return j
+    raise AssertionError(f"unbalanced {src[i]} at {i}")
+
+
+def _body(fname, name):
+    """The definition of `name` (a function, a kernel or a constant table), from the start of its
+    line to its closing brace, whitespace squeezed.  The parameter list may span lines and hold
+    parentheses of its own (array references)."""
+    src = _source(fname)
+    for m in re.finditer(r"[^\n;{}]*\b" + re.escape(name) + r"\b", src):
+        i = m.end()
+        for opener in "[(=":
+            while src[i].isspace():
+                i += 1
+            if src[i] == opener:
+                i = i + 1 if opener == "=" else _closing(src, i) + 1
+        while src[i].isspace():
+            i += 1
+        if src[i] == "{":
+            return " ".join(src[m.start():_closing(src, i) + 1].split())
+    raise AssertionError(f"{name} not found in {fname}")
 
 
 def _body_digest(fname, name):
@@ -503,3 +550,210 @@ def test_wide_mask_constants_match_header():
     src = open(os.path.join(_CSRC, "fp29.cuh")).read()
     got = {k: int(v, 16) for k, v in re.findall(r"constexpr uint32_t (WIDE_[A-Z]+) = (0x[0-9A-Fa-f]+)u;", src)}
     assert got == {"WIDE_ALL": WIDE_ALL, "WIDE_GH": WIDE_GH, "WIDE_EH": WIDE_EH, "WIDE_EF": WIDE_EF}
+
+
+# ---- the per-lane point kernels (msm_kernels.hip k_shift_bases, k_decompress_x, k_scale_points, ----
+# ---- k_fixed_build, k_fixed_eval, k_fixed_normalise) ------------------------------------------------
+# One lane runs a whole chain of field code per point.  The proofs below walk each chain's call sites
+# with the interval machinery above, starting from the record forms k_prepare_points' proof derives
+# (test_madd_bounds; _bases_model.RECORD_VALUE_BOUNDS: (y-x)/2 < 10p, (y+x)/2 < 4p, d t < 2p).
+import _fp29_model as FM  # noqa: E402
+from _bases_model import RECORD_VALUE_BOUNDS  # noqa: E402
+
+
+def const_form(limbs) -> B:
+    """A constant operand: its own limbs and value."""
+    return B(limbs, value_of(limbs) + 1)
+
+
+def within(a: B, bound: B) -> bool:
+    return all(x <= y for x, y in zip(a.l, bound.l)) and a.v <= bound.v
+
+
+ONE_B, HALF_B, R2_B = const_form(FM.ONE29), const_form(FM.HALF29), const_form(FM.R2_29)
+UNIT_B = const_form([1] + [0] * (NL - 1))  # fe_to_std's multiplier
+REC_YMX, REC_YPX, REC_KT = (B.normalised(v) for v in RECORD_VALUE_BOUNDS)
+IDENTITY_PT = dict(X=const_form([0] * NL), Y=ONE_B, T=const_form([0] * NL), Z=ONE_B)
+
+
+def fe_mul_d(a: B) -> B:
+    """fp29.cuh fe_mul_d's input contract: normalised, value < 2^254.  Its output is an fe_mul output
+    (test_mul_d_exact_and_below_2p)."""
+    assert all(x <= MASK for x in a.l[:NL - 1]) and a.v <= 1 << 254, "fe_mul_d: operand outside its contract"
+    return N_MUL
+
+
+def fe_inv(a: B) -> B:
+    """fp29.cuh fe_inv: r = 1, then r = fe_sqr(r) and r = fe_mul(r, a) bit by bit, so r is ONE29 or an
+    fe_mul output at every multiply."""
+    for r in (ONE_B, N_MUL):
+        fe_mul(r, r)
+        fe_mul(r, a)
+    return N_MUL
+
+
+def fe_to_std(a: B) -> B:
+    return fe_mul(a, UNIT_B)
+
+
+def from_record_bounds(ymx: B, ypx: B):
+    """msm_kernels.hip pt_from_record (and its two textual copies, test_record_rebuild_is_one_text)."""
+    a = fe_mul(ymx, ONE_B)                # (y-x)/2, N_MUL
+    xs = fe_sub(ypx, a)                   # x + 8p: normalised, < 12p
+    assert within(xs, B.normalised(12 * P))
+    ys = fe_norm(fe_add(ypx, a))          # y: normalised, < 6p
+    assert within(ys, B.normalised(6 * P))
+    X = fe_mul(xs, ONE_B)
+    Y = fe_mul(ys, ONE_B)
+    assert xs.v * ys.v <= 72 * P * P < P * R  # the comment's "72 p^2 < p R"
+    T = fe_mul(xs, ys)
+    p = dict(X=X, Y=Y, T=T, Z=ONE_B)
+    assert all(within(c, N_MUL) for c in p.values())
+    return p
+
+
+def test_from_record_bounds():
+    # why (y-x)/2 takes the multiply by R first: its top limb may pass K8P's, which fe_sub would wrap
+    assert REC_YMX.l[NL - 1] > K8P29[NL - 1]
+    assert within(fe_sub(N_MUL, N_MUL), REC_YMX) and within(fe_norm(fe_add(N_MUL, N_MUL)), REC_YPX)
+    from_record_bounds(REC_YMX, REC_YPX)
+
+
+def shift_epilogue_bounds(p):
+    """k_shift_bases from fe_inv(p.Z) on: the three limb vectors of the record it writes."""
+    zh = fe_mul(fe_inv(p["Z"]), HALF_B)
+    x = fe_mul(p["X"], zh)
+    y = fe_mul(p["Y"], zh)
+    kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)))
+    return fe_sub(y, x), fe_norm(fe_add(y, x)), kt
+
+
+def test_shift_bases_closure():
+    """The records k_shift_bases writes satisfy the bounds of the records it reads, so level j + 1 may
+    feed level j + 2 and pt_madd (madd_bounds) alike."""
+    p0 = from_record_bounds(REC_YMX, REC_YPX)
+    p1 = pdbl_bounds(p0)   # the first doubling meets Z = 1, the later ones fe_mul outputs
+    p2 = pdbl_bounds(p1)
+    assert all(within(c, N_MUL) for c in p2.values())
+    for p in (p0, p1, p2):
+        for out, bound in zip(shift_epilogue_bounds(p), (REC_YMX, REC_YPX, REC_KT)):
+            assert within(out, bound), "k_shift_bases writes a record outside the bounds it reads"
+    madd_bounds(REC_YMX, REC_YPX, REC_KT)
+
+
+def _omega_limbs():
+    m = re.search(r"W\[NL\] = \{([^}]*)\}", _body("msm_kernels.hip", "dx_omega_limb"))
+    return [int(x.strip().rstrip("u")) for x in m.group(1).split(",")]
+
+
+def sqrt_ts_bounds(u: B):
+    """msm_kernels.hip fe_sqrt_ts: w, r, t, t2, b and c are 1, omega or fe_mul outputs, and every
+    multiply takes two of them or u."""
+    omega = _omega_limbs()
+    assert all(x <= MASK for x in omega) and value_of(omega) < P, "dx_omega_limb: not normalised below p"
+    forms = (ONE_B, const_form(omega), N_MUL, u)
+    for a in forms:
+        for b in forms:
+            fe_mul(a, b)
+    return N_MUL
+
+
+def test_omega_is_the_model_s():
+    omega = _omega_limbs()
+    assert omega == FM.OMEGA29
+    w = value_of(omega) * FM.RINV % P
+    assert pow(w, 1 << 47, P) == 1 and pow(w, 1 << 46, P) == P - 1
+
+
+def decompress_prologue_bounds():
+    """k_decompress_x from the x words to u = (x^2 + 1) / (1 - d x^2), and the point its ladder takes."""
+    xw = B.normalised(1 << 256)            # fe_from_words_le: eight words, normalised
+    xm = fe_mul(xw, R2_B)                  # fe_to_mont
+    x2 = fe_mul(xm, xm)
+    num = fe_norm(fe_add(x2, ONE_B))       # normalised, < 3p
+    assert within(num, B.normalised(3 * P))
+    den = fe_sub(ONE_B, fe_mul_d(x2))      # normalised, < 9p: one of the forms fe_inv receives
+    assert within(den, B.normalised(10 * P))
+    u = fe_mul(num, fe_inv(den))
+    r = sqrt_ts_bounds(u)
+    fe_to_std(fe_mul(r, r))
+    fe_to_std(u)
+    return dict(X=xm, Y=r, T=fe_mul(xm, r), Z=ONE_B)
+
+
+def test_decompress_bounds():
+    p = decompress_prologue_bounds()
+    assert all(within(c, N_MUL) for c in p.values())
+
+
+def ladder_step(acc, p):
+    """pt_add(pt_dbl(pt_dbl(acc)), p): a window of k_scale_points; k_fixed_build's and pt_mul_order's
+    pt_add(pt_dbl(acc), p) is the same pair of call sites."""
+    out = padd_bounds(pdbl_bounds(pdbl_bounds(acc)), p)
+    assert all(within(c, N_MUL) for c in out.values())
+    return out
+
+
+def test_ladder_closure():
+    rebuilt = from_record_bounds(REC_YMX, REC_YPX)
+    for p1 in (rebuilt, decompress_prologue_bounds(), PT):
+        p2 = pdbl_bounds(p1)             # k_scale_points' table: P, 2P, 3P and the identity
+        p3 = padd_bounds(p2, p1)
+        for acc in (IDENTITY_PT, PT):
+            for q in (IDENTITY_PT, p1, p2, p3):
+                acc = ladder_step(acc, q)
+            padd_bounds(pdbl_bounds(acc), p1)  # k_fixed_build, pt_mul_order
+
+
+def stage_affine_bounds(x: B, y: B):
+    """fx_stage_affine (and k_scale_points' own output statements): three canonical forms."""
+    fe_to_std(x)
+    fe_to_std(y)
+    fe_to_std(fe_mul(x, y))
+
+
+def test_remaining_call_sites():
+    # fe_inv's first multiply, for every form it is called with
+    fe_inv(N_MUL)                                     # k_shift_bases, k_scale_points, k_fixed_*: a Z
+    fe_inv(ONE_B)                                     # the identity's
+    fe_inv(fe_sub(ONE_B, N_MUL))                      # k_decompress_x: 1 - d x^2, an fe_sub output
+    fe_inv(B.normalised(10 * P))
+    # k_scale_points / k_fixed_build: one inversion per lane
+    zi = fe_inv(N_MUL)
+    stage_affine_bounds(fe_mul(N_MUL, zi), fe_mul(N_MUL, zi))
+    # k_fixed_normalise: Z is a pt_madd output or the identity's 1 (lanes past m)
+    for z in (N_MUL, ONE_B):
+        prefix = fe_mul(z, z)                         # fx_norm_prefix
+        prefix = fe_mul(prefix, z)
+        inv = fe_inv(prefix)
+        inv = fe_inv(z)                               # E = 1: prefix[0] itself
+        zi = fe_mul(inv, prefix)                      # fx_norm_emit
+        inv = fe_mul(inv, z)
+        stage_affine_bounds(fe_mul(N_MUL, zi), fe_mul(N_MUL, zi))
+        stage_affine_bounds(fe_mul(N_MUL, inv), fe_mul(N_MUL, inv))
+    # k_fixed_eval: the table's records are k_prepare_points' (PT_FMT_XY): test_madd_bounds' operands
+    madd_bounds(fe_sub(N_MUL, N_MUL), fe_norm(fe_add(N_MUL, N_MUL)), N_MUL)
+
+
+# ---- the record-rebuilding prologue exists as three texts; they are one reviewed text -------------
+def _statements(text, start, end, var=None):
+    text = text[text.index(start):]
+    text = text[:text.index(end) + len(end)]
+    if var:
+        text = re.sub(r"\b%s\b" % re.escape(var), "p", text)
+    return [" ".join(st.split()) for st in text.split(";")]
+
+
+def test_record_rebuild_is_one_text():
+    ref = _statements(_body("msm_kernels.hip", "pt_from_record"), "const fe one", "p.Z = one")
+    assert len(ref) == 9
+    for kernel, var in (("k_shift_bases", "p"), ("k_scale_points", "p1")):
+        got = _statements(_body("msm_kernels.hip", kernel), "const fe one", var + ".Z = one", var)
+        assert got == ref, f"{kernel} rebuilds the record's point differently from pt_from_record"
+
+
+def test_shift_lane_hook_runs_the_kernel_s_statements():
+    """k_test_limbs_lane's LOP_SHIFT_LANE: pt_from_record, then k_shift_bases' own epilogue."""
+    span = ("const fe zh", "rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1]")
+    ref = _statements(_body("msm_kernels.hip", "k_shift_bases"), *span)
+    assert _statements(_body("msm_kernels.hip", "k_test_limbs_lane"), *span) == ref and len(ref) > 12

@@ -39,6 +39,8 @@ void launch_limb_op(const uint32_t* a, const uint32_t* b, const uint32_t* neg, u
   const dim3 g(grid_for(n, 256)), t(256);
   if constexpr (OP == LOP_PT_QUAD)
     hipLaunchKernelGGL(k_test_limbs_quad, dim3(grid_for(4 * (size_t)n, 256)), t, 0, 0, a, b, out, n);
+  else if constexpr (OP >= LOP_SQR)
+    hipLaunchKernelGGL(k_test_limbs_lane<OP>, dim3(grid_for(n, 64)), dim3(64), 0, 0, a, b, out, n);
   else if constexpr (OP >= LOP_PT_ADD)
     hipLaunchKernelGGL(k_test_limbs_point<OP>, g, t, 0, 0, a, b, neg, out, n);
   else
@@ -411,10 +413,16 @@ int msm_test_fixed_plan(uint32_t k, uint32_t w, uint32_t b, uint32_t out[7]) {
 
 // out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
 // msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
+// The lane ops' loops are bounded whatever the operands hold: fe_sqrt_ts' m strictly decreases from
+// 47 and its inner loops stop at m, pt_mul_order and fe_inv walk constants, and LOP_SHIFT_LANE's
+// count (b, one word per record) is refused here above LOP_SHIFT_MAX.
 int msm_test_limb_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* neg, uint32_t* out, size_t n) {
   if (op >= (uint32_t)LOP_COUNT || n == 0 || n > (1u << 24) || !a || !out) return MSM_ERR_INVALID_ARG;
   const size_t wa = limb_op_in_words((int)op), wb = limb_op_b_words((int)op), wo = limb_op_out_words((int)op);
   if ((wb && !b) || (op == (uint32_t)LOP_PT_MADD && !neg)) return MSM_ERR_INVALID_ARG;
+  if (op == (uint32_t)LOP_SHIFT_LANE)  // the lane's loop is bounded before anything is launched
+    for (size_t i = 0; i < n; i++)
+      if (b[i] > LOP_SHIFT_MAX) return MSM_ERR_INVALID_ARG;
   DevCtx* c;
   int rc = get_ctx(-1, &c);
   if (rc != MSM_OK) return rc;
@@ -686,6 +694,94 @@ int msm_test_fixed_bases(const msm_fixed* h, msm_bases** out) {
     return MSM_OK;
   });
   return rc != MSM_OK ? rc : register_bases(nb, out);
+}
+
+// What the last msm_fixed_mul* of m points left in slot 0's fx_proj on the default device, read back
+// after the call as msm_test_acc_state reads its slot: nothing is launched.  out takes k_fixed_eval's
+// whole blocks, ceil(m / 64) * 27 * 64 words in the kernel's own layout (limb q of X | Y | Z of point
+// 64 g + l at (g * 27 + q) * 64 + l), the identities of the lanes past m included.
+int msm_test_fixed_proj(uint32_t* out, size_t m) {
+  if (!out || m == 0 || m >= (1ull << 30)) return MSM_ERR_INVALID_ARG;
+  DevCtx* c;
+  int rc = get_ctx(-1, &c);
+  if (rc != MSM_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  Slot& sl = c->slot[0];
+  const Buf& b = sl.ws.fx_proj;
+  const size_t bytes = fixed_proj_bytes(m);
+  if (!b.p || bytes > b.cap || !sl.stream) return MSM_ERR_INVALID_ARG;
+  HIPCHECK(hipStreamSynchronize(sl.stream));
+  HIPCHECK(hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
+  return MSM_OK;
+}
+
+// ---- the host field at operand level (hostfield.h, tests/test_host_field.py) ----------------------
+// out[i] = op(a[i], b[i]) on raw representatives: an element is the four little-endian 64-bit limbs an
+// Fq holds (its Montgomery form, R = 2^256), a point sixteen of them (X | Y | T | Z).  Nothing is
+// converted on the way in or out, so the caller prices every operation on plain integers:
+//   0 fq_mul   1, 2 fq_mul_n<3>, fq_mul_n<4> (element i on lane i mod N of its group; a last short
+//   group is filled with the elements before it)   3 fq_add   4 fq_sub   5 fq_inv   6 fq_from_std
+//   (a: a standard-form integer)   7 fq_to_std   8, 9, 10 div2k_mod at k = 1, 32, 63
+//   11, 12 pt_add with and without want_t   13 pt_dbl   14, 15, 16 pt_dbl_n at k = 1, 2, 5
+// b is read by ops 0..4, 11 and 12.  Every operand must be below p (the functions' precondition):
+// MSM_ERR_INVALID_ARG otherwise.  Needs no device.
+int msm_test_host_field(uint32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+  if (op > 16 || !a || !out || n == 0) return MSM_ERR_INVALID_ARG;
+  const bool pts = op >= 11;
+  const bool two = op <= 4 || op == 11 || op == 12;
+  const size_t w = pts ? 16 : 4;
+  if (two && !b) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n * w / 4; i++)
+    if (msmh::geq_p(a + 4 * i) || (two && msmh::geq_p(b + 4 * i))) return MSM_ERR_INVALID_ARG;
+  auto fq_at = [](const uint64_t* v, size_t i) {
+    Fq x;
+    memcpy(x.l, v + 4 * i, 32);
+    return x;
+  };
+  auto pt_at = [&](const uint64_t* v, size_t i) { return Pt{fq_at(v, 4 * i), fq_at(v, 4 * i + 1), fq_at(v, 4 * i + 2), fq_at(v, 4 * i + 3)}; };
+  auto put = [&](size_t i, const Fq& x) { memcpy(out + 4 * i, x.l, 32); };
+  auto put_pt = [&](size_t i, const Pt& p) {
+    put(4 * i, p.X);
+    put(4 * i + 1, p.Y);
+    put(4 * i + 2, p.T);
+    put(4 * i + 3, p.Z);
+  };
+  if (op == 1 || op == 2) {
+    const size_t N = op == 1 ? 3 : 4;
+    if (n < N) return MSM_ERR_INVALID_ARG;
+    for (size_t g0 = 0; g0 < n; g0 += N) {
+      const size_t g = g0 + N <= n ? g0 : n - N;  // the last group moves back to stay whole
+      Fq x[4], y[4], r[4];
+      for (size_t k = 0; k < N; k++) x[k] = fq_at(a, g + k), y[k] = fq_at(b, g + k);
+      if (N == 3) msmh::fq_mul_n<3>(r, x, y);
+      else msmh::fq_mul_n<4>(r, x, y);
+      for (size_t k = 0; k < N; k++) put(g + k, r[k]);
+    }
+    return MSM_OK;
+  }
+  for (size_t i = 0; i < n; i++) {
+    if (pts) {
+      const Pt p = pt_at(a, i);
+      Pt r;
+      if (op == 11) r = msmh::pt_add(p, pt_at(b, i));
+      else if (op == 12) r = msmh::pt_add(p, pt_at(b, i), false);
+      else if (op == 13) r = msmh::pt_dbl(p);
+      else r = msmh::pt_dbl_n(p, op == 14 ? 1 : op == 15 ? 2 : 5);
+      put_pt(i, r);
+      continue;
+    }
+    const Fq x = fq_at(a, i);
+    Fq r = x;
+    if (op == 0) r = msmh::fq_mul(x, fq_at(b, i));
+    else if (op == 3) r = msmh::fq_add(x, fq_at(b, i));
+    else if (op == 4) r = msmh::fq_sub(x, fq_at(b, i));
+    else if (op == 5) r = msmh::fq_inv(x);
+    else if (op == 6) r = msmh::fq_from_std(x.l);
+    else if (op == 7) msmh::fq_to_std(x, r.l);
+    else msmh::div2k_mod(r.l, op == 8 ? 1 : op == 9 ? 32 : 63);
+    put(i, r);
+  }
+  return MSM_OK;
 }
 
 // k_split_scalars on n wire scalars: out = the k * n virtual scalars of S bits (8 words each,

@@ -3503,17 +3503,27 @@ enum LimbOp : int {
   LOP_MUL_2D, LOP_MUL_D, LOP_SUB, LOP_NEG, LOP_ADD_N, LOP_DBL_N, LOP_TO_STD, LOP_TO_HOST_MONT, LOP_INV,
   LOP_FROM_WORDS, LOP_TO_WORDS, LOP_WORDS_LT_P,                       // [n][8] LE words on one side
   LOP_PT_ADD, LOP_PT_DBL, LOP_PT_MADD, LOP_PT_QUAD,                   // [n][36] X|Y|T|Z limbs
+  // the per-lane point kernels' functions (k_test_limbs_lane, tests/test_gpu_lanes.py)
+  LOP_SQR, LOP_STD_NEG, LOP_IS_ONE, LOP_SQRT_TS,                      // [n][9] limbs (is_one: one word out)
+  LOP_FROM_RECORD, LOP_MUL_ORDER, LOP_SHIFT_LANE,                     // record -> point, point -> point, record -> record
   LOP_COUNT
 };
+constexpr uint32_t LOP_SHIFT_MAX = 255;  // LOP_SHIFT_LANE's doublings per record: a handle's chunk bits S never pass it
+__host__ __device__ constexpr bool limb_op_is_point(int op) { return op >= LOP_PT_ADD && op <= LOP_PT_QUAD; }
 __host__ __device__ constexpr uint32_t limb_op_in_words(int op) {
-  return op >= LOP_PT_ADD ? PT_WORDS : (op == LOP_FROM_WORDS || op == LOP_WORDS_LT_P) ? 8u : (uint32_t)NL;
+  return limb_op_is_point(op) || op == LOP_MUL_ORDER ? PT_WORDS
+         : (op == LOP_FROM_RECORD || op == LOP_SHIFT_LANE) ? PRE_WORDS
+         : (op == LOP_FROM_WORDS || op == LOP_WORDS_LT_P) ? 8u : (uint32_t)NL;
 }
 __host__ __device__ constexpr uint32_t limb_op_b_words(int op) {  // 0: no second operand
   return op == LOP_PT_MADD ? 3u * NL : (op == LOP_PT_ADD || op == LOP_PT_QUAD) ? PT_WORDS
+         : op == LOP_SHIFT_LANE ? 1u  // the record's number of doublings
          : (op <= LOP_MUL_SD_S || op == LOP_SUB || op == LOP_ADD_N) ? (uint32_t)NL : 0u;
 }
 __host__ __device__ constexpr uint32_t limb_op_out_words(int op) {
-  return op >= LOP_PT_ADD ? PT_WORDS : op == LOP_TO_WORDS ? 8u : op == LOP_WORDS_LT_P ? 1u : (uint32_t)NL;
+  return limb_op_is_point(op) || op == LOP_FROM_RECORD || op == LOP_MUL_ORDER ? PT_WORDS
+         : op == LOP_SHIFT_LANE ? PRE_WORDS : op == LOP_TO_WORDS ? 8u
+         : (op == LOP_WORDS_LT_P || op == LOP_IS_ONE) ? 1u : (uint32_t)NL;
 }
 
 template <int OP>
@@ -3605,6 +3615,68 @@ __global__ void k_test_limbs_gather(const uint32_t* __restrict__ pts, const uint
   if (j >= m) return;
   const pre q = load_pre_signed(pts, ents[j]);
   store_pt(out + (size_t)j * PT_WORDS, pt_madd(load_pt(acc + (size_t)j * PT_WORDS), q));
+}
+
+// The functions the per-lane point kernels run (k_shift_bases, k_decompress_x, k_scale_points,
+// k_fixed_build) on raw limbs, one element per lane, 64 lanes per workgroup as those kernels have.
+// LOP_SHIFT_LANE is k_shift_bases' lane: the record's point rebuilt (pt_from_record, the very
+// statements of the kernel's prologue -- tests/test_limb_bounds.py compares the texts), doubled
+// b[i] times, and written back with the kernel's own epilogue statements (compared likewise).
+// Every loop is bounded whatever the operands hold: fe_sqrt_ts' m strictly decreases from 47 and
+// its inner loops stop at m, pt_mul_order runs the constant's 251 bits, fe_inv the exponent's 256,
+// and the host refuses a LOP_SHIFT_LANE count above LOP_SHIFT_MAX before it launches.
+template <int OP>
+__global__ void __launch_bounds__(64) k_test_limbs_lane(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                        uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (OP == LOP_SQR) {
+    store_fe(out + (size_t)i * NL, fe_sqr(load_fe(a + (size_t)i * NL)));
+  } else if constexpr (OP == LOP_STD_NEG) {
+    store_fe(out + (size_t)i * NL, fe_std_neg(load_fe(a + (size_t)i * NL)));
+  } else if constexpr (OP == LOP_IS_ONE) {
+    const fe one = fe_one();
+    const fe one_p = fe_add_n(one, fe_const(P29));  // as fe_sqrt_ts makes it
+    out[i] = fe_mul_out_is_one(load_fe(a + (size_t)i * NL), one, one_p) ? 1u : 0u;
+  } else if constexpr (OP == LOP_SQRT_TS) {
+    store_fe(out + (size_t)i * NL, fe_sqrt_ts(load_fe(a + (size_t)i * NL)));
+  } else if constexpr (OP == LOP_MUL_ORDER) {
+    store_pt(out + (size_t)i * PT_WORDS, pt_mul_order(load_pt(a + (size_t)i * PT_WORDS)));
+  } else {
+    uint32_t rec[32];
+#pragma unroll
+    for (int k = 0; k < 32; k++) rec[k] = a[(size_t)i * PRE_WORDS + k];
+    xyzt p = pt_from_record(rec);
+    if constexpr (OP == LOP_FROM_RECORD) {
+      store_pt(out + (size_t)i * PT_WORDS, p);
+    } else {
+      const uint32_t S = min(b[i], LOP_SHIFT_MAX);
+#pragma unroll 1
+      for (uint32_t s = 0; s < S; s++) p = pt_dbl(p);
+      // halved affine record, as k_prepare_points' projective branch writes it
+      const fe zh = fe_mul(fe_inv(p.Z), fe_const(HALF29));
+      const fe x = fe_mul(p.X, zh);
+      const fe y = fe_mul(p.Y, zh);
+      const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
+      const fe o_ymx = fe_sub(y, x);
+      const fe o_ypx = fe_add_n(y, x);
+#pragma unroll
+      for (int k = 0; k < 32; k++) rec[k] = 0;
+#pragma unroll
+      for (int k = 0; k < NL; k++) {
+        rec[k] = o_ymx.v[k];
+        rec[PRE_HALF + k] = o_ypx.v[k];
+      }
+#pragma unroll
+      for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
+      // the duplicated top limbs (msm_dev.h PRE_WORDS)
+      rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
+      rec[NL + 1] = o_ypx.v[NL - 1];
+      rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1];
+#pragma unroll
+      for (int k = 0; k < 32; k++) out[(size_t)i * PRE_WORDS + k] = rec[k];
+    }
+  }
 }
 
 }  // namespace msm

@@ -218,6 +218,8 @@ def load() -> ctypes.CDLL:
                                    ctypes.POINTER(ctypes.c_int32), u32p, u32p], ctypes.c_int),
         "msm_test_fixed_plan": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
         "msm_test_fixed_bases": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_test_fixed_proj": ([u32p, sz], ctypes.c_int),
+        "msm_test_host_field": ([ctypes.c_uint32, vp, vp, vp, sz], ctypes.c_int),
         "msm_test_subset_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
                                   u32p], ctypes.c_int),
         "msm_test_bases_plan": ([sz, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -1499,7 +1501,9 @@ _LIMB_OPS = {name: (i, wa, wb, wo) for i, (name, wa, wb, wo) in enumerate((
     ("mul_sd_u", 9, 9, 9), ("mul_sd_s", 9, 9, 9), ("mul_2d", 9, 0, 9), ("mul_d", 9, 0, 9), ("sub", 9, 9, 9),
     ("neg", 9, 0, 9), ("add_n", 9, 9, 9), ("dbl_n", 9, 0, 9), ("to_std", 9, 0, 9), ("to_host_mont", 9, 0, 9),
     ("inv", 9, 0, 9), ("from_words", 8, 0, 9), ("to_words", 9, 0, 8), ("words_lt_p", 8, 0, 1),
-    ("pt_add", 36, 36, 36), ("pt_dbl", 36, 0, 36), ("pt_madd", 36, 27, 36), ("pt_add_quad", 36, 36, 36)))}
+    ("pt_add", 36, 36, 36), ("pt_dbl", 36, 0, 36), ("pt_madd", 36, 27, 36), ("pt_add_quad", 36, 36, 36),
+    ("sqr", 9, 0, 9), ("std_neg", 9, 0, 9), ("is_one", 9, 0, 1), ("sqrt_ts", 9, 0, 9),
+    ("from_record", 32, 0, 36), ("mul_order", 36, 0, 36), ("shift_lane", 32, 1, 32)))}
 
 
 def _test_wide_masks() -> Tuple[int, int, int, int]:
@@ -1554,9 +1558,51 @@ def _test_fixed_plan(bases: int, window_bits: int = 0, scalar_bits: int = 0) -> 
             "records": int(o[3]) | int(o[4]) << 32, "bytes": int(o[5]) | int(o[6]) << 32}
 
 
+# msm_test_host_field's ops (csrc/host_test_hooks.h): name -> (op, takes b, works on points)
+_HOST_FIELD_OPS = {name: (i, two, pt) for i, (name, two, pt) in enumerate((
+    ("mul", True, False), ("mul_n3", True, False), ("mul_n4", True, False), ("add", True, False), ("sub", True, False),
+    ("inv", False, False), ("from_std", False, False), ("to_std", False, False), ("div2k_1", False, False),
+    ("div2k_32", False, False), ("div2k_63", False, False), ("pt_add", True, True), ("pt_add_no_t", True, True),
+    ("pt_dbl", False, True), ("pt_dbl_n1", False, True), ("pt_dbl_n2", False, True), ("pt_dbl_n5", False, True)))}
+
+
+def _test_host_field(name: str, a, b=None) -> list:
+    """hostfield.h's function `name` (_HOST_FIELD_OPS) on raw representatives below p: Python ints, the
+    integer an Fq's four limbs hold (msm_test_host_field); points are (X, Y, T, Z) tuples of them.
+    Returns ints, or tuples of four.  Needs no device."""
+    op, two, pt = _HOST_FIELD_OPS[name]
+    w = 4 if pt else 1
+
+    def pack(vals):
+        flat = [c for v in vals for c in v] if pt else list(vals)
+        return np.array([(int(v) >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for v in flat for k in range(4)], dtype=np.uint64)
+
+    av = pack(a)
+    n = av.size // (4 * w)
+    bv = pack(b) if two else None
+    if two and bv.size != av.size:
+        raise ValueError("a and b differ in length")
+    out = np.zeros(av.size, dtype=np.uint64)
+    _check(load().msm_test_host_field(op, av.ctypes.data, bv.ctypes.data if two else None, out.ctypes.data, n),
+           "msm_test_host_field")
+    vals = [sum(int(x) << (64 * k) for k, x in enumerate(out[4 * i: 4 * i + 4])) for i in range(n * w)]
+    return [tuple(vals[4 * i: 4 * i + 4]) for i in range(n)] if pt else vals
+
+
+def _test_fixed_proj(m: int) -> np.ndarray:
+    """What the last fixed-base evaluation of m points on the default device left in its slot
+    (msm_test_fixed_proj; nothing is launched): [ceil(m / 64) * 64, 27] limbs X | Y | Z per lane,
+    the lanes past m included."""
+    nblk = (int(m) + 63) // 64
+    o, op_ = _out(nblk * 27 * 64)
+    _check(load().msm_test_fixed_proj(op_, int(m)), "msm_test_fixed_proj")
+    return np.ascontiguousarray(o.reshape(nblk, 27, 64).transpose(0, 2, 1)).reshape(nblk * 64, 27)
+
+
 def _test_limb_op(name: str, a, b=None, neg=None) -> np.ndarray:
     """Device op `name` (_LIMB_OPS) on raw u32 limb arrays: a [n, wa], b [n, wb] for the two-operand
-    ops, neg [n] negate flags for pt_madd -> [n, wo] (test hook)."""
+    ops (shift_lane: the doublings of each record, at most 255), neg [n] negate flags for pt_madd
+    -> [n, wo] (test hook)."""
     op, wa, wb, wo = _LIMB_OPS[name]
     a = _u32(a).reshape(-1, wa)
     n = a.shape[0]
