@@ -172,7 +172,8 @@ def fe_mul_sd(a: SB, b: SB, wide: int = WIDE_ALL) -> B:
 
 
 def test_madd_bounds():
-    # halved record from k_prepare_points: ymx = fe_sub (normalised), ypx = fe_add_n, kt = fe_mul
+    # halved record from record_from_halved (k_prepare_points, k_shift_bases): ymx = fe_sub (normalised),
+    # ypx = fe_add_n, kt = fe_mul_d of an fe_mul output
     madd_bounds(fe_sub(N_MUL, N_MUL), fe_norm(fe_add(N_MUL, N_MUL)), N_MUL)
 
 
@@ -475,7 +476,7 @@ REVIEWED = {
     ("fp29.cuh", "R2H_29"): "67d729fb41ed6ee0",
     ("fp29.cuh", "HALF29"): "fb513a1a00dd9fdd",
     ("fp29.cuh", "R256_29"): "d4cab8ce33c9709c",
-    ("msm_kernels.hip", "k_prepare_points"): "931ef0feb027c2bc",
+    ("msm_kernels.hip", "k_prepare_points"): "dbf1e8d8c7910cf4",
     ("msm_kernels.hip", "load_pre_signed"): "05db1a9e570b7dcc",
     # the per-lane point kernels: mirrored by the proofs at the end of this file, by the limb-exact
     # models of tests/_fp29_model.py (compared with the device by tests/test_gpu_lanes.py), or both
@@ -485,14 +486,20 @@ REVIEWED = {
     ("msm_kernels.hip", "fe_std_neg"): "9e7074f7530e4424",
     ("msm_kernels.hip", "fe_mul_out_is_one"): "d0b82e8a0a18d7de",
     ("msm_kernels.hip", "fe_eq_limbs"): "3692a860963bb15f",
-    ("msm_kernels.hip", "fx_stage_affine"): "269d0c51e61e6955",
+    # the lane frame: the helpers that hold field code or a limb layout (rec[32] <-> slots, words <-> slots)
+    ("msm_kernels.hip", "record_from_halved"): "9ca1278c4dccbb09",
+    ("msm_kernels.hip", "lane_read_record"): "5e0294e9f8020f58",
+    ("msm_kernels.hip", "lane_gather_record"): "dac88734a06a41b0",
+    ("msm_kernels.hip", "lane_put_record"): "6fb72bb7c188c881",
+    ("msm_kernels.hip", "lane_stage_words"): "b7ffb7a516e0e1b0",
+    ("msm_kernels.hip", "lane_stage_affine"): "c76c0f00406dd582",
     ("msm_kernels.hip", "fx_norm_prefix"): "6b51be8e8612ca6d",
-    ("msm_kernels.hip", "fx_norm_emit"): "99061a86909c099a",
-    ("msm_kernels.hip", "k_shift_bases"): "e5a8f1ad8f4395b1",
-    ("msm_kernels.hip", "k_decompress_x"): "f36e85518183137b",
-    ("msm_kernels.hip", "k_scale_points"): "7a84fc5274034f84",
-    ("msm_kernels.hip", "k_fixed_build"): "3800ab7a970e09cc",
-    ("msm_kernels.hip", "k_fixed_eval"): "76d61ec0169d6a38",
+    ("msm_kernels.hip", "fx_norm_emit"): "9db8989a95464049",
+    ("msm_kernels.hip", "k_shift_bases"): "f0d08d8c3998f392",
+    ("msm_kernels.hip", "k_decompress_x"): "f9e7902f9984724f",
+    ("msm_kernels.hip", "k_scale_points"): "bfde00ebbfd9ffd9",
+    ("msm_kernels.hip", "k_fixed_build"): "70a4acb75279aa06",
+    ("msm_kernels.hip", "k_fixed_eval"): "5098db9f158c1bc0",
     ("msm_kernels.hip", "k_fixed_normalise"): "d1986b0a91989aff",
     ("msm_kernels.hip", "dx_omega_limb"): "b1639a51b5be8512",
     ("msm_kernels.hip", "dx_exp_word"): "0551f4741ef8d48c",
@@ -597,7 +604,8 @@ def fe_to_std(a: B) -> B:
 
 
 def from_record_bounds(ymx: B, ypx: B):
-    """msm_kernels.hip pt_from_record (and its two textual copies, test_record_rebuild_is_one_text)."""
+    """msm_kernels.hip pt_from_record, the only place the rebuild exists (test_record_rebuild_is_one_text):
+    k_shift_bases, k_scale_points, k_fixed_build and k_test_limbs_lane call it."""
     a = fe_mul(ymx, ONE_B)                # (y-x)/2, N_MUL
     xs = fe_sub(ypx, a)                   # x + 8p: normalised, < 12p
     assert within(xs, B.normalised(12 * P))
@@ -620,7 +628,8 @@ def test_from_record_bounds():
 
 
 def shift_epilogue_bounds(p):
-    """k_shift_bases from fe_inv(p.Z) on: the three limb vectors of the record it writes."""
+    """k_shift_bases from fe_inv(p.Z) on -- its zh, x and y, then record_from_halved: the three limb vectors
+    of the record it writes."""
     zh = fe_mul(fe_inv(p["Z"]), HALF_B)
     x = fe_mul(p["X"], zh)
     y = fe_mul(p["Y"], zh)
@@ -706,7 +715,8 @@ def test_ladder_closure():
 
 
 def stage_affine_bounds(x: B, y: B):
-    """fx_stage_affine (and k_scale_points' own output statements): three canonical forms."""
+    """lane_stage_affine (k_scale_points, k_fixed_build, k_fixed_normalise): three canonical forms, handed
+    to lane_stage_words as words."""
     fe_to_std(x)
     fe_to_std(y)
     fe_to_std(fe_mul(x, y))
@@ -735,25 +745,44 @@ def test_remaining_call_sites():
     madd_bounds(fe_sub(N_MUL, N_MUL), fe_norm(fe_add(N_MUL, N_MUL)), N_MUL)
 
 
-# ---- the record-rebuilding prologue exists as three texts; they are one reviewed text -------------
-def _statements(text, start, end, var=None):
+# ---- the record-rebuilding prologue and the record epilogue exist once ----------------------------
+def _squeezed(fname):
+    return " ".join(_source(fname).split())
+
+
+def _statements(text, start, end):
     text = text[text.index(start):]
     text = text[:text.index(end) + len(end)]
-    if var:
-        text = re.sub(r"\b%s\b" % re.escape(var), "p", text)
     return [" ".join(st.split()) for st in text.split(";")]
 
 
+def _calls(kernel, helper):
+    return re.search(r"\b%s\(" % re.escape(helper), _body("msm_kernels.hip", kernel)) is not None
+
+
 def test_record_rebuild_is_one_text():
+    """No kernel rebuilds a record's point with statements of its own: every right-hand side of
+    pt_from_record's field code occurs once in msm_kernels.hip, and the kernels that rebuild call it."""
+    src = _squeezed("msm_kernels.hip")
     ref = _statements(_body("msm_kernels.hip", "pt_from_record"), "const fe one", "p.Z = one")
     assert len(ref) == 9
-    for kernel, var in (("k_shift_bases", "p"), ("k_scale_points", "p1")):
-        got = _statements(_body("msm_kernels.hip", kernel), "const fe one", var + ".Z = one", var)
-        assert got == ref, f"{kernel} rebuilds the record's point differently from pt_from_record"
+    field = [st.split(" = ", 1)[1] for st in ref if re.search(r"= fe_(mul|sub|add_n)\(", st)]
+    assert len(field) == 6 and field[0] == "fe_mul(ymx, one)"
+    for rhs in field:
+        assert src.count(rhs) == 1, f"{rhs} occurs {src.count(rhs)} times"
+    for kernel in ("k_shift_bases", "k_scale_points", "k_fixed_build", "k_test_limbs_lane"):
+        assert _calls(kernel, "pt_from_record"), f"{kernel} does not call pt_from_record"
 
 
 def test_shift_lane_hook_runs_the_kernel_s_statements():
-    """k_test_limbs_lane's LOP_SHIFT_LANE: pt_from_record, then k_shift_bases' own epilogue."""
-    span = ("const fe zh", "rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1]")
-    ref = _statements(_body("msm_kernels.hip", "k_shift_bases"), *span)
-    assert _statements(_body("msm_kernels.hip", "k_test_limbs_lane"), *span) == ref and len(ref) > 12
+    """The record epilogue (d t, the two halves, the duplicated top limbs) exists once, in
+    record_from_halved; k_prepare_points, k_shift_bases and k_test_limbs_lane's LOP_SHIFT_LANE call it,
+    and the hook rebuilds with pt_from_record as the kernel does."""
+    src = _squeezed("msm_kernels.hip")
+    body = _body("msm_kernels.hip", "record_from_halved")
+    for text in ("fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)))", "rec[NL] = rec[PRE_HALF + NL] =", "rec[NL + 1] =",
+                 "rec[PRE_HALF + NL + 1] =", "rec[PRE_KT + k] ="):
+        assert body.count(text) == 1 and src.count(text) == 1, f"{text} occurs {src.count(text)} times"
+    for kernel in ("k_prepare_points", "k_shift_bases", "k_test_limbs_lane"):
+        assert _calls(kernel, "record_from_halved"), f"{kernel} does not call record_from_halved"
+    assert _calls("k_test_limbs_lane", "pt_from_record")

@@ -89,19 +89,126 @@ void launch_shift_levels(const Bases& b, uint32_t nt, hipStream_t s) {
                        b.geo.S, nt);
 }
 
-// A finished creation into the registry: *out is the new handle's token.
-int register_bases(const std::shared_ptr<Bases>& b, msm_bases** out) {
-  b->alive = true;  // n = 0: nothing allocated
+// A finished creation (a handle, or host_fixed.h's table) into its registry: *out is the new token.
+// `has_rec` is false for a handle of no points, which allocated nothing.
+template <typename H, typename Tok>
+int register_handle(std::map<uintptr_t, std::shared_ptr<H>>& registry, const std::shared_ptr<H>& h, bool has_rec,
+                    Tok** out) {
+  h->alive = true;
   std::lock_guard<std::mutex> lk(g_mu);
-  // msm_shutdown may have run since the records were made (it frees only registered handles)
-  if (b->n && ((int)g_ctx.size() <= b->device || !g_ctx[b->device])) {
-    b->rec.release();
+  // msm_shutdown may have run since the records were made (it frees only registered handles and tables)
+  if (has_rec && ((int)g_ctx.size() <= h->device || !g_ctx[h->device])) {
+    h->rec.release();
     return MSM_ERR_INVALID_ARG;
   }
   const uintptr_t id = g_bases_next++;
-  g_bases[id] = b;
-  *out = reinterpret_cast<msm_bases*>(id);
+  registry[id] = h;
+  *out = reinterpret_cast<Tok*>(id);
   return MSM_OK;
+}
+int register_bases(const std::shared_ptr<Bases>& b, msm_bases** out) { return register_handle(g_bases, b, b->n != 0, out); }
+
+// The device's error bits as the entry's return code.  A kernel that never raises a bit never sets it,
+// so one order serves every caller.
+int dev_err_code(uint32_t bits) {
+  if (bits & (MSM_DEV_ERR_BAD_INDEX | MSM_DEV_ERR_SCALAR_RANGE)) return MSM_ERR_INVALID_ARG;
+  if (bits & MSM_DEV_ERR_COORD_RANGE) return MSM_ERR_COORD_RANGE;
+  if (bits & MSM_DEV_ERR_BAD_POINT) return MSM_ERR_BAD_POINT;
+  return MSM_OK;
+}
+
+// The call frame of the entries that run the per-point kernels on slot 0's stream (create_bases,
+// decompress_points, bases_scale, fixed_create, fixed_mul): the kernels' error word, the new records
+// (if the call makes any), and every exit past the allocations.
+struct PointCall {
+  DevCtx* c = nullptr;
+  Buf errb;             // the error word
+  Buf* rec = nullptr;   // the new records: released on failure, so a failure leaves nothing allocated
+  hipStream_t stream() const { return c->slot[0].stream; }
+  uint32_t* errp() { return errb.as<uint32_t>(); }
+  // The error word, then `rec_bytes` of new records in *new_rec (null: the call makes none), then the
+  // word zeroed on the stream.
+  int begin(DevCtx* ctx, Buf* new_rec = nullptr, size_t rec_bytes = 0) {
+    c = ctx;
+    int r = errb.ensure(16);
+    if (r != MSM_OK) return r;
+    if (new_rec && (r = new_rec->ensure(rec_bytes)) != MSM_OK) {
+      errb.release();
+      return r;
+    }
+    rec = new_rec;
+    if (hipMemsetAsync(errp(), 0, 16, stream()) != hipSuccess) return done(MSM_ERR_HIP);
+    return MSM_OK;
+  }
+  // The stream behind the caller's.
+  int after_user(hipStream_t user_stream) {
+    const int r = order_after_user(c, user_stream, 1);
+    return r != MSM_OK ? done(r) : r;
+  }
+  int done(int code) {
+    drain_streams(c, 1, code);
+    if (errb.base) {  // guarded (host_guard.h): the word does not outlive the call, so it is looked at here
+      std::lock_guard<std::mutex> gl(g_guard_mu);
+      (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
+    }
+    errb.release();
+    if (code != MSM_OK && rec) rec->release();
+    return code;
+  }
+  // After the last launch: m wire records from `d_points` to the host's `points` (null: none), the
+  // error word back, and the call's code.
+  int finish(uint32_t* points = nullptr, const uint32_t* d_points = nullptr, size_t m = 0) {
+    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
+    uint32_t e[4] = {};
+    if ((points && hipMemcpyAsync(points, d_points, m * 128, hipMemcpyDeviceToHost, stream()) != hipSuccess) ||
+        hipMemcpyAsync(e, errp(), 16, hipMemcpyDeviceToHost, stream()) != hipSuccess ||
+        hipStreamSynchronize(stream()) != hipSuccess)
+      return done(MSM_ERR_HIP);
+    return done(dev_err_code(e[0]));
+  }
+};
+
+// Host words up into slot buffers on the copy stream -- every buffer sized first, then every copy --
+// and slot 0's stream behind them.  An entry without words (src null) is skipped.
+struct HostWords {
+  Buf* dst;
+  const uint32_t* src;
+  size_t bytes;
+};
+int upload_words(DevCtx* c, std::initializer_list<HostWords> sets) {
+  for (const HostWords& w : sets)
+    if (w.src)
+      if (int r = w.dst->ensure(w.bytes)) return r;
+  for (const HostWords& w : sets)
+    if (w.src)
+      if (int r = upload(c, w.dst->p, w.src, w.bytes, w.bytes, [](size_t, size_t) { return MSM_OK; })) return r;
+  HIPCHECK(hipEventRecord(c->ev_chunk[0], c->copy_stream));
+  HIPCHECK(hipStreamWaitEvent(c->slot[0].stream, c->ev_chunk[0], 0));
+  return MSM_OK;
+}
+
+// msm_bases_scale* and msm_fixed_mul*: a device caller's pointers, from their values -- the scalars'
+// alignment (`per` words per output point, `sw` of them per scalar), and the m wire records of `points`
+// (null: the call creates a handle) 16-byte aligned and clear of the scalars.
+bool point_call_ptrs_ok(const uint32_t* scalars, size_t sw, size_t per, size_t m, const uint32_t* points) {
+  const uintptr_t sp = reinterpret_cast<uintptr_t>(scalars), pp = reinterpret_cast<uintptr_t>(points);
+  if (sp & (sw == 8 ? 15u : 3u)) return false;
+  return !points || !((pp & 15u) || (pp < sp + m * per * 4 && sp < pp + m * 128));
+}
+// Where their kernels write: the caller's `points`, or the slot's dx_pts for a host call (wire records,
+// copied down by PointCall::finish) and for a creation (x|y, prepared by launch_created).
+int point_call_output(Slot& s0, bool host, bool created, size_t m, uint32_t** d_out) {
+  if (!host && !created) return MSM_OK;
+  if (int r = s0.ws.dx_pts.ensure(m * (created ? 64 : 128))) return r;
+  *d_out = s0.ws.dx_pts.as<uint32_t>();
+  return MSM_OK;
+}
+// A creation's tail: the m x|y points at `xy` into nb's level 0, as a compressed creation's are, and its
+// shifted levels.
+void launch_created(const Bases& nb, const uint32_t* xy, size_t m, uint32_t* errp, hipStream_t s) {
+  const uint32_t nt = prep_nt((size_t)nb.levels * m);
+  launch_prepare(xy, nb.rec.as<uint32_t>(), (uint32_t)m, errp, nt, s, PT_FMT_XY);
+  launch_shift_levels(nb, nt, s);
 }
 
 // `form` 0: `points` are wire records; MSM_POINTS_X_*: compressed points, decompressed into the slot's
@@ -123,55 +230,32 @@ int create_bases(const uint32_t* points, bool host, size_t n, uint32_t form, con
     if (!n) return MSM_OK;
     if (int prc = bases_plan_exists(c, *b, wb)) return prc;
     Slot& s0 = c->slot[0];
-    Buf errb;  // the preparation's error word
-    int r = errb.ensure(16);
-    if (r != MSM_OK) return r;
-    if ((r = b->rec.ensure((size_t)levels * n * PRE_WORDS * 4)) != MSM_OK) {
-      errb.release();
-      return r;
-    }
-    auto done = [&](int code) {  // every exit past the allocations: a failure leaves nothing allocated
-      drain_streams(c, 1, code);
-      if (errb.base) {  // guarded (host_guard.h): the word does not outlive the call, so it is looked at here
-        std::lock_guard<std::mutex> gl(g_guard_mu);
-        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
-      }
-      errb.release();
-      if (code != MSM_OK) b->rec.release();
-      return code;
-    };
+    PointCall f;
+    int r = f.begin(c, &b->rec, (size_t)levels * n * PRE_WORDS * 4);
+    if (r != MSM_OK || (r = f.after_user(user_stream)) != MSM_OK) return r;
     uint32_t* rec = b->rec.as<uint32_t>();
-    uint32_t* errp = errb.as<uint32_t>();
-    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
-    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    uint32_t* errp = f.errp();
     const uint32_t nt = prep_nt((size_t)levels * n);
     if (form) {
       const uint32_t* d_xs = points;
       if (host) {  // 32 n bytes up, into the wire buffer
-        if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK) return done(r);
+        if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK) return f.done(r);
         if ((r = upload_scalars(c, points, n, s0.ws.wire_pts.as<uint32_t>(), s0.stream, c->ev_chunk[0])) != MSM_OK)
-          return done(r);
+          return f.done(r);
         d_xs = s0.ws.wire_pts.as<uint32_t>();
       }
-      if ((r = s0.ws.dx_pts.ensure(n * 64)) != MSM_OK) return done(r);
+      if ((r = s0.ws.dx_pts.ensure(n * 64)) != MSM_OK) return f.done(r);
       launch_decompress(d_xs, s0.ws.dx_pts.as<uint32_t>(), (uint32_t)n, form, 0, errp, s0.stream);
       launch_prepare(s0.ws.dx_pts.as<uint32_t>(), rec, (uint32_t)n, errp, nt, s0.stream, PT_FMT_XY);
     } else if (host) {
-      if ((r = s0.ws.wire_pts.ensure(n * 128)) != MSM_OK) return done(r);
+      if ((r = s0.ws.wire_pts.ensure(n * 128)) != MSM_OK) return f.done(r);
       if ((r = upload_points(c, points, n, s0.ws.wire_pts.as<uint32_t>(), rec, errp, s0.stream)) != MSM_OK)
-        return done(r);
+        return f.done(r);
     } else {
       launch_prepare(points, rec, (uint32_t)n, errp, nt, s0.stream);
     }
     launch_shift_levels(*b, nt, s0.stream);
-    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
-    uint32_t e[4] = {};
-    if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
-        hipStreamSynchronize(s0.stream) != hipSuccess)
-      return done(MSM_ERR_HIP);
-    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
-    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
-    return done(MSM_OK);
+    return f.finish();
   });
   if (rc != MSM_OK) return rc;
   return register_bases(b, out);
@@ -190,40 +274,21 @@ int decompress_points(const uint32_t* xs, bool host, size_t n, uint32_t form, co
   return on_device(&od, [&](DevCtx* c) -> int {
     if (!n) return MSM_OK;
     Slot& s0 = c->slot[0];
-    Buf errb;
-    int r = errb.ensure(16);
-    if (r != MSM_OK) return r;
-    auto done = [&](int code) {  // as create_bases'
-      drain_streams(c, 1, code);
-      if (errb.base) {
-        std::lock_guard<std::mutex> gl(g_guard_mu);
-        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
-      }
-      errb.release();
-      return code;
-    };
-    uint32_t* errp = errb.as<uint32_t>();
-    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
-    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    PointCall f;
+    int r = f.begin(c);
+    if (r != MSM_OK || (r = f.after_user(user_stream)) != MSM_OK) return r;
     const uint32_t* d_xs = xs;
     uint32_t* d_out = points;
     if (host) {
-      if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK || (r = s0.ws.dx_pts.ensure(n * 128)) != MSM_OK) return done(r);
+      if ((r = s0.ws.wire_pts.ensure(n * 32)) != MSM_OK || (r = s0.ws.dx_pts.ensure(n * 128)) != MSM_OK)
+        return f.done(r);
       if ((r = upload_scalars(c, xs, n, s0.ws.wire_pts.as<uint32_t>(), s0.stream, c->ev_chunk[0])) != MSM_OK)
-        return done(r);
+        return f.done(r);
       d_xs = s0.ws.wire_pts.as<uint32_t>();
       d_out = s0.ws.dx_pts.as<uint32_t>();
     }
-    launch_decompress(d_xs, d_out, (uint32_t)n, form, 1, errp, s0.stream);
-    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
-    uint32_t e[4] = {};
-    if ((host && hipMemcpyAsync(points, d_out, n * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
-        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
-        hipStreamSynchronize(s0.stream) != hipSuccess)
-      return done(MSM_ERR_HIP);
-    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
-    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
-    return done(MSM_OK);
+    launch_decompress(d_xs, d_out, (uint32_t)n, form, 1, f.errp(), s0.stream);
+    return f.finish(host ? points : nullptr, d_out, n);
   });
 }
 
@@ -275,11 +340,9 @@ int bases_scale(const msm_bases* h, const msm_subset_t* sub, const uint32_t* sca
   if (created)
     if (int rc = bases_shape(nb.get(), m, levels, wb)) return rc;
   const size_t sw = (bits + 31) / 32;
-  if (!host && m) {  // alignment and overlap, from the pointer values
-    const uintptr_t sp = reinterpret_cast<uintptr_t>(scalars), pp = reinterpret_cast<uintptr_t>(points);
-    if ((sp & (sw == 8 ? 15u : 3u)) || (reinterpret_cast<uintptr_t>(indices) & 3u)) return MSM_ERR_INVALID_ARG;
-    if (!created && ((pp & 15u) || (pp < sp + m * sw * 4 && sp < pp + m * 128))) return MSM_ERR_INVALID_ARG;
-  }
+  if (!host && m &&
+      (!point_call_ptrs_ok(scalars, sw, sw, m, created ? nullptr : points) || (reinterpret_cast<uintptr_t>(indices) & 3u)))
+    return MSM_ERR_INVALID_ARG;
   if (host) {  // every scalar and every index, before anything is uploaded or enqueued
     if (bits & 31u) {
       const uint32_t excess = ~((1u << (bits & 31u)) - 1u);
@@ -299,63 +362,24 @@ int bases_scale(const msm_bases* h, const msm_subset_t* sub, const uint32_t* sca
     if (created)
       if (int prc = bases_plan_exists(c, *nb, wb)) return prc;
     Slot& s0 = c->slot[0];
-    Buf errb;
-    int r = errb.ensure(16);
-    if (r != MSM_OK) return r;
-    if (created && (r = nb->rec.ensure((size_t)nb->levels * m * PRE_WORDS * 4)) != MSM_OK) {
-      errb.release();
-      return r;
-    }
-    auto done = [&](int code) {  // as create_bases'
-      drain_streams(c, 1, code);
-      if (errb.base) {
-        std::lock_guard<std::mutex> gl(g_guard_mu);
-        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
-      }
-      errb.release();
-      if (code != MSM_OK) nb->rec.release();
-      return code;
-    };
-    uint32_t* errp = errb.as<uint32_t>();
-    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
-    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    PointCall f;
+    int r = f.begin(c, created ? &nb->rec : nullptr, (size_t)nb->levels * m * PRE_WORDS * 4);
+    if (r != MSM_OK || (r = f.after_user(user_stream)) != MSM_OK) return r;
     const uint32_t* d_sc = scalars;
     const uint32_t* d_ix = indices;
     uint32_t* d_out = points;
     if (host) {
-      if ((r = s0.ws.wire_pts.ensure(m * sw * 4)) != MSM_OK || (indices && (r = s0.ws.sub_idx.ensure(m * 4)) != MSM_OK))
-        return done(r);
-      auto whole = [](size_t, size_t) { return MSM_OK; };
-      if ((r = upload(c, s0.ws.wire_pts.p, scalars, m * sw * 4, m * sw * 4, whole)) != MSM_OK) return done(r);
-      if (indices && (r = upload(c, s0.ws.sub_idx.p, indices, m * 4, m * 4, whole)) != MSM_OK) return done(r);
-      if (hipEventRecord(c->ev_chunk[0], c->copy_stream) != hipSuccess ||
-          hipStreamWaitEvent(s0.stream, c->ev_chunk[0], 0) != hipSuccess)
-        return done(MSM_ERR_HIP);
+      if ((r = upload_words(c, {{&s0.ws.wire_pts, scalars, m * sw * 4}, {&s0.ws.sub_idx, indices, m * 4}})) != MSM_OK)
+        return f.done(r);
       d_sc = s0.ws.wire_pts.as<uint32_t>();
       if (indices) d_ix = s0.ws.sub_idx.as<uint32_t>();
     }
-    if (host || created) {
-      if ((r = s0.ws.dx_pts.ensure(m * (created ? 64 : 128))) != MSM_OK) return done(r);
-      d_out = s0.ws.dx_pts.as<uint32_t>();
-    }
+    if ((r = point_call_output(s0, host, created, m, &d_out)) != MSM_OK) return f.done(r);
     hipLaunchKernelGGL(k_scale_points, dim3(grid_for(m, SC_THREADS)), dim3(SC_THREADS), 0, s0.stream,
                        b->rec.as<uint32_t>(), (uint32_t)b->n, (uint32_t)first, d_ix, d_sc, (uint32_t)sw, bits, d_out,
-                       (uint32_t)m, created ? 0u : 1u, errp);
-    if (created) {
-      const uint32_t nt = prep_nt((size_t)nb->levels * m);
-      launch_prepare(d_out, nb->rec.as<uint32_t>(), (uint32_t)m, errp, nt, s0.stream, PT_FMT_XY);
-      launch_shift_levels(*nb, nt, s0.stream);
-    }
-    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
-    uint32_t e[4] = {};
-    if ((host && !created && hipMemcpyAsync(points, d_out, m * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
-        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
-        hipStreamSynchronize(s0.stream) != hipSuccess)
-      return done(MSM_ERR_HIP);
-    if (e[0] & (MSM_DEV_ERR_BAD_INDEX | MSM_DEV_ERR_SCALAR_RANGE)) return done(MSM_ERR_INVALID_ARG);
-    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
-    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
-    return done(MSM_OK);
+                       (uint32_t)m, created ? 0u : 1u, f.errp());
+    if (created) launch_created(*nb, d_out, m, f.errp(), s0.stream);
+    return f.finish(host && !created ? points : nullptr, d_out, m);
   });
   if (rc != MSM_OK || !created) return rc;
   return register_bases(nb, created);

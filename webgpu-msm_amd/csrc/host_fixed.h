@@ -91,51 +91,18 @@ int fixed_create(const msm_bases* h, const msm_subset_t* sub, uint32_t w, uint32
     if (!b->alive) return MSM_ERR_INVALID_ARG;  // destroyed, or the library shut down, meanwhile
     t->device = c->device;
     Slot& s0 = c->slot[0];
-    Buf errb;  // the preparation's error word
-    int r = errb.ensure(16);
+    PointCall f;  // (no caller's stream to order after)
+    int r = f.begin(c, &t->rec, fp.bytes);
     if (r != MSM_OK) return r;
-    if ((r = t->rec.ensure(fp.bytes)) != MSM_OK) {
-      errb.release();
-      return r;
-    }
-    auto done = [&](int code) {  // as create_bases'
-      drain_streams(c, 1, code);
-      if (errb.base) {
-        std::lock_guard<std::mutex> gl(g_guard_mu);
-        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
-      }
-      errb.release();
-      if (code != MSM_OK) t->rec.release();
-      return code;
-    };
-    uint32_t* errp = errb.as<uint32_t>();
-    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
-    if ((r = s0.ws.dx_pts.ensure(fp.records * 64)) != MSM_OK) return done(r);
+    if ((r = s0.ws.dx_pts.ensure(fp.records * 64)) != MSM_OK) return f.done(r);
     uint32_t* xy = s0.ws.dx_pts.as<uint32_t>();
     hipLaunchKernelGGL(k_fixed_build, dim3(grid_for(fp.records, FX_THREADS)), dim3(FX_THREADS), 0, s0.stream,
                        b->rec.as<uint32_t>(), bi, fp.w, fp.Wn, xy, (uint32_t)fp.records);
-    launch_prepare(xy, t->rec.as<uint32_t>(), (uint32_t)fp.records, errp, 0u, s0.stream, PT_FMT_XY);
-    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
-    uint32_t e[4] = {};
-    if (hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
-        hipStreamSynchronize(s0.stream) != hipSuccess)
-      return done(MSM_ERR_HIP);
-    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
-    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
-    return done(MSM_OK);
+    launch_prepare(xy, t->rec.as<uint32_t>(), (uint32_t)fp.records, f.errp(), 0u, s0.stream, PT_FMT_XY);
+    return f.finish();
   });
   if (rc != MSM_OK) return rc;
-  t->alive = true;
-  std::lock_guard<std::mutex> lk(g_mu);
-  // msm_shutdown may have run since the records were made (it frees only registered tables)
-  if ((int)g_ctx.size() <= t->device || !g_ctx[t->device]) {
-    t->rec.release();
-    return MSM_ERR_INVALID_ARG;
-  }
-  const uintptr_t id = g_bases_next++;
-  g_fixed[id] = t;
-  *out = reinterpret_cast<msm_fixed*>(id);
-  return MSM_OK;
+  return register_handle(g_fixed, t, true, out);
 }
 
 // The device buffer k_fixed_eval leaves its points in: whole blocks of 64.
@@ -166,11 +133,7 @@ int fixed_mul(const msm_fixed* h, const uint32_t* scalars, size_t m, bool host, 
   if (created)
     if (int rc = bases_shape(nb.get(), m, levels, wb)) return rc;
   const size_t ksw = t->k * sw;
-  if (!host && m) {  // alignment and overlap, from the pointer values
-    const uintptr_t sp = reinterpret_cast<uintptr_t>(scalars), pp = reinterpret_cast<uintptr_t>(points);
-    if (sp & (sw == 8 ? 15u : 3u)) return MSM_ERR_INVALID_ARG;
-    if (!created && ((pp & 15u) || (pp < sp + m * ksw * 4 && sp < pp + m * 128))) return MSM_ERR_INVALID_ARG;
-  }
+  if (!host && m && !point_call_ptrs_ok(scalars, sw, ksw, m, created ? nullptr : points)) return MSM_ERR_INVALID_ARG;
   if (host && width < 32 * sw) {  // every scalar, before anything is uploaded or enqueued
     const size_t wi = sw - 1 - ((width - 1) >> 5);  // the word that holds bit width - 1
     const uint32_t excess = (width & 31u) ? ~((1u << (width & 31u)) - 1u) : 0u;
@@ -190,62 +153,24 @@ int fixed_mul(const msm_fixed* h, const uint32_t* scalars, size_t m, bool host, 
     if (created)
       if (int prc = bases_plan_exists(c, *nb, wb)) return prc;
     Slot& s0 = c->slot[0];
-    Buf errb;
-    int r = errb.ensure(16);
-    if (r != MSM_OK) return r;
-    if (created && (r = nb->rec.ensure((size_t)nb->levels * m * PRE_WORDS * 4)) != MSM_OK) {
-      errb.release();
-      return r;
-    }
-    auto done = [&](int code) {  // as create_bases'
-      drain_streams(c, 1, code);
-      if (errb.base) {
-        std::lock_guard<std::mutex> gl(g_guard_mu);
-        (void)guard_scan(errb, guard_id("bases_prep_err"), c->device, -1, &g_guard_pending);
-      }
-      errb.release();
-      if (code != MSM_OK) nb->rec.release();
-      return code;
-    };
-    uint32_t* errp = errb.as<uint32_t>();
-    if (hipMemsetAsync(errp, 0, 16, s0.stream) != hipSuccess) return done(MSM_ERR_HIP);
-    if ((r = order_after_user(c, user_stream, 1)) != MSM_OK) return done(r);
+    PointCall f;
+    int r = f.begin(c, created ? &nb->rec : nullptr, (size_t)nb->levels * m * PRE_WORDS * 4);
+    if (r != MSM_OK || (r = f.after_user(user_stream)) != MSM_OK) return r;
     const uint32_t* d_sc = scalars;
     uint32_t* d_out = points;
     if (host) {
-      if ((r = s0.ws.wire_pts.ensure(m * ksw * 4)) != MSM_OK) return done(r);
-      auto whole = [](size_t, size_t) { return MSM_OK; };
-      if ((r = upload(c, s0.ws.wire_pts.p, scalars, m * ksw * 4, m * ksw * 4, whole)) != MSM_OK) return done(r);
-      if (hipEventRecord(c->ev_chunk[0], c->copy_stream) != hipSuccess ||
-          hipStreamWaitEvent(s0.stream, c->ev_chunk[0], 0) != hipSuccess)
-        return done(MSM_ERR_HIP);
+      if ((r = upload_words(c, {{&s0.ws.wire_pts, scalars, m * ksw * 4}})) != MSM_OK) return f.done(r);
       d_sc = s0.ws.wire_pts.as<uint32_t>();
     }
-    if (host || created) {
-      if ((r = s0.ws.dx_pts.ensure(m * (created ? 64 : 128))) != MSM_OK) return done(r);
-      d_out = s0.ws.dx_pts.as<uint32_t>();
-    }
-    if ((r = s0.ws.fx_proj.ensure(fixed_proj_bytes(m))) != MSM_OK) return done(r);
+    if ((r = point_call_output(s0, host, created, m, &d_out)) != MSM_OK) return f.done(r);
+    if ((r = s0.ws.fx_proj.ensure(fixed_proj_bytes(m))) != MSM_OK) return f.done(r);
     uint32_t* proj = s0.ws.fx_proj.as<uint32_t>();
     hipLaunchKernelGGL(k_fixed_eval, dim3(grid_for(m, FX_THREADS)), dim3(FX_THREADS), FX_THREADS * ksw * 4, s0.stream,
-                       t->rec.as<uint32_t>(), t->k, t->w, t->Wn, d_sc, (uint32_t)sw, width, proj, (uint32_t)m, errp);
+                       t->rec.as<uint32_t>(), t->k, t->w, t->Wn, d_sc, (uint32_t)sw, width, proj, (uint32_t)m, f.errp());
     hipLaunchKernelGGL(k_fixed_normalise, dim3(grid_for(m, FX_THREADS * FX_NORM_E)), dim3(FX_THREADS), 0, s0.stream,
                        proj, d_out, (uint32_t)m, created ? 0u : 1u);
-    if (created) {
-      const uint32_t nt = prep_nt((size_t)nb->levels * m);
-      launch_prepare(d_out, nb->rec.as<uint32_t>(), (uint32_t)m, errp, nt, s0.stream, PT_FMT_XY);
-      launch_shift_levels(*nb, nt, s0.stream);
-    }
-    if (hipGetLastError() != hipSuccess) return done(MSM_ERR_HIP);
-    uint32_t e[4] = {};
-    if ((host && !created && hipMemcpyAsync(points, d_out, m * 128, hipMemcpyDeviceToHost, s0.stream) != hipSuccess) ||
-        hipMemcpyAsync(e, errp, 16, hipMemcpyDeviceToHost, s0.stream) != hipSuccess ||
-        hipStreamSynchronize(s0.stream) != hipSuccess)
-      return done(MSM_ERR_HIP);
-    if (e[0] & MSM_DEV_ERR_SCALAR_RANGE) return done(MSM_ERR_INVALID_ARG);
-    if (e[0] & MSM_DEV_ERR_COORD_RANGE) return done(MSM_ERR_COORD_RANGE);
-    if (e[0] & MSM_DEV_ERR_BAD_POINT) return done(MSM_ERR_BAD_POINT);
-    return done(MSM_OK);
+    if (created) launch_created(*nb, d_out, m, f.errp(), s0.stream);
+    return f.finish(host && !created ? points : nullptr, d_out, m);
   });
   if (rc != MSM_OK || !created) return rc;
   return register_bases(nb, created);

@@ -114,6 +114,154 @@ __host__ __device__ constexpr uint32_t pt_fmt_slots(uint32_t fmt) {  // 16-B slo
   return fmt == PT_FMT_XY ? 4u : fmt == PT_FMT_XYZ ? 6u : 8u;
 }
 
+// ---- the lane frame: what the per-lane point kernels (one lane = one point) share ---------------
+// A workgroup of T lanes (PP_THREADS, or one wave of 64) owns a staging array of 8 T 16-byte slots,
+// record i in slots pp_slot(i, 0 .. 7).  `np` is the number of the block's live records or points.
+//
+// The block's np prepared records (128 B each, `in` = the first one) into the staging array: coalesced
+// 16-byte loads.  A barrier comes before lane_read_record.
+template <uint32_t T>
+__device__ __forceinline__ void lane_stage_records(uint4* st, const uint4* in, uint32_t np) {
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * T + threadIdx.x;  // 16-B slot within the block's records
+    if (g < np * 8) st[pp_slot(g >> 3, g & 7)] = in[g];
+  }
+}
+// Lane i's record out of its slots.  A lane past the block's last record works on zeros (x = y = 0:
+// every doubling, addition and the inversion stay 0) and nothing of its is written back.
+__device__ __forceinline__ void lane_read_record(const uint4* st, uint32_t i, bool live, uint32_t (&rec)[32]) {
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) {
+    const uint4 v = live ? st[pp_slot(i, q)] : make_uint4(0u, 0u, 0u, 0u);
+    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+  }
+}
+// Record `idx` of `recs` straight from HBM, a 128-byte gather per lane; zeros for a dead lane.
+__device__ __forceinline__ void lane_gather_record(const uint32_t* __restrict__ recs, size_t idx, bool live,
+                                                   uint32_t (&rec)[32]) {
+  const uint4* in = reinterpret_cast<const uint4*>(recs) + idx * 8;
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) {
+    const uint4 v = live ? in[q] : make_uint4(0u, 0u, 0u, 0u);
+    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+  }
+}
+// The extended point (X : Y : T : Z) = (x : y : x y : 1) of a halved record, every coordinate an
+// fe_mul output as pt_dbl's and pt_add's bound proofs take them.  (y-x)/2 may reach 10p with a top
+// limb above K8P's, so it goes through one multiply by R (value kept, < 2p) before it is subtracted.
+__device__ __forceinline__ xyzt pt_from_record(const uint32_t (&rec)[32]) {
+  fe ymx, ypx;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    ymx.v[k] = rec[k];
+    ypx.v[k] = rec[PRE_HALF + k];
+  }
+  const fe one = fe_one();
+  const fe a = fe_mul(ymx, one);   // (y-x)/2, N_MUL
+  const fe xs = fe_sub(ypx, a);    // x + 8p: normalised, < 12p
+  const fe ys = fe_add_n(ypx, a);  // y: normalised, < 6p
+  xyzt p;
+  p.X = fe_mul(xs, one);
+  p.Y = fe_mul(ys, one);
+  p.T = fe_mul(xs, ys);            // 72 p^2 < p R
+  p.Z = one;
+  return p;
+}
+// The halved record (ec.cuh pt_madd; layout: msm_dev.h PRE_WORDS) of the affine point whose x/2 and
+// y/2 are `x` and `y`, Montgomery form, fe_mul outputs (N_MUL).  Limb forms written, which
+// tests/test_limb_bounds.py test_madd_bounds proves for pt_madd's record operand: (y-x)/2 =
+// fe_sub(N_MUL, N_MUL) (normalised, < 10p), (y+x)/2 = fe_norm(fe_add(N_MUL, N_MUL)) (normalised,
+// < 4p) and d t = fe_mul_d of an fe_mul output (normalised, < 2p: N_MUL).
+__device__ __forceinline__ void record_from_halved(const fe& x, const fe& y, uint32_t (&rec)[32]) {
+  // d x y: (2 (x/2)) (2 (y/2)) = x y in Montgomery form (S x S operands), then d by limb scaling
+  const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
+  const fe ymx = fe_sub(y, x);
+  const fe ypx = fe_add_n(y, x);
+#pragma unroll
+  for (int k = 0; k < 32; k++) rec[k] = 0;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    rec[k] = ymx.v[k];
+    rec[PRE_HALF + k] = ypx.v[k];
+  }
+#pragma unroll
+  for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
+  // each half also carries d*t's top limb and the OTHER half's top limb: the half read first
+  // supplies both, so the half read second needs only its eight low limbs (seven loads in all)
+  rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
+  rec[NL + 1] = ypx.v[NL - 1];
+  rec[PRE_HALF + NL + 1] = ymx.v[NL - 1];
+}
+// Lane i's record into its slots, and the block's np records out to `dst` (the first one's place) in
+// coalesced 16-byte stores, nontemporal with `nt`.  A barrier goes between the two.
+__device__ __forceinline__ void lane_put_record(uint4* st, uint32_t i, const uint32_t (&rec)[32]) {
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++)
+    st[pp_slot(i, q)] = make_uint4(rec[4 * q], rec[4 * q + 1], rec[4 * q + 2], rec[4 * q + 3]);
+}
+template <uint32_t T>
+__device__ __forceinline__ void lane_flush_records(const uint4* st, uint4* dst, uint32_t np, uint32_t nt) {
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * T + threadIdx.x;
+    if (g < np * 8) {
+      const uint4 v = st[pp_slot(g >> 3, g & 7)];
+      if (nt) {
+        const pp_v4 w = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(w, reinterpret_cast<pp_v4*>(dst + g));
+      } else {
+        dst[g] = v;
+      }
+    }
+  }
+}
+// Lane i's point as the canonical big-endian record x | y | t | z = 1 in its slots: from little-endian
+// words, or from the affine Montgomery (x, y) with t = x y.
+__device__ __forceinline__ void lane_stage_words(uint4* st, uint32_t i, const uint32_t (&xw)[8],
+                                                 const uint32_t (&yw)[8], const uint32_t (&tw)[8]) {
+  // big-endian word order: word 0 is the most significant 32 bits
+  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
+  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
+  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
+  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
+  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
+  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
+  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
+  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+}
+__device__ __forceinline__ void lane_stage_affine(uint4* st, uint32_t i, const fe& x, const fe& y) {
+  uint32_t xw[8], yw[8], tw[8];
+  fe_to_words_le(fe_to_std(x), xw);
+  fe_to_words_le(fe_to_std(y), yw);
+  fe_to_words_le(fe_to_std(fe_mul(x, y)), tw);
+  lane_stage_words(st, i, xw, yw, tw);
+}
+// A staged block's first np points out to `out`, block at point p0: 128-byte wire records (wire = 1)
+// or the 64-byte x | y that k_prepare_points(PT_FMT_XY) reads (wire = 0), coalesced 16-byte stores.
+template <uint32_t T>
+__device__ __forceinline__ void lane_flush_points(const uint4* st, uint32_t* __restrict__ out, size_t p0, uint32_t np,
+                                                  uint32_t wire) {
+  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
+  uint4* dst = reinterpret_cast<uint4*>(out) + (p0 << sh);
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint32_t g = j * T + threadIdx.x;
+    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
+  }
+}
+// `total` scalar words of the vector `scalars`, from word `w0` on (a multiple of 64 words), into LDS:
+// 16-byte loads where the vector is 16-byte aligned, word by word where it is not.
+template <uint32_t T>
+__device__ __forceinline__ void lane_stage_scalars(uint4* ssc4, const uint32_t* __restrict__ scalars, size_t w0,
+                                                   uint32_t total) {
+  uint32_t* ssc = reinterpret_cast<uint32_t*>(ssc4);
+  const uint32_t* sp = scalars + w0;
+  const uint32_t nv = (reinterpret_cast<uintptr_t>(scalars) & 15u) ? 0u : total >> 2;
+  for (uint32_t g = threadIdx.x; g < nv; g += T) ssc4[g] = reinterpret_cast<const uint4*>(sp)[g];
+  for (uint32_t g = (nv << 2) + threadIdx.x; g < total; g += T) ssc[g] = sp[g];
+}
+
 // blockIdx.y = MSM of the batch: its wire points come from wires.p[y], its records go to
 // pts[y n ..).
 extern "C" __global__ void __launch_bounds__(PP_THREADS) k_prepare_points(BatchPtrs wires,
@@ -186,25 +334,10 @@ extern "C" __global__ void __launch_bounds__(PP_THREADS) k_prepare_points(BatchP
     x = fe_mul(fe_to_mont(fe_from_words_le(xw)), zh);
     y = fe_mul(fe_to_mont(fe_from_words_le(yw)), zh);
   }
-  // d x y: (2 (x/2)) (2 (y/2)) = x y in Montgomery form (S x S operands), then d by limb scaling
-  const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
-  fe ymx = fe_sub(y, x);
-  fe ypx = fe_add_n(y, x);
-  uint32_t rec[32];  // layout: msm_dev.h PRE_WORDS
-#pragma unroll
-  for (int k = 0; k < 32; k++) rec[k] = 0;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    rec[k] = ymx.v[k];
-    rec[PRE_HALF + k] = ypx.v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
-  // each half also carries d*t's top limb and the OTHER half's top limb: the half read first
-  // supplies both, so the half read second needs only its eight low limbs (seven loads in all)
-  rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
-  rec[NL + 1] = ypx.v[NL - 1];
-  rec[PRE_HALF + NL + 1] = ymx.v[NL - 1];
+  uint32_t rec[32];
+  record_from_halved(x, y, rec);
+  // lane_put_record and lane_flush_records, written out: through the helpers this kernel, which every
+  // MSM runs, compiles to a dozen instructions more (the input stage above is its own as well)
 #pragma unroll
   for (uint32_t q = 0; q < 8; q++)
     st[pp_slot(i, q)] = make_uint4(rec[4 * q], rec[4 * q + 1], rec[4 * q + 2], rec[4 * q + 3]);
@@ -250,97 +383,33 @@ extern "C" __global__ void __launch_bounds__(256) k_pad_identity(uint32_t* __res
 // resident prepared bases (msm_bases_*): shifted levels and the scalar cut
 // ---------------------------------------------------------------------------------------------
 // Level j + 1 of a handle's records from level j: record i of `src` (the halved affine form of
-// Q_i = 2^(jS) P_i) -> record i of `dst` for 2^S Q_i.  One workgroup = PP_THREADS records, moved
-// between HBM and LDS exactly as k_prepare_points moves them (coalesced 16-B accesses, slots
-// XOR-swizzled by the record index); each lane rebuilds its extended point, doubles it S times
-// (pt_dbl, complete: the identity, the order-2 point (0, -1) and the order-4 points with y = 0
-// need no branch), and normalises with one fe_inv (~260 of the lane's 8 S + ~270 multiplies).
+// Q_i = 2^(jS) P_i) -> record i of `dst` for 2^S Q_i.  One workgroup = PP_THREADS records, in and
+// out through the lane frame (lane_stage_records .. lane_flush_records); each lane rebuilds its
+// extended point (pt_from_record), doubles it S times (pt_dbl, complete: the identity, the order-2
+// point (0, -1) and the order-4 points with y = 0 need no branch), and normalises with one fe_inv
+// (~260 of the lane's 8 S + ~270 multiplies) into record_from_halved's operands.
 // Results are specified for on-curve points (Z of a multiple is then never 0).
-// Limb forms written -- the ones k_prepare_points writes, which tests/test_limb_bounds.py
-// test_madd_bounds proves for pt_madd's record operand: x and y below are fe_mul outputs (N_MUL),
-// so (y-x)/2 = fe_sub(N_MUL, N_MUL) (normalised, < 10p), (y+x)/2 = fe_norm(fe_add(N_MUL, N_MUL))
-// (normalised, < 4p) and d t = fe_mul_d of an fe_mul output (normalised, < 2p: N_MUL).
 extern "C" __global__ void __launch_bounds__(PP_THREADS) k_shift_bases(const uint32_t* __restrict__ src,
                                                                        uint32_t* __restrict__ dst, uint32_t n,
                                                                        uint32_t S, uint32_t nt) {
   __shared__ uint4 st[PP_THREADS * 8];
   const uint32_t p0 = blockIdx.x * PP_THREADS;
   const uint32_t np = min(PP_THREADS, n - p0);
-  const uint4* in = reinterpret_cast<const uint4*>(src) + (size_t)p0 * 8;
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t g = j * PP_THREADS + threadIdx.x;
-    if (g < np * 8) st[pp_slot(g >> 3, g & 7)] = in[g];
-  }
+  lane_stage_records<PP_THREADS>(st, reinterpret_cast<const uint4*>(src) + (size_t)p0 * 8, np);
   __syncthreads();
   const uint32_t i = threadIdx.x;
   uint32_t rec[32];
-#pragma unroll
-  for (uint32_t q = 0; q < 8; q++) {
-    // lanes past the block's last record work on zeros (x = y = 0: every doubling and the
-    // inversion stay 0) and nothing of theirs is written back
-    const uint4 v = i < np ? st[pp_slot(i, q)] : make_uint4(0u, 0u, 0u, 0u);
-    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
-  }
+  lane_read_record(st, i, i < np, rec);
   __syncthreads();
-  fe ymx, ypx;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    ymx.v[k] = rec[k];
-    ypx.v[k] = rec[PRE_HALF + k];
-  }
-  // The extended point (X : Y : T : Z) = (x : y : x y : 1), every coordinate an fe_mul output as
-  // pt_dbl's bound proof takes them.  (y-x)/2 may reach 10p with a top limb above K8P's, so it
-  // goes through one multiply by R (value kept, < 2p) before it is subtracted.
-  const fe one = fe_one();
-  const fe a = fe_mul(ymx, one);        // (y-x)/2, N_MUL
-  const fe xs = fe_sub(ypx, a);         // x + 8p: normalised, < 12p
-  const fe ys = fe_add_n(ypx, a);       // y: normalised, < 6p
-  xyzt p;
-  p.X = fe_mul(xs, one);
-  p.Y = fe_mul(ys, one);
-  p.T = fe_mul(xs, ys);                 // 72 p^2 < p R
-  p.Z = one;
+  xyzt p = pt_from_record(rec);
 #pragma unroll 1
   for (uint32_t s = 0; s < S; s++) p = pt_dbl(p);
-  // halved affine record, as k_prepare_points' projective branch writes it
+  // x/2 and y/2, as k_prepare_points' projective branch makes them
   const fe zh = fe_mul(fe_inv(p.Z), fe_const(HALF29));
-  const fe x = fe_mul(p.X, zh);
-  const fe y = fe_mul(p.Y, zh);
-  const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
-  const fe o_ymx = fe_sub(y, x);
-  const fe o_ypx = fe_add_n(y, x);
-#pragma unroll
-  for (int k = 0; k < 32; k++) rec[k] = 0;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    rec[k] = o_ymx.v[k];
-    rec[PRE_HALF + k] = o_ypx.v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
-  // the duplicated top limbs (msm_dev.h PRE_WORDS)
-  rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
-  rec[NL + 1] = o_ypx.v[NL - 1];
-  rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1];
-#pragma unroll
-  for (uint32_t q = 0; q < 8; q++)
-    st[pp_slot(i, q)] = make_uint4(rec[4 * q], rec[4 * q + 1], rec[4 * q + 2], rec[4 * q + 3]);
+  record_from_halved(fe_mul(p.X, zh), fe_mul(p.Y, zh), rec);
+  lane_put_record(st, i, rec);
   __syncthreads();
-  uint4* out = reinterpret_cast<uint4*>(dst) + (size_t)p0 * 8;
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t g = j * PP_THREADS + threadIdx.x;
-    if (g < np * 8) {
-      const uint4 v = st[pp_slot(g >> 3, g & 7)];
-      if (nt) {
-        const pp_v4 w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<pp_v4*>(out + g));
-      } else {
-        out[g] = v;
-      }
-    }
-  }
+  lane_flush_records<PP_THREADS>(st, reinterpret_cast<uint4*>(dst) + (size_t)p0 * 8, np, nt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -461,8 +530,7 @@ __device__ inline xyzt pt_mul_order(const xyzt& p) {
 // Compressed points -> affine points: x (8 big-endian words, msm.h MSM_POINTS_X_*) to the 64-byte
 // x|y that k_prepare_points(PT_FMT_XY) reads, or with `wire` to a whole 128-byte record
 // (t = x y, z = 1).  One lane per point; a wave's 2 KiB of input arrives with two 16-byte loads per
-// lane, and the output goes through LDS (slots swizzled as k_prepare_points') to leave in coalesced
-// 16-byte stores.
+// lane, and the output leaves through the lane frame (lane_stage_words, lane_flush_points).
 //   y^2 = (a x^2 - 1) / (d x^2 - 1) = (x^2 + 1) / (1 - d x^2)       (a = -1)
 // The denominator is never 0: d = 3021 is a non-residue, so d x^2 = 1 has no solution.
 // form 1 (subgroup): y is the root with [r](x, y) = O.  (x, -y) = -(x, y) + (0, -1) and r is odd, so
@@ -551,23 +619,9 @@ extern "C" __global__ void __launch_bounds__(DX_THREADS, 2) k_decompress_x(const
   uint32_t yw[8], tw[8];
   fe_to_words_le(ys, yw);
   fe_to_words_le(ts, tw);
-  // big-endian word order: word 0 is the most significant 32 bits
-  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
-  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
-  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
-  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
-  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
-  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
-  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
-  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+  lane_stage_words(st, i, xw, yw, tw);
   __syncthreads();
-  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
-  uint4* dst = reinterpret_cast<uint4*>(out) + ((size_t)p0 << sh);
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t g = j * DX_THREADS + threadIdx.x;
-    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
-  }
+  lane_flush_points<DX_THREADS>(st, out, p0, np, wire);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -594,20 +648,17 @@ __host__ __device__ inline uint32_t scale_digit(const uint32_t* s_be, uint32_t s
 // per SIMD as k_decompress_x (225 VGPRs, no scratch: the table and the accumulator are 144 of them).
 // The plain double-and-add with a selected add was measured beside this ladder and lost by a quarter
 // (DESIGN.md §9).
-//   records  range form: the workgroup's 8 KiB arrive coalesced through LDS, as k_shift_bases reads
-//            them; indexed form: a 128-byte gather per lane.  An index >= n is replaced by 0 and
-//            raises MSM_DEV_ERR_BAD_INDEX.  The extended point is rebuilt as k_shift_bases rebuilds
-//            it: every coordinate an fe_mul output, which pt_dbl's and pt_add's bound proofs take.
+//   records  range form: the workgroup's 8 KiB arrive through the lane frame (lane_stage_records,
+//            lane_read_record); indexed form: lane_gather_record.  An index >= n is replaced by 0 and
+//            raises MSM_DEV_ERR_BAD_INDEX.  pt_from_record rebuilds the extended point.
 //   scalars  sw big-endian words each (the full integer: nothing is reduced mod r), the workgroup's
-//            64 sw words staged in LDS with 16-byte loads where the vector is 16-byte aligned, word by
-//            word where it is not.  A bit at or above b is masked (scale_digit) and raises
-//            MSM_DEV_ERR_SCALAR_RANGE.
+//            64 sw words staged in LDS (lane_stage_scalars).  A bit at or above b is masked
+//            (scale_digit) and raises MSM_DEV_ERR_SCALAR_RANGE.
 //   ladder   scale_windows(b) rounds of SC_W doublings and one addition of {O, P, 2P, 3P}[digit],
 //            chosen with pt_sel: no lane takes a branch of its own, and the unified addition is
 //            complete, so the identity, the torsion points and P + P need none either.
-//   output   one fe_inv per lane, canonical standard form, x | y | t = x y | z = 1 (wire = 1: 128-byte
-//            records) or x | y (wire = 0: what k_prepare_points(PT_FMT_XY) reads), through LDS as
-//            k_decompress_x writes them.  The identity comes out as (0 : Z : 0 : Z) and is written
+//   output   one fe_inv per lane, then lane_stage_affine and lane_flush_points: wire records
+//            (wire = 1) or x | y (wire = 0).  The identity comes out as (0 : Z : 0 : Z) and is written
 //            (0, 1, 0, 1).  Results are specified for on-curve bases (Z is then never 0).
 constexpr uint32_t SC_THREADS = 64;
 extern "C" __global__ void __launch_bounds__(SC_THREADS, 2) k_scale_points(
@@ -621,13 +672,8 @@ extern "C" __global__ void __launch_bounds__(SC_THREADS, 2) k_scale_points(
   const uint32_t np = min(SC_THREADS, m - p0);
   const uint32_t i = threadIdx.x;
   const bool live = i < np;
-  {  // the workgroup's np * sw scalar words; p0 * sw * 4 is a multiple of 256 bytes
-    const uint32_t* sp = scalars + (size_t)p0 * sw;
-    const uint32_t total = np * sw;
-    const uint32_t nv = (reinterpret_cast<uintptr_t>(scalars) & 15u) ? 0u : total >> 2;
-    for (uint32_t g = i; g < nv; g += SC_THREADS) ssc4[g] = reinterpret_cast<const uint4*>(sp)[g];
-    for (uint32_t g = (nv << 2) + i; g < total; g += SC_THREADS) ssc[g] = sp[g];
-  }
+  // the workgroup's np * sw scalar words; p0 * sw * 4 is a multiple of 256 bytes
+  lane_stage_scalars<SC_THREADS>(ssc4, scalars, (size_t)p0 * sw, np * sw);
   uint32_t rec[32];
   if (indices) {
     uint32_t idx = live ? indices[p0 + i] : 0u;
@@ -635,47 +681,17 @@ extern "C" __global__ void __launch_bounds__(SC_THREADS, 2) k_scale_points(
       idx = 0;
       atomicOr(err, MSM_DEV_ERR_BAD_INDEX);
     }
-    const uint4* in = reinterpret_cast<const uint4*>(recs) + (size_t)idx * 8;
-#pragma unroll
-    for (uint32_t q = 0; q < 8; q++) {
-      const uint4 v = live ? in[q] : make_uint4(0u, 0u, 0u, 0u);
-      rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
-    }
+    lane_gather_record(recs, idx, live, rec);
     __syncthreads();
   } else {
-    const uint4* in = reinterpret_cast<const uint4*>(recs) + ((size_t)first + p0) * 8;
-#pragma unroll
-    for (uint32_t j = 0; j < 8; j++) {
-      const uint32_t g = j * SC_THREADS + threadIdx.x;
-      if (g < np * 8) st[pp_slot(g >> 3, g & 7)] = in[g];
-    }
+    lane_stage_records<SC_THREADS>(st, reinterpret_cast<const uint4*>(recs) + ((size_t)first + p0) * 8, np);
     __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < 8; q++) {
-      // lanes past the block's last point work on zeros, as k_shift_bases', and write nothing
-      const uint4 v = live ? st[pp_slot(i, q)] : make_uint4(0u, 0u, 0u, 0u);
-      rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
-    }
+    lane_read_record(st, i, live, rec);
   }
   const uint32_t* my = ssc + i * sw;
   const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
   if (live && (my[0] & ~top_mask)) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
-  fe ymx, ypx;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    ymx.v[k] = rec[k];
-    ypx.v[k] = rec[PRE_HALF + k];
-  }
-  // (X : Y : T : Z) = (x : y : x y : 1) from the halved record, limb forms as in k_shift_bases
-  const fe one = fe_one();
-  const fe a = fe_mul(ymx, one);   // (y-x)/2, N_MUL
-  const fe xs = fe_sub(ypx, a);    // x + 8p: normalised, < 12p
-  const fe ys = fe_add_n(ypx, a);  // y: normalised, < 6p
-  xyzt p1;
-  p1.X = fe_mul(xs, one);
-  p1.Y = fe_mul(ys, one);
-  p1.T = fe_mul(xs, ys);
-  p1.Z = one;
+  const xyzt p1 = pt_from_record(rec);
   xyzt acc = pt_identity();
   const xyzt p2 = pt_dbl(p1);
   const xyzt p3 = pt_add(p2, p1);
@@ -690,28 +706,10 @@ extern "C" __global__ void __launch_bounds__(SC_THREADS, 2) k_scale_points(
   const fe zi = fe_inv(acc.Z);
   const fe x = fe_mul(acc.X, zi);
   const fe y = fe_mul(acc.Y, zi);
-  uint32_t xw[8], yw[8], tw[8];
-  fe_to_words_le(fe_to_std(x), xw);
-  fe_to_words_le(fe_to_std(y), yw);
-  fe_to_words_le(fe_to_std(fe_mul(x, y)), tw);
   __syncthreads();
-  // big-endian word order: word 0 is the most significant 32 bits
-  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
-  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
-  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
-  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
-  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
-  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
-  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
-  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
+  lane_stage_affine(st, i, x, y);
   __syncthreads();
-  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
-  uint4* dst = reinterpret_cast<uint4*>(out) + ((size_t)p0 << sh);
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t g = j * SC_THREADS + threadIdx.x;
-    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
-  }
+  lane_flush_points<SC_THREADS>(st, out, p0, np, wire);
 }
 
 // The virtual scalars of a folded launch (levels = k > 1): out[m][j n + i] = bits [j S, (j+1) S)
@@ -817,64 +815,14 @@ struct FixedBaseIdx {  // the table's bases as records of the source handle (ker
   uint32_t v[FX_MAX_BASES];
 };
 
-// The extended point (x : y : x y : 1) of a halved record, every coordinate an fe_mul output: what
-// k_shift_bases and k_scale_points rebuild, limb forms as there.
-__device__ __forceinline__ xyzt pt_from_record(const uint32_t (&rec)[32]) {
-  fe ymx, ypx;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    ymx.v[k] = rec[k];
-    ypx.v[k] = rec[PRE_HALF + k];
-  }
-  const fe one = fe_one();
-  const fe a = fe_mul(ymx, one);   // (y-x)/2, N_MUL
-  const fe xs = fe_sub(ypx, a);    // x + 8p: normalised, < 12p
-  const fe ys = fe_add_n(ypx, a);  // y: normalised, < 6p
-  xyzt p;
-  p.X = fe_mul(xs, one);
-  p.Y = fe_mul(ys, one);
-  p.T = fe_mul(xs, ys);
-  p.Z = one;
-  return p;
-}
-
-// Lane i's affine point (Montgomery x, y) as the canonical big-endian record x | y | t = x y | z = 1 in
-// the swizzled slots of `st`, and a staged block's first np points out to `out` (wire = 1: 128-byte
-// records; wire = 0: x | y, what k_prepare_points(PT_FMT_XY) reads) with coalesced 16-byte stores:
-// k_scale_points' output path.
-__device__ __forceinline__ void fx_stage_affine(uint4* st, uint32_t i, const fe& x, const fe& y) {
-  uint32_t xw[8], yw[8], tw[8];
-  fe_to_words_le(fe_to_std(x), xw);
-  fe_to_words_le(fe_to_std(y), yw);
-  fe_to_words_le(fe_to_std(fe_mul(x, y)), tw);
-  // big-endian word order: word 0 is the most significant 32 bits
-  st[pp_slot(i, 0)] = make_uint4(xw[7], xw[6], xw[5], xw[4]);
-  st[pp_slot(i, 1)] = make_uint4(xw[3], xw[2], xw[1], xw[0]);
-  st[pp_slot(i, 2)] = make_uint4(yw[7], yw[6], yw[5], yw[4]);
-  st[pp_slot(i, 3)] = make_uint4(yw[3], yw[2], yw[1], yw[0]);
-  st[pp_slot(i, 4)] = make_uint4(tw[7], tw[6], tw[5], tw[4]);
-  st[pp_slot(i, 5)] = make_uint4(tw[3], tw[2], tw[1], tw[0]);
-  st[pp_slot(i, 6)] = make_uint4(0u, 0u, 0u, 0u);
-  st[pp_slot(i, 7)] = make_uint4(0u, 0u, 0u, 1u);
-}
-__device__ __forceinline__ void fx_flush_staged(const uint4* st, uint32_t* __restrict__ out, size_t p0, uint32_t np,
-                                                uint32_t wire) {
-  const uint32_t sh = wire ? 3u : 2u;  // 16-byte slots per output point: 8 or 4
-  uint4* dst = reinterpret_cast<uint4*>(out) + (p0 << sh);
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t g = j * FX_THREADS + threadIdx.x;
-    if (g < (np << sh)) dst[g] = st[pp_slot(g >> sh, g & ((1u << sh) - 1u))];
-  }
-}
-
 // The table's points, one lane per entry e < total = k Wn 2^(w-1): e = (j Wn + win) 2^(w-1) + d - 1
 // gives d 2^(w win) B_j, B_j record bases.v[j] of `recs` (a handle's level 0; every index was checked
-// on the host).  The lane rebuilds the extended point, doubles it w win times, takes the multiple d
-// with a w-round double-and-add whose addition is selected (pt_sel, complete formulas: no branch for
-// the identity or the torsion points), and normalises with its own fe_inv -- the table is built once.
-// Output: x | y canonical, through LDS as k_scale_points writes them; k_prepare_points(PT_FMT_XY)
-// makes the records, so they are msm_bases_create's records of these points.
+// on the host).  The lane gathers the record (lane_gather_record), rebuilds the extended point
+// (pt_from_record), doubles it w win times, takes the multiple d with a w-round double-and-add whose
+// addition is selected (pt_sel, complete formulas: no branch for the identity or the torsion points),
+// and normalises with its own fe_inv -- the table is built once.
+// Output: x | y canonical (lane_stage_affine, lane_flush_points); k_prepare_points(PT_FMT_XY) makes
+// the records, so they are msm_bases_create's records of these points.
 extern "C" __global__ void __launch_bounds__(FX_THREADS, 2) k_fixed_build(const uint32_t* __restrict__ recs,
                                                                         FixedBaseIdx bases, uint32_t w, uint32_t Wn,
                                                                         uint32_t* __restrict__ out_xy,
@@ -892,12 +840,7 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS, 2) k_fixed_build(const 
 #pragma unroll
   for (uint32_t q = 1; q < FX_MAX_BASES; q++) base = j == q ? bases.v[q] : base;
   uint32_t rec[32];
-  const uint4* in = reinterpret_cast<const uint4*>(recs) + (size_t)base * 8;
-#pragma unroll
-  for (uint32_t q = 0; q < 8; q++) {
-    const uint4 v = in[q];
-    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
-  }
+  lane_gather_record(recs, base, true, rec);
   xyzt p = pt_from_record(rec);
 #pragma unroll 1
   for (uint32_t s = w * win; s > 0; s--) p = pt_dbl(p);
@@ -908,17 +851,16 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS, 2) k_fixed_build(const 
     acc = pt_sel(((d >> bit) & 1u) != 0, acc, pt_add(acc, p));  // (c ? b : a)
   }
   const fe zi = fe_inv(acc.Z);
-  fx_stage_affine(st, i, fe_mul(acc.X, zi), fe_mul(acc.Y, zi));
+  lane_stage_affine(st, i, fe_mul(acc.X, zi), fe_mul(acc.Y, zi));
   __syncthreads();
-  fx_flush_staged(st, out_xy, p0, np, 0u);
+  lane_flush_points<FX_THREADS>(st, out_xy, p0, np, 0u);
 }
 
 // The evaluation: Q_i = sum_j s_ij B_j for i < m as (X : Y : Z).  One lane per output, one wave per
 // workgroup, four waves per SIMD (k_dense_units' budget and loop: the next entry is worked out beside
 // the current addition).
 //   scalars  [m][k][sw] big-endian words (the full integers: nothing is reduced mod r), the
-//            workgroup's 64 k sw words staged in LDS as k_scale_points stages them: 16-byte loads where
-//            the vector is 16-byte aligned, word by word where it is not.  A bit at or above b is
+//            workgroup's 64 k sw words staged in LDS (lane_stage_scalars).  A bit at or above b is
 //            masked (fixed_window_bits) and raises MSM_DEV_ERR_SCALAR_RANGE.
 //   digits   fixed_windows(b, w) signed digits per scalar, least significant window first (no
 //            doubling orders them); b is the call's width, at most the table's, so the windows read are
@@ -941,13 +883,8 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS, 4) k_fixed_eval(const u
   const uint32_t i = threadIdx.x;
   const bool live = i < np;
   const uint32_t ksw = k * sw;
-  {  // the workgroup's np k sw scalar words; p0 k sw 4 is a multiple of 256 bytes
-    const uint32_t* sp = scalars + (size_t)p0 * ksw;
-    const uint32_t total = np * ksw;
-    const uint32_t nv = (reinterpret_cast<uintptr_t>(scalars) & 15u) ? 0u : total >> 2;
-    for (uint32_t g = i; g < nv; g += FX_THREADS) fx_sc4[g] = reinterpret_cast<const uint4*>(sp)[g];
-    for (uint32_t g = (nv << 2) + i; g < total; g += FX_THREADS) ssc[g] = sp[g];
-  }
+  // the workgroup's np k sw scalar words; p0 k sw 4 is a multiple of 256 bytes
+  lane_stage_scalars<FX_THREADS>(fx_sc4, scalars, (size_t)p0 * ksw, np * ksw);
   __syncthreads();
   const uint32_t* my = ssc + (live ? i : 0u) * ksw;
   const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
@@ -996,8 +933,8 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS, 4) k_fixed_eval(const u
 // back gives 1 / Z_e = inv prefix_(e-1), inv <- inv Z_e.  3 (E - 1) / E multiplies per point for the
 // trick, 3 for x, y and t = x y, 3 for the canonical forms, and fe_inv's ~380 / E: ~56 at E = 8.
 // Blocks past the last one are skipped (wave-uniform); the lanes past m in the last block hold the
-// identity (Z = 1) and write nothing.  Output as k_scale_points': wire = 1 canonical wire records,
-// the identity (0, 1, 0, 1); wire = 0 x | y.  Results are specified for on-curve bases (no Z is 0).
+// identity (Z = 1) and write nothing.  Output through lane_stage_affine and lane_flush_points: wire = 1
+// canonical wire records, the identity (0, 1, 0, 1); wire = 0 x | y.  Results are specified for on-curve bases (no Z is 0).
 #ifndef MSM_FX_NORM_E
 #define MSM_FX_NORM_E 8
 #endif
@@ -1037,10 +974,10 @@ __device__ __forceinline__ void fx_norm_emit(const fe (&prefix)[FX_NORM_E], fe i
     const fe x = fe_mul(fx_load_coord(blk, 0), zi);
     const fe y = fe_mul(fx_load_coord(blk, 1), zi);
     __syncthreads();  // the previous block's stores have read st
-    fx_stage_affine(st, threadIdx.x, x, y);
+    lane_stage_affine(st, threadIdx.x, x, y);
     __syncthreads();
     const uint32_t pb = (g0 + E0) * FX_THREADS;
-    fx_flush_staged(st, out, pb, min(FX_THREADS, m - pb), wire);
+    lane_flush_points<FX_THREADS>(st, out, pb, min(FX_THREADS, m - pb), wire);
   }
   if constexpr (E0 > 0) fx_norm_emit<E0 - 1>(prefix, inv, mine, g0, nblk, st, out, m, wire);
 }
@@ -3619,9 +3556,8 @@ __global__ void k_test_limbs_gather(const uint32_t* __restrict__ pts, const uint
 
 // The functions the per-lane point kernels run (k_shift_bases, k_decompress_x, k_scale_points,
 // k_fixed_build) on raw limbs, one element per lane, 64 lanes per workgroup as those kernels have.
-// LOP_SHIFT_LANE is k_shift_bases' lane: the record's point rebuilt (pt_from_record, the very
-// statements of the kernel's prologue -- tests/test_limb_bounds.py compares the texts), doubled
-// b[i] times, and written back with the kernel's own epilogue statements (compared likewise).
+// LOP_SHIFT_LANE is k_shift_bases' lane: the record's point rebuilt (pt_from_record), doubled
+// b[i] times, and made a record again (record_from_halved) -- the functions the kernel calls.
 // Every loop is bounded whatever the operands hold: fe_sqrt_ts' m strictly decreases from 47 and
 // its inner loops stop at m, pt_mul_order runs the constant's 251 bits, fe_inv the exponent's 256,
 // and the host refuses a LOP_SHIFT_LANE count above LOP_SHIFT_MAX before it launches.
@@ -3653,26 +3589,9 @@ __global__ void __launch_bounds__(64) k_test_limbs_lane(const uint32_t* __restri
       const uint32_t S = min(b[i], LOP_SHIFT_MAX);
 #pragma unroll 1
       for (uint32_t s = 0; s < S; s++) p = pt_dbl(p);
-      // halved affine record, as k_prepare_points' projective branch writes it
+      // x/2 and y/2, as k_shift_bases makes them
       const fe zh = fe_mul(fe_inv(p.Z), fe_const(HALF29));
-      const fe x = fe_mul(p.X, zh);
-      const fe y = fe_mul(p.Y, zh);
-      const fe kt = fe_mul_d(fe_mul(fe_add(x, x), fe_add(y, y)));
-      const fe o_ymx = fe_sub(y, x);
-      const fe o_ypx = fe_add_n(y, x);
-#pragma unroll
-      for (int k = 0; k < 32; k++) rec[k] = 0;
-#pragma unroll
-      for (int k = 0; k < NL; k++) {
-        rec[k] = o_ymx.v[k];
-        rec[PRE_HALF + k] = o_ypx.v[k];
-      }
-#pragma unroll
-      for (int k = 0; k < NL - 1; k++) rec[PRE_KT + k] = kt.v[k];
-      // the duplicated top limbs (msm_dev.h PRE_WORDS)
-      rec[NL] = rec[PRE_HALF + NL] = kt.v[NL - 1];
-      rec[NL + 1] = o_ypx.v[NL - 1];
-      rec[PRE_HALF + NL + 1] = o_ymx.v[NL - 1];
+      record_from_halved(fe_mul(p.X, zh), fe_mul(p.Y, zh), rec);
 #pragma unroll
       for (int k = 0; k < 32; k++) out[(size_t)i * PRE_WORDS + k] = rec[k];
     }
