@@ -558,6 +558,66 @@ int msm_bases_scale_create(const msm_bases* bases, const msm_subset_t* subset, c
 int msm_bases_scale_create_device(const msm_bases* bases, const msm_subset_t* subset, const uint32_t* d_scalars_be,
                                   const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out);
 
+/* Pairwise combinations of bases handles: R_i = a_i * A_i +- b_i * B_i, m points out -- the other half
+ * of a folding step beside msm_bases_scale (G_i + x * G_(i+m), x^-1 * G_i + x * G_(i+m)), a key updated
+ * by a delta (P_i + Q_i) or differenced against another (P_i - Q_i), on the device, from the resident
+ * records of one handle or of two.  Three kernels serve the three forms (DESIGN.md §9 has the cost):
+ *
+ *   no scalars                R_i = A_i +- B_i                 one complete addition per point
+ *   one side has scalars      R_i = a_i * A_i +- B_i, or       msm_bases_scale's ladder on that side,
+ *                             R_i = A_i +- b_i * B_i           then one addition
+ *   both sides have scalars   R_i = a_i * A_i +- b_i * B_i     one joint ladder over {A, B, A + B}: a
+ *                                                              doubling and an addition per scalar bit
+ *
+ * and every form shares one inversion among eight outputs (k_fixed_normalise).
+ *
+ * The A_i are the m bases that `a` selects from `bases`, the B_i the m that `b` selects from b_bases
+ * (NULL: from `bases` too); each subset is read as msm_bases_scale reads one (the range form, or
+ * indices[0]; repeats allowed), its rules (msm_bases_compute_subset's) hold per side, and the two
+ * sides may mix the forms.  a.m == b.m == m.  Both handles are read at level 0 and must be on the same
+ * device (MSM_ERR_INVALID_ARG).
+ *
+ * Scalars: as msm_bases_scale's -- 8 big-endian words each, or ceil(b / 32) with MSM_FLAG_SCALAR_BITS
+ * and scalar_bits = b in 1..256, one width for both sides; the integer it is, not reduced mod r.  A
+ * NULL array means every scalar is 1.  With MSM_COMBINE_A_BROADCAST (_B_BROADCAST) the array holds one
+ * scalar that every i uses.  MSM_COMBINE_SUB subtracts the B term.  An unknown flag bit, reserved != 0,
+ * a.m != b.m, a broadcast flag on a NULL array, and the opts flags msm_bases_scale refuses give
+ * MSM_ERR_INVALID_ARG before any device work.
+ *
+ * msm_bases_combine* write m wire records x | y | t = x y | z = 1, canonical, the identity as
+ * (0, 1, 0, 1); msm_bases_combine_create* keep the points as a new handle whose level 0 is bit-identical
+ * to what msm_bases_create makes from those records (`levels`, opts->window_bits, the limits and the
+ * errors of a creation as there; a failed creation leaves *out null and nothing allocated).  m = 0: the
+ * combine entries return MSM_OK and write nothing, the create entries return an empty handle.
+ *
+ * A scalar bit at or above b, or an index >= n of its side's handle, gives MSM_ERR_INVALID_ARG: from
+ * the host entries before anything is uploaded or enqueued; from the device entries after the launch,
+ * which masks the bit or reads base 0 instead, runs to its end and never reads out of range (the output
+ * is then unspecified, a creation leaves nothing allocated, and both source handles stay usable).
+ * Device pointers: as msm_bases_scale's, for both scalar arrays and both index arrays -- d_points_be and
+ * 8-word scalars 16-byte aligned, narrow scalars and indices 4-byte aligned; the output must overlap
+ * none of them.  The device entries are ordered after the work queued on hip_stream and return when the
+ * result is complete.  A stale handle or a null argument: MSM_ERR_INVALID_ARG. */
+#define MSM_COMBINE_SUB          1u  /* R_i = a_i A_i - b_i B_i                               */
+#define MSM_COMBINE_A_BROADCAST  2u  /* a_scalars holds ONE scalar, used for every i          */
+#define MSM_COMBINE_B_BROADCAST  4u  /* likewise b_scalars                                    */
+typedef struct msm_combine_t {
+  const msm_bases* b_bases;   /* NULL: the B_i come from the same handle as the A_i          */
+  msm_subset_t a, b;          /* the m bases A_i and B_i, each as msm_bases_scale reads a subset
+                                 (range, or indices[0]); a.m == b.m == m                     */
+  const uint32_t* a_scalars;  /* NULL: a_i = 1.  Else [m][sw] (or [sw] with _A_BROADCAST)     */
+  const uint32_t* b_scalars;  /* NULL: b_i = 1.  Likewise                                    */
+  uint32_t flags, reserved;   /* reserved = 0                                                */
+} msm_combine_t;
+int msm_bases_combine(const msm_bases* bases, const msm_combine_t* combine, const msm_opts* opts,
+                      uint32_t* points_be /* [m][32] wire records */);
+int msm_bases_combine_device(const msm_bases* bases, const msm_combine_t* combine, const msm_opts* opts,
+                             void* hip_stream, uint32_t* d_points_be);
+int msm_bases_combine_create(const msm_bases* bases, const msm_combine_t* combine, const msm_opts* opts,
+                             uint32_t levels, msm_bases** out);
+int msm_bases_combine_create_device(const msm_bases* bases, const msm_combine_t* combine, const msm_opts* opts,
+                                    uint32_t levels, void* hip_stream, msm_bases** out);
+
 /* Fixed-base tables: Q_i = sum_(j<k) s_ij * B_j for m rows of scalars over the same k bases (ark-ec's
  * FixedBase::msm / batch_mul on a generator, beside the two above): powers-of-tau and SRS generation
  * ([tau^i] G), batches of public keys or nonces (k_i * G), of Pedersen commitments (v_i * G + r_i * H),

@@ -109,6 +109,19 @@ the awaited device-to-device call and the host entry (scalars up, wire records b
 checked against the oracle's scalar multiplication and the host result against the device one.
 ratio_to_scale (k = 1, device) is the baseline's median over this row's.
 
+With --combine the pass is the pairwise-combination sweep of DESIGN.md §9 (msm_bases_combine*), in one
+process: for m in --combine-sizes (log2; default 12,16,18,20) the A_i are bases [0, m) and the B_i bases
+[m, 2 m) of one handle, and for b in --combine-bits (default 64,128,256), on the same random scalars,
+
+  {"entry": "combine", "m", "bits", "form", "ms", "ns_per_point", "runs_ms", "ratio", "spread"}
+
+with "form" one of "scale_once" (Bases.scale_device on the B side: the one-scalar form's reference),
+"scale_twice" (both sides, one call after the other: the joint form's), "one" (A_i + b_i B_i), "joint"
+(a_i A_i + b_i B_i), "one_broadcast" and "joint_broadcast" (one scalar per side), and per m a "sum" row
+(A_i + B_i, with "bytes" and "gb_per_s").  Every call is the awaited device-to-device entry; "ratio" is the
+row's median over its reference's (one*: scale_once, joint*: scale_twice) and "spread" the runs' max - min.
+Sampled rows are checked against the oracle.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -772,6 +785,93 @@ def scale_pass(a):
     return 1 if bad else 0
 
 
+def combine_pass(a):
+    """--combine: every size of the sweep in this one process (one context, one torch import)."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+    from oracle import oracle as O
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def affine(rec):
+        return (O.be_words_to_int(rec[:8]), O.be_words_to_int(rec[8:16]))
+
+    def mul(p, k):
+        return p if k is None else O.c_scalar_mul(p, k)
+
+    bad = 0
+    rng = np.random.default_rng(2025)
+    mmax = 1 << max(a.combine_sizes)
+    pts = M.gen_points(2 * mmax, k0=3, step=5)
+    with M.Bases.from_wire(pts, levels=1) as h:
+        for lg in a.combine_sizes:
+            m = 1 << lg
+            d_out = torch.zeros((m, 32), dtype=torch.int32, device="cuda")
+            d_out2 = torch.zeros((m, 32), dtype=torch.int32, device="cuda")
+            sample = [0, m - 1] + [int(i) for i in rng.integers(0, m, size=2)]
+
+            def check(ka, kb):
+                got = d_out.cpu().numpy().view(np.uint32)
+                return all(affine(got[i]) == O.aff_add(mul(affine(pts[i]), ka(i)), mul(affine(pts[m + i]), kb(i))) and
+                           got[i][31] == 1 for i in sample)
+
+            torch.cuda.synchronize()
+            ms, runs, _ = timed(lambda: h.combine_device(d_out, b_first=m, m=m), a.runs)
+            ok = check(lambda i: None, lambda i: None)
+            nbytes = m * (2 * 128 + 2 * 108 + 128)  # two records in, (X : Y : Z) out and in again, a wire record out
+            emit({"entry": "combine", "m": m, "bits": 0, "form": "sum", "ms": round(ms, 4),
+                  "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs, "spread": round(max(runs) - min(runs), 4),
+                  "bytes": nbytes, "gb_per_s": round(nbytes / ms / 1e6, 1), "correct": bool(ok)})
+            bad += not ok
+            for bits in a.combine_bits:
+                sw = (bits + 31) // 32
+                sc = rng.integers(0, 1 << 32, size=(2, m, sw), dtype=np.uint64).astype(np.uint32)
+                if bits % 32:
+                    sc[:, :, 0] &= (1 << (bits % 32)) - 1
+                d_sa, d_sb = dev(sc[0]), dev(sc[1])
+                d_xa, d_xb = dev(sc[0][:1]), dev(sc[1][:1])
+                ia = lambda i: O.be_words_to_int(sc[0][i])  # noqa: E731
+                ib = lambda i: O.be_words_to_int(sc[1][i])  # noqa: E731
+                kw = {} if bits == 256 else {"scalar_bits": bits}
+                torch.cuda.synchronize()
+
+                def twice():
+                    h.scale_device(d_sa, d_out, **kw)
+                    h.scale_device(d_sb, d_out2, first=m, **kw)
+
+                rows, oks = {}, {}
+                rows["scale_once"] = timed(lambda: h.scale_device(d_sb, d_out2, first=m, **kw), a.runs)
+                rows["scale_twice"] = timed(twice, a.runs)
+                rows["one"] = timed(lambda: h.combine_device(d_out, b=d_sb, b_first=m, **kw), a.runs)
+                oks["one"] = check(lambda i: None, ib)
+                rows["joint"] = timed(lambda: h.combine_device(d_out, a=d_sa, b=d_sb, b_first=m, **kw), a.runs)
+                oks["joint"] = check(ia, ib)
+                rows["one_broadcast"] = timed(
+                    lambda: h.combine_device(d_out, b=d_xb, b_first=m, m=m, b_broadcast=True, **kw), a.runs)
+                oks["one_broadcast"] = check(lambda i: None, lambda i: ib(0))
+                rows["joint_broadcast"] = timed(
+                    lambda: h.combine_device(d_out, a=d_xa, b=d_xb, b_first=m, m=m, a_broadcast=True, b_broadcast=True,
+                                             **kw), a.runs)
+                oks["joint_broadcast"] = check(lambda i: ia(0), lambda i: ib(0))
+                for form, (ms, runs, _) in rows.items():
+                    ref = rows["scale_twice" if form.startswith("joint") else "scale_once"][0]
+                    emit({"entry": "combine", "m": m, "bits": bits, "form": form, "ms": round(ms, 4),
+                          "ns_per_point": round(ms * 1e6 / m, 2), "runs_ms": runs,
+                          "spread": round(max(runs) - min(runs), 4), "ratio": round(ms / ref, 4),
+                          "correct": bool(oks.get(form, True))})
+                bad += not all(oks.values())
+    return 1 if bad else 0
+
+
 def fixed_pass(a):
     """--fixed: every size of the fixed-base sweep in this one process (one context, one torch import)."""
     import numpy as np
@@ -916,12 +1016,19 @@ def main():
     ap.add_argument("--fixed-widths", default="6,8,10,12", help="window widths w of the fixed sweep")
     ap.add_argument("--fixed-bases", default="1,2", help="base counts k of the fixed sweep")
     ap.add_argument("--fixed-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--combine", action="store_true", help="the pairwise-combination sweep (msm_bases_combine*) instead")
+    ap.add_argument("--combine-sizes", default="12,16,18,20", help="log2 point counts m of the combine sweep")
+    ap.add_argument("--combine-bits", default="64,128,256", help="scalar widths b of the combine sweep")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
     a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
     if a.dense:
         return dense_sweep(a)
+    if a.combine:  # one process, as the sweep's references are timed beside its rows
+        a.combine_sizes = sorted(int(x) for x in str(a.combine_sizes).split(",") if x)
+        a.combine_bits = [int(x) for x in str(a.combine_bits).split(",") if x]
+        return combine_pass(a)
     if a.fixed:
         lists = {"--fixed-sizes": "fixed_sizes", "--fixed-bits": "fixed_bits", "--fixed-widths": "fixed_widths",
                  "--fixed-bases": "fixed_bases"}

@@ -380,6 +380,17 @@ int msm_test_scale_digits(const uint32_t* scalar_be, uint32_t sw, uint32_t b, ui
   return MSM_OK;
 }
 
+// k_combine_joint's own digit function on the host (msm_kernels.hip combine_digit): the joint ladder's
+// digits of two b-bit scalars of sw big-endian words each, least significant first -- bit j of a + 2 * bit
+// j of b -- and their count, the ladder's trip count b.  digits holds 256 entries.
+int msm_test_combine_digits(const uint32_t* a_be, const uint32_t* b_be, uint32_t sw, uint32_t b, uint32_t* digits,
+                            uint32_t* count) {
+  if (!a_be || !b_be || !digits || !count || b < 1 || b > 256 || sw != (b + 31) / 32) return MSM_ERR_INVALID_ARG;
+  *count = b;
+  for (uint32_t j = 0; j < b; j++) digits[j] = combine_digit(a_be, b_be, sw, b, j);
+  return MSM_OK;
+}
+
 // k_fixed_eval's own digit function on the host (msm_kernels.hip fixed_digit, fixed_windows): the
 // signed digits of one b-bit scalar of sw big-endian words for windows of w bits, least significant
 // first, their count, and the carry out of the last one (always 0).  digits holds 257 entries.

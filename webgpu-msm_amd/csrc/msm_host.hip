@@ -57,6 +57,7 @@ namespace {
 #include "host_multi.h"
 #include "host_bases.h"
 #include "host_fixed.h"
+#include "host_combine.h"
 }  // namespace
 #include "host_test_hooks.h"
 
@@ -381,6 +382,27 @@ int msm_bases_scale_create_device(const msm_bases* h, const msm_subset_t* sub, c
                                   const msm_opts* opts, uint32_t levels, void* hip_stream, msm_bases** out) {
   if (!out) return MSM_ERR_INVALID_ARG;
   return bases_scale(h, sub, d_scalars_be, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
+}
+
+int msm_bases_combine(const msm_bases* h, const msm_combine_t* combine, const msm_opts* opts, uint32_t* points_be) {
+  return bases_combine(h, combine, true, opts, nullptr, points_be, 0, nullptr);
+}
+
+int msm_bases_combine_device(const msm_bases* h, const msm_combine_t* combine, const msm_opts* opts, void* hip_stream,
+                             uint32_t* d_points_be) {
+  return bases_combine(h, combine, false, opts, (hipStream_t)hip_stream, d_points_be, 0, nullptr);
+}
+
+int msm_bases_combine_create(const msm_bases* h, const msm_combine_t* combine, const msm_opts* opts, uint32_t levels,
+                             msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return bases_combine(h, combine, true, opts, nullptr, nullptr, levels, out);
+}
+
+int msm_bases_combine_create_device(const msm_bases* h, const msm_combine_t* combine, const msm_opts* opts,
+                                    uint32_t levels, void* hip_stream, msm_bases** out) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  return bases_combine(h, combine, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
 }
 
 int msm_fixed_create(const msm_bases* h, const msm_subset_t* sub, uint32_t window_bits, uint32_t scalar_bits,

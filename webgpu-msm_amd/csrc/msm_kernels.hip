@@ -995,6 +995,196 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS) k_fixed_normalise(const
 }
 
 // ---------------------------------------------------------------------------------------------
+// pairwise combinations of bases handles (msm_bases_combine*): R_i = a_i A_i +- b_i B_i
+// ---------------------------------------------------------------------------------------------
+// One lane per output point and one wave per workgroup, as k_scale_points.  Three kernels, chosen on
+// the host (the form is wave-uniform): k_combine_sum (no scalars), k_combine_one (one side has
+// scalars) and k_combine_joint (both).  Every one leaves (X : Y : Z) in k_fixed_eval's block layout
+// and k_fixed_normalise writes the points, so eight outputs share one inversion.
+constexpr uint32_t CB_THREADS = FX_THREADS;
+static_assert(CB_THREADS == 64, "the combine kernels write k_fixed_eval's blocks of 64");
+// One side's m bases: records `first + i` (indices == nullptr) or `indices[i]` of the n records `recs`
+// of a handle's level 0 (kernel argument, by value).
+struct CombineSide {
+  const uint32_t* recs;
+  const uint32_t* indices;
+  uint32_t n, first;
+};
+// Digit j (j < b) of the joint ladder: bit j of a + 2 * bit j of b, both b-bit scalars of sw =
+// ceil(b / 32) big-endian words.  The ladder asks for the digits below b only, so a stray bit at or
+// above b (flagged by the kernel) never reaches it; a j past them reads as 0.  Runs on the host too
+// (msm_test_combine_digits).
+__host__ __device__ inline uint32_t combine_digit(const uint32_t* a_be, const uint32_t* b_be, uint32_t sw, uint32_t b,
+                                                  uint32_t j) {
+  if (j >= b) return 0u;
+  const uint32_t wi = sw - 1 - (j >> 5), sh = j & 31u;
+  return ((a_be[wi] >> sh) & 1u) | (((b_be[wi] >> sh) & 1u) << 1);
+}
+// A side's records into the staging array (range form; the indexed form stages nothing), and lane i's
+// record out of it or gathered by its index.  An index >= n is replaced by 0 and raises
+// MSM_DEV_ERR_BAD_INDEX.  A barrier goes between the two, and before the array is staged again.
+__device__ __forceinline__ void cb_stage_side(uint4* st, const CombineSide& s, uint32_t p0, uint32_t np) {
+  if (!s.indices)
+    lane_stage_records<CB_THREADS>(st, reinterpret_cast<const uint4*>(s.recs) + ((size_t)s.first + p0) * 8, np);
+}
+__device__ __forceinline__ void cb_read_side(const uint4* st, const CombineSide& s, uint32_t p0, uint32_t i, bool live,
+                                             uint32_t* __restrict__ err, uint32_t (&rec)[32]) {
+  if (s.indices) {
+    uint32_t idx = live ? s.indices[p0 + i] : 0u;
+    if (idx >= s.n) {
+      idx = 0;
+      atomicOr(err, MSM_DEV_ERR_BAD_INDEX);
+    }
+    lane_gather_record(s.recs, idx, live, rec);
+  } else {
+    lane_read_record(st, i, live, rec);
+  }
+}
+// -P for `neg` (wave-uniform): X and T negated (fe_neg: normalised, at most 8p) and put through a
+// multiply by one, so every coordinate is again an fe_mul output as pt_add and pt_dbl take them.
+__device__ __forceinline__ xyzt cb_neg_if(const xyzt& p, bool neg) {
+  xyzt r = p;
+  if (neg) {
+    const fe unit = fe_one();
+    r.X = fe_mul(fe_neg(p.X), unit);
+    r.T = fe_mul(fe_neg(p.T), unit);
+  }
+  return r;
+}
+// The workgroup's scalars into LDS: np sw words, or the one scalar every lane reads (`bcast`); and
+// lane i's scalar there.  A bit at or above b raises MSM_DEV_ERR_SCALAR_RANGE (the digit functions mask it).
+__device__ __forceinline__ void cb_stage_scalars(uint4* ssc4, const uint32_t* __restrict__ scalars, bool bcast,
+                                                 uint32_t p0, uint32_t np, uint32_t sw) {
+  if (bcast) lane_stage_scalars<CB_THREADS>(ssc4, scalars, 0, sw);
+  else lane_stage_scalars<CB_THREADS>(ssc4, scalars, (size_t)p0 * sw, np * sw);
+}
+__device__ __forceinline__ const uint32_t* cb_my_scalar(const uint4* ssc4, bool bcast, uint32_t i, bool live, uint32_t sw,
+                                                        uint32_t b, uint32_t* __restrict__ err) {
+  const uint32_t* my = reinterpret_cast<const uint32_t*>(ssc4) + (bcast ? 0u : i * sw);
+  const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
+  if (live && (my[0] & ~top_mask)) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+  return my;
+}
+// Lane i's point into the block's (X : Y : Z) rows (k_fixed_eval's layout); a lane past m stores the
+// identity, so k_fixed_normalise needs no bound and meets no Z = 0.
+__device__ __forceinline__ void cb_store_proj(uint32_t* __restrict__ proj, const xyzt& acc, bool live) {
+  const xyzt r = pt_sel(live, pt_identity(), acc);
+  uint32_t* dst = proj + (size_t)blockIdx.x * FX_PROJ_WORDS * CB_THREADS + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < NL; q++) {
+    dst[q * CB_THREADS] = r.X.v[q];
+    dst[(NL + q) * CB_THREADS] = r.Y.v[q];
+    dst[(2 * NL + q) * CB_THREADS] = r.Z.v[q];
+  }
+}
+
+// R_i = A_i + B_i, or A_i - B_i with `sub`: one complete addition per lane.
+extern "C" __global__ void __launch_bounds__(CB_THREADS) k_combine_sum(CombineSide A, CombineSide B, uint32_t sub,
+                                                                      uint32_t* __restrict__ proj, uint32_t m,
+                                                                      uint32_t* __restrict__ err) {
+  __shared__ uint4 st[CB_THREADS * 8];
+  const uint32_t p0 = blockIdx.x * CB_THREADS;
+  const uint32_t np = min(CB_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  uint32_t rec[32];
+  cb_stage_side(st, A, p0, np);
+  __syncthreads();
+  cb_read_side(st, A, p0, i, live, err, rec);
+  const xyzt pa = pt_from_record(rec);
+  __syncthreads();
+  cb_stage_side(st, B, p0, np);
+  __syncthreads();
+  cb_read_side(st, B, p0, i, live, err, rec);
+  const xyzt pb = cb_neg_if(pt_from_record(rec), sub != 0);
+  cb_store_proj(proj, pt_add(pa, pb), live);
+}
+
+// R_i = s_i S_i + Q_i: k_scale_points' ladder (scale_digit, scale_windows: 2-bit windows over
+// {O, S, 2S, 3S}) on the side with scalars, then one addition of the plain side's point.  The host
+// names the sides, so that MSM_COMBINE_SUB stays on B: `neg` bit 0 negates S_i, bit 1 negates Q_i.
+// Q's record is staged in the array S's has left, and read (or gathered) after the ladder, so that it
+// holds no registers across the loop.
+extern "C" __global__ void __launch_bounds__(CB_THREADS, 2) k_combine_one(CombineSide S, CombineSide Q,
+                                                                         const uint32_t* __restrict__ scalars,
+                                                                         uint32_t bcast, uint32_t sw, uint32_t b,
+                                                                         uint32_t neg, uint32_t* __restrict__ proj,
+                                                                         uint32_t m, uint32_t* __restrict__ err) {
+  __shared__ uint4 st[CB_THREADS * 8];
+  __shared__ uint4 ssc4[CB_THREADS * 2];
+  const uint32_t p0 = blockIdx.x * CB_THREADS;
+  const uint32_t np = min(CB_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  cb_stage_scalars(ssc4, scalars, bcast != 0, p0, np, sw);
+  uint32_t rec[32];
+  cb_stage_side(st, S, p0, np);
+  __syncthreads();
+  cb_read_side(st, S, p0, i, live, err, rec);
+  const xyzt p1 = cb_neg_if(pt_from_record(rec), (neg & 1u) != 0);
+  __syncthreads();
+  cb_stage_side(st, Q, p0, np);
+  __syncthreads();
+  const uint32_t* my = cb_my_scalar(ssc4, bcast != 0, i, live, sw, b, err);
+  xyzt acc = pt_identity();
+  const xyzt p2 = pt_dbl(p1);
+  const xyzt p3 = pt_add(p2, p1);
+  const xyzt p0i = pt_identity();
+#pragma unroll 1
+  for (uint32_t j = scale_windows(b); j-- > 0;) {
+    acc = pt_dbl(pt_dbl(acc));
+    const uint32_t d = live ? scale_digit(my, sw, b, j) : 0u;
+    const bool hi = (d & 2u) != 0;
+    acc = pt_add(acc, pt_sel((d & 1u) != 0, pt_sel(hi, p0i, p2), pt_sel(hi, p1, p3)));
+  }
+  cb_read_side(st, Q, p0, i, live, err, rec);
+  const xyzt pq = cb_neg_if(pt_from_record(rec), (neg & 2u) != 0);
+  cb_store_proj(proj, pt_add(acc, pq), live);
+}
+
+// R_i = a_i A_i + b_i B_i (B negated with `sub`): the joint (Straus) ladder over {O, A, B, A + B},
+// b rounds of one doubling and one complete addition of the entry combine_digit names, most
+// significant bit first.  The entry is chosen with pt_sel: no lane takes a branch of its own.  The
+// trip count is the kernel argument alone.  Table and accumulator are 144 VGPRs, as k_scale_points'.
+extern "C" __global__ void __launch_bounds__(CB_THREADS, 2) k_combine_joint(
+    CombineSide A, CombineSide B, const uint32_t* __restrict__ a_scalars, const uint32_t* __restrict__ b_scalars,
+    uint32_t bcast, uint32_t sw, uint32_t b, uint32_t sub, uint32_t* __restrict__ proj, uint32_t m,
+    uint32_t* __restrict__ err) {
+  __shared__ uint4 st[CB_THREADS * 8];
+  __shared__ uint4 sa4[CB_THREADS * 2];
+  __shared__ uint4 sb4[CB_THREADS * 2];
+  const uint32_t p0 = blockIdx.x * CB_THREADS;
+  const uint32_t np = min(CB_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  cb_stage_scalars(sa4, a_scalars, (bcast & 1u) != 0, p0, np, sw);
+  cb_stage_scalars(sb4, b_scalars, (bcast & 2u) != 0, p0, np, sw);
+  uint32_t rec[32];
+  cb_stage_side(st, A, p0, np);
+  __syncthreads();
+  cb_read_side(st, A, p0, i, live, err, rec);
+  const xyzt pa = pt_from_record(rec);
+  __syncthreads();
+  cb_stage_side(st, B, p0, np);
+  __syncthreads();
+  cb_read_side(st, B, p0, i, live, err, rec);
+  const xyzt pb = cb_neg_if(pt_from_record(rec), sub != 0);
+  const uint32_t* mya = cb_my_scalar(sa4, (bcast & 1u) != 0, i, live, sw, b, err);
+  const uint32_t* myb = cb_my_scalar(sb4, (bcast & 2u) != 0, i, live, sw, b, err);
+  const xyzt pab = pt_add(pa, pb);
+  const xyzt p0i = pt_identity();
+  xyzt acc = pt_identity();
+#pragma unroll 1
+  for (uint32_t j = b; j-- > 0;) {
+    acc = pt_dbl(acc);
+    const uint32_t d = live ? combine_digit(mya, myb, sw, b, j) : 0u;
+    const bool hi = (d & 2u) != 0;
+    acc = pt_add(acc, pt_sel((d & 1u) != 0, pt_sel(hi, p0i, pb), pt_sel(hi, pa, pab)));
+  }
+  cb_store_proj(proj, acc, live);
+}
+
+// ---------------------------------------------------------------------------------------------
 // scalar recoding
 // ---------------------------------------------------------------------------------------------
 // Signed recoding of one scalar (little-endian words, consumed in place).  Calls f(window,

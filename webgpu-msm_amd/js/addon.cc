@@ -33,6 +33,10 @@
 //       over a subset of the bases: the range [first, first + m), or bases indices[0..m)
 //   scaleBases(id, scalars: Uint32Array(8m), first?, indices?, scalarBits?, asBases?, levels?, windowSize?)
 //       -> Uint32Array(32m), the wire points s_i * P_i, or with asBases the object of a new handle
+//   combineBases(id, otherId?, a?: Uint32Array, b?: Uint32Array, aFirst, bFirst, aIndices?, bIndices?, m, flags,
+//                scalarBits?, keep?, levels?, windowSize?)
+//       -> Uint32Array(32m), the wire points a_i * A_i +- b_i * B_i (flags: MSM_COMBINE_*), or with keep the
+//          object of a new handle
 //   releaseBases(id) -> number (0 ok, -1 for a handle already released)
 // Fixed-base tables (msm_fixed_*; not enumerable either):
 //   prepareFixedBase(id, first?, count?, indices?, windowBits?, scalarBits?)
@@ -714,6 +718,87 @@ napi_value ScaleBases(napi_env env, napi_callback_info info) {
   return make_u32(env, out.data(), m * 32);
 }
 
+// combineBases(id, otherId?, a?, b?, aFirst, bFirst, aIndices?, bIndices?, m, flags, scalarBits?, keep?, levels?,
+// windowSize?): the pairwise combinations a_i * A_i +- b_i * B_i of two subsets of one handle's bases or of
+// two handles' (msm_bases_combine; synchronous, as prepareBases is).  `a` and `b` hold m scalars, or one with
+// the side's broadcast flag, or are absent (the scalar 1).  A Uint32Array of m x 32 wire words, or with
+// `keep` the object of a new handle (msm_bases_combine_create).
+napi_value CombineBases(napi_env env, napi_callback_info info) {
+  size_t argc = 14;
+  napi_value argv[14];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  auto given = [&](size_t at) {
+    napi_valuetype vt = napi_undefined;
+    return argc > at && napi_typeof(env, argv[at], &vt) == napi_ok && vt != napi_undefined && vt != napi_null;
+  };
+  auto index_of = [&](size_t at, double* v) {  // a non-negative integer a double holds exactly
+    return napi_get_value_double(env, argv[at], v) == napi_ok && *v >= 0 && *v <= 9007199254740992.0 &&
+           *v == (double)(uint64_t)*v;
+  };
+  const msm_bases* h = argc > 0 ? get_handle(env, argv[0]) : nullptr;
+  const msm_bases* other = given(1) ? get_handle(env, argv[1]) : nullptr;
+  const uint32_t* sc[2] = {nullptr, nullptr};
+  const uint32_t* ix[2] = {nullptr, nullptr};
+  size_t slen[2] = {0, 0}, ilen[2] = {0, 0};
+  double first[2] = {0, 0}, m = 0, flags = 0, bits = 0;
+  bool keep = false;
+  const bool has_bits = given(10);
+  bool ok = argc >= 10 && h && (!given(1) || other) && index_of(8, &m) && index_of(9, &flags) && flags < 8;
+  for (int s = 0; ok && s < 2; s++) {
+    if (given(2 + s)) ok = get_u32_array(env, argv[2 + s], &sc[s], &slen[s]);
+    if (ok && given(4 + s)) ok = index_of(4 + s, &first[s]);
+    if (ok && given(6 + s)) ok = get_u32_array(env, argv[6 + s], &ix[s], &ilen[s]);
+  }
+  if (ok && has_bits) ok = napi_get_value_double(env, argv[10], &bits) == napi_ok && bits == (double)(uint32_t)bits;
+  if (ok && given(11)) ok = napi_get_value_bool(env, argv[11], &keep) == napi_ok;
+  if (!ok) {
+    napi_throw_type_error(env, nullptr,
+                          "combineBases(id: number, otherId?: number, a?: Uint32Array, b?: Uint32Array, aFirst: number, "
+                          "bFirst: number, aIndices?: Uint32Array, bIndices?: Uint32Array, m: number, flags: number, "
+                          "scalarBits?: number, keep?: boolean, levels?: number, windowSize?: number)");
+    return nullptr;
+  }
+  if (has_bits && (bits < 1 || bits > 256)) return throw_rc(env, MSM_ERR_INVALID_ARG);
+  const size_t sw = has_bits ? ((size_t)bits + 31) / 32 : 8;  // words per scalar
+  const uint32_t fl = (uint32_t)flags;
+  for (int s = 0; s < 2; s++) {
+    const bool bcast = fl & (s ? MSM_COMBINE_B_BROADCAST : MSM_COMBINE_A_BROADCAST);
+    if ((sc[s] && slen[s] != (bcast ? 1 : (size_t)m) * sw) || (ix[s] && ilen[s] != (size_t)m)) {
+      napi_throw_range_error(env, nullptr, "m scalars (one for a broadcast side) and m indices per side");
+      return nullptr;
+    }
+  }
+  msm_opts o;
+  memset(&o, 0, sizeof(o));
+  o.device = -1;
+  o.window_bits = given(13) ? get_window(env, argv[13]) : 0;
+  if (has_bits) {
+    o.flags |= MSM_FLAG_SCALAR_BITS;
+    o.scalar_bits = (uint32_t)bits;
+  }
+  msm_combine_t cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.b_bases = other;
+  cb.a.first = (uint64_t)first[0];
+  cb.b.first = (uint64_t)first[1];
+  cb.a.m = cb.b.m = (uint64_t)m;
+  cb.a.indices = ix[0] ? &ix[0] : nullptr;
+  cb.b.indices = ix[1] ? &ix[1] : nullptr;
+  cb.a_scalars = sc[0];
+  cb.b_scalars = sc[1];
+  cb.flags = fl;
+  if (keep) {
+    msm_bases* nh = nullptr;
+    int rc = msm_bases_combine_create(h, &cb, &o, given(12) ? get_window(env, argv[12]) : 0, &nh);
+    if (rc != MSM_OK) return throw_rc(env, rc);
+    return bases_object(env, nh);
+  }
+  std::vector<uint32_t> out((size_t)m * 32 + 1);
+  int rc = msm_bases_combine(h, &cb, &o, out.data());
+  if (rc != MSM_OK) return throw_rc(env, rc);
+  return make_u32(env, out.data(), (size_t)m * 32);
+}
+
 // computeMsmPrepared(id, scalars[, first, indices]): with `first` (a number) or `indices` (a
 // Uint32Array) the MSM runs over a subset of the handle's bases and the scalar array gives its
 // length (msm_bases_compute_subset); with neither (absent or undefined) over all of them.  With
@@ -1080,6 +1165,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"releaseBases", nullptr, ReleaseBases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decompressPoints", nullptr, DecompressPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"scaleBases", nullptr, ScaleBases, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"combineBases", nullptr, CombineBases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"prepareFixedBase", nullptr, PrepareFixedBase, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fixedBaseMul", nullptr, FixedBaseMul, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"releaseFixedBase", nullptr, ReleaseFixedBase, nullptr, nullptr, nullptr, napi_default, nullptr},

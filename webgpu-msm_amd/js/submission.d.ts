@@ -72,6 +72,16 @@ export declare function scale_bases_prepared(
   scalars: bigint[] | Uint32Array[] | Uint32Array,
   options: ScaleOptions & { asBases: true }
 ): BasesHandle;
+// Pairwise combinations a_i * A_i +- b_i * B_i of two subsets of a handle's bases, or of two handles':
+// m x 32 wire words, or with keep a new handle of those points.  a / b: absent (1), one bigint (broadcast)
+// or m scalars.  Synchronous.
+export type CombineOptions = {
+  other?: BasesHandle; a?: bigint | bigint[] | Uint32Array[] | Uint32Array; b?: bigint | bigint[] | Uint32Array[] | Uint32Array;
+  aFirst?: number; bFirst?: number; aIndices?: Uint32Array; bIndices?: Uint32Array; m?: number; sub?: boolean;
+  scalarBits?: number; levels?: number; windowSize?: number;
+};
+export declare function combine_bases_prepared(handle: BasesHandle, options?: CombineOptions & { keep?: false }): Uint32Array;
+export declare function combine_bases_prepared(handle: BasesHandle, options: CombineOptions & { keep: true }): BasesHandle;
 // Fixed-base tables: the windowed table of k <= 8 of a handle's bases (all, the range from `first` of
 // `count`, or bases indices[j]), then sum_j s_ij * B_j for m rows of k scalars (row after row): m x 32
 // wire words, or with asBases a new handle of those points.  Synchronous.

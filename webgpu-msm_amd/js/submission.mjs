@@ -334,6 +334,47 @@ export function scale_bases_prepared(handle, scalars, options) {
                           !!asBases, levels ? levels | 0 : 0, windowFrom(options));
 }
 
+// The pairwise combinations a_i * A_i +- b_i * B_i of two subsets of a handle's bases (msm_bases_combine*):
+// the A_i are the handle's bases from { aFirst } or { aIndices }, the B_i those of { other } (another
+// handle; default the same one) from { bFirst } or { bIndices }.  { a } and { b }: absent (the scalar 1), one
+// bigint (the same scalar for every i), or m scalars as scale_bases_prepared takes them, narrow with
+// { scalarBits }; the integer is not reduced mod r.  { sub: true } subtracts the B term.  { m } is the
+// number of points -- default the number of per-point scalars or indices, else what both ranges hold.
+// A flat Uint32Array of m x 32 wire words, or with { keep: true } a new handle ({ levels, windowSize } as
+// in prepare_bases).  Synchronous, as prepare_bases is.
+export function combine_bases_prepared(handle, options) {
+  if (!handle || typeof handle.id !== "number") throw new TypeError("combine_bases_prepared(handle, options): not a handle");
+  const { other, a, b, aFirst, bFirst, aIndices, bIndices, sub, scalarBits, keep, levels } = options || {};
+  let { m } = options || {};
+  if (other !== undefined && (!other || typeof other.id !== "number")) throw new TypeError("options.other: not a handle");
+  if (scalarBits !== undefined && !(Number.isInteger(scalarBits) && scalarBits >= 1 && scalarBits <= 256))
+    throw new RangeError("options.scalarBits: an integer in 1..256");
+  for (const [name, v] of [["aIndices", aIndices], ["bIndices", bIndices]])
+    if (v !== undefined && !(v instanceof Uint32Array)) throw new TypeError(`options.${name}: a Uint32Array`);
+  for (const [name, v] of [["aFirst", aFirst], ["bFirst", bFirst], ["m", m]])
+    if (v !== undefined && !(Number.isSafeInteger(v) && v >= 0)) throw new RangeError(`options.${name}: a non-negative integer`);
+  const words = scalarBits === undefined ? 8 : Math.ceil(scalarBits / 32);
+  let flags = sub ? 1 : 0;
+  const side = (v, flag) => {
+    if (v === undefined || v === null) return undefined;
+    if (typeof v === "bigint") {
+      flags |= flag;
+      return scalarWords([v], scalarBits);
+    }
+    const w = scalarWords(v, scalarBits);
+    if (m === undefined) m = w.length / words;
+    return w;
+  };
+  const aw = side(a, 2), bw = side(b, 4);
+  if (m === undefined) {
+    if (aIndices) m = aIndices.length;
+    else if (bIndices) m = bIndices.length;
+    else m = Math.max(0, Math.min(handle.n - (aFirst || 0), (other || handle).n - (bFirst || 0)));
+  }
+  return addon.combineBases(handle.id, other ? other.id : undefined, aw, bw, aFirst || 0, bFirst || 0, aIndices, bIndices, m,
+                            flags, scalarBits, !!keep, levels ? levels | 0 : 0, windowFrom(options));
+}
+
 // Fixed-base tables (msm_fixed_*): prepare_fixed_base builds the windowed table of k <= 8 of a handle's
 // bases -- all of them, the range { first, count } or the bases { indices } (repeats allowed) -- with
 // { windowBits } (2..16, default the library's 12) and { scalarBits } (the widest scalar served, default

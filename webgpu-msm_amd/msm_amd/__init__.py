@@ -98,6 +98,15 @@ class Subset(ctypes.Structure):
     _fields_ = [("first", ctypes.c_uint64), ("m", ctypes.c_uint64), ("indices", ctypes.c_void_p)]
 
 
+class Combine(ctypes.Structure):
+    """include/msm.h msm_combine_t."""
+    _fields_ = [("b_bases", ctypes.c_void_p), ("a", Subset), ("b", Subset), ("a_scalars", ctypes.c_void_p),
+                ("b_scalars", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+MSM_COMBINE_SUB = 1  # R_i = a_i A_i - b_i B_i (include/msm.h)
+MSM_COMBINE_A_BROADCAST = 2  # a_scalars holds one scalar, used for every i
+MSM_COMBINE_B_BROADCAST = 4  # likewise b_scalars
 MSM_FLAG_SERIAL = 1  # pipelined entries: one launch in flight at a time
 MSM_FLAG_DEVICES = 2  # msm_opts carries a device list (include/msm.h)
 MSM_FLAG_WINDOWS = 4  # msm_opts carries a window range
@@ -206,6 +215,13 @@ def load() -> ctypes.CDLL:
         "msm_bases_scale_create_device": ([vp, ctypes.POINTER(Subset), vp, optp, ctypes.c_uint32, vp,
                                            ctypes.POINTER(vp)], ctypes.c_int),
         "msm_test_scale_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
+        "msm_bases_combine": ([vp, ctypes.POINTER(Combine), optp, vp], ctypes.c_int),
+        "msm_bases_combine_device": ([vp, ctypes.POINTER(Combine), optp, vp, vp], ctypes.c_int),
+        "msm_bases_combine_create": ([vp, ctypes.POINTER(Combine), optp, ctypes.c_uint32, ctypes.POINTER(vp)],
+                                     ctypes.c_int),
+        "msm_bases_combine_create_device": ([vp, ctypes.POINTER(Combine), optp, ctypes.c_uint32, vp,
+                                             ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_test_combine_digits": ([vp, vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
         "msm_fixed_create": ([vp, ctypes.POINTER(Subset), ctypes.c_uint32, ctypes.c_uint32, optp, ctypes.POINTER(vp)],
                              ctypes.c_int),
         "msm_fixed_destroy": ([vp], ctypes.c_int),
@@ -1172,6 +1188,106 @@ class Bases:
                "msm_bases_scale_create_device")
         return Bases(h.value or 0)
 
+    # ---- pairwise combinations (include/msm.h msm_bases_combine*) ----
+    # R_i = a_i * A_i +- b_i * B_i: the A_i are this handle's bases [a_first, a_first + m) or a_indices[i],
+    # the B_i those of `other` (None: this handle again) at b_first or b_indices.  `a` and `b`: None (the
+    # scalar 1), one int (the same scalar for every i), or m scalars as scalars_to_wire takes them; the
+    # device calls take tensors, one row with a_broadcast / b_broadcast.  `sub` subtracts the B term.
+
+    def _combine_args(self, other, a, b, a_first, b_first, a_indices, b_indices, m, sub, scalar_bits, host,
+                      a_broadcast=False, b_broadcast=False):
+        """The msm_combine_t of a call, what it keeps alive, and m."""
+        oth = self if other is None else other
+        flags = MSM_COMBINE_SUB if sub else 0
+        sides = []
+        for sc, bc, flag in ((a, a_broadcast, MSM_COMBINE_A_BROADCAST), (b, b_broadcast, MSM_COMBINE_B_BROADCAST)):
+            if host and isinstance(sc, (int, np.integer)):
+                sc, bc = [int(sc)], True
+            if host and sc is not None:
+                sc = np.ascontiguousarray(scalars_to_wire(sc, scalar_bits))
+            if bc:
+                flags |= flag
+            sides.append((sc, bc))
+        if m is None:
+            lens = [len(sc) for sc, bc in sides if sc is not None and not bc]
+            lens += [len(ix) for ix in (a_indices, b_indices) if ix is not None]
+            m = lens[0] if lens else min(self.info["n"] - int(a_first), oth.info["n"] - int(b_first))
+        m = int(m)
+        for sc, bc in sides:
+            if host and sc is not None and sc.shape[0] != (1 if bc else m):
+                raise ValueError("a scalar array's length differs from m")
+        keep, subs = [sides], []
+        for first, indices in ((a_first, a_indices), (b_first, b_indices)):
+            if indices is None:
+                ptrs = None
+            elif host:
+                k, ptrs = self._host_indices(indices, m, 1)
+                keep.append(k)
+            else:
+                ptrs = self._device_indices(indices, 1)
+            subs.append(self._subset(first, m, ptrs))
+        ptr = (lambda x: None if x is None else _ptr(x)) if host else (lambda x: None if x is None else _dev_ptr(x))
+        cb = Combine(None if other is None else (other._h or None), subs[0], subs[1], ptr(sides[0][0]), ptr(sides[1][0]),
+                     flags, 0)
+        keep.append(subs)
+        return cb, keep, m
+
+    def combine(self, other=None, a=None, b=None, a_first: int = 0, b_first: int = 0, a_indices=None, b_indices=None,
+                m: Optional[int] = None, sub: bool = False, scalar_bits: Optional[int] = None) -> np.ndarray:
+        """a_i * A_i +- b_i * B_i for host scalars (and indices): wire records [m, 32] (x | y | t | z = 1,
+        canonical)."""
+        cb, keep, m = self._combine_args(other, a, b, a_first, b_first, a_indices, b_indices, m, sub, scalar_bits, True)
+        out = np.zeros((m, 32), dtype=np.uint32)
+        _check(load().msm_bases_combine(self._h or None, ctypes.byref(cb), _opts(None, scalar_bits=scalar_bits),
+                                        _ptr(out)), "msm_bases_combine")
+        return out
+
+    def combine_device(self, d_out, other=None, a=None, b=None, a_first: int = 0, b_first: int = 0, a_indices=None,
+                       b_indices=None, m: Optional[int] = None, sub: bool = False, scalar_bits: Optional[int] = None,
+                       a_broadcast: bool = False, b_broadcast: bool = False, stream: int = 0) -> None:
+        """The same between device buffers (torch tensors, or raw pointers with `m`): d_out takes m x 32
+        words (16-byte aligned, overlapping no input); complete on return."""
+        cb, keep, m = self._combine_args(other, a, b, a_first, b_first, a_indices, b_indices, m, sub, scalar_bits, False,
+                                         a_broadcast, b_broadcast)
+        _check(load().msm_bases_combine_device(self._h or None, ctypes.byref(cb), _opts(None, scalar_bits=scalar_bits),
+                                               _stream(stream, a, b, a_indices, b_indices, d_out), _dev_ptr(d_out)),
+               "msm_bases_combine_device")
+
+    def combined(self, other=None, a=None, b=None, a_first: int = 0, b_first: int = 0, a_indices=None, b_indices=None,
+                 m: Optional[int] = None, sub: bool = False, scalar_bits: Optional[int] = None, levels: int = 0,
+                 window_size: Optional[int] = None) -> "Bases":
+        """A new handle of the points a_i * A_i +- b_i * B_i, which never leave the device: the handle
+        Bases.from_wire(self.combine(...)) makes."""
+        cb, keep, m = self._combine_args(other, a, b, a_first, b_first, a_indices, b_indices, m, sub, scalar_bits, True)
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_combine_create(self._h or None, ctypes.byref(cb),
+                                               _opts(window_size, scalar_bits=scalar_bits), int(levels),
+                                               ctypes.byref(h)), "msm_bases_combine_create")
+        return Bases(h.value or 0)
+
+    def combined_device(self, other=None, a=None, b=None, a_first: int = 0, b_first: int = 0, a_indices=None,
+                        b_indices=None, m: Optional[int] = None, sub: bool = False, scalar_bits: Optional[int] = None,
+                        a_broadcast: bool = False, b_broadcast: bool = False, levels: int = 0,
+                        window_size: Optional[int] = None, stream: int = 0) -> "Bases":
+        """The same with device-resident scalars (and indices)."""
+        cb, keep, m = self._combine_args(other, a, b, a_first, b_first, a_indices, b_indices, m, sub, scalar_bits, False,
+                                         a_broadcast, b_broadcast)
+        h = ctypes.c_void_p()
+        _check(load().msm_bases_combine_create_device(self._h or None, ctypes.byref(cb),
+                                                      _opts(window_size, scalar_bits=scalar_bits), int(levels),
+                                                      _stream(stream, a, b, a_indices, b_indices), ctypes.byref(h)),
+               "msm_bases_combine_create_device")
+        return Bases(h.value or 0)
+
+    def fold(self, x, x_inv=None, levels: int = 0, window_size: Optional[int] = None) -> "Bases":
+        """One folding step of an inner-product argument's generators, for an even n: the handle of
+        x_inv * P_i + x * P_(i + n/2), i < n/2 (x_inv None: P_i + x * P_(i + n/2)), both scalars broadcast."""
+        n = self.info["n"]
+        if n % 2:
+            raise ValueError("fold needs an even number of bases")
+        return self.combined(a=None if x_inv is None else int(x_inv), b=int(x), b_first=n // 2, m=n // 2, levels=levels,
+                             window_size=window_size)
+
     def points(self, first: int = 0, m: Optional[int] = None, indices=None) -> np.ndarray:
         """The wire records [m, 32] of the handle's own points (all, a range or an index list): scale by
         ones at scalar_bits = 1.  A handle made from x-coordinates has no other copy of its y."""
@@ -1533,6 +1649,19 @@ def _test_scale_digits(value: int, scalar_bits: int) -> list:
     _check(load().msm_test_scale_digits(_ptr(sc), sc.shape[1], int(scalar_bits),
                                         digits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(count)),
            "msm_test_scale_digits")
+    return [int(d) for d in digits[:count.value]]
+
+
+def _test_combine_digits(a: int, b: int, scalar_bits: int) -> list:
+    """The joint ladder's digits of the `scalar_bits`-bit values a and b, least significant first (bit j of
+    a + 2 * bit j of b), by the kernel's own digit function run on the host (msm_test_combine_digits);
+    their number is the ladder's trip count.  Needs no device."""
+    sa, sb = scalars_to_wire([int(a)], scalar_bits), scalars_to_wire([int(b)], scalar_bits)
+    digits = np.zeros(256, dtype=np.uint32)
+    count = ctypes.c_uint32()
+    _check(load().msm_test_combine_digits(_ptr(sa), _ptr(sb), sa.shape[1], int(scalar_bits),
+                                          digits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(count)),
+           "msm_test_combine_digits")
     return [int(d) for d in digits[:count.value]]
 
 
