@@ -679,6 +679,24 @@ typedef struct msm_fixed_info_t {
 } msm_fixed_info_t;
 int msm_fixed_create(const msm_bases* bases, const msm_subset_t* subset, uint32_t window_bits, uint32_t scalar_bits,
                      const msm_opts* opts, msm_fixed** out);
+/* The same table over up to MSM_FIXED_VECTOR_MAX_BASES bases, for many rows over the same few hundred or
+ * few thousand generators: the row commitments of a matrix (Hyrax, Dory), batches of Pedersen vector
+ * commitments, the L and R terms of an inner-product argument's short rounds.  msm_fixed_create_vector
+ * returns an ordinary table: the subset, the record layout, the scalars' layout [m][k][sw], the widths,
+ * the errors, the 256 MiB limit and the lifetime are msm_fixed_create's, and msm_fixed_destroy,
+ * msm_fixed_info (`bases` = k) and the four msm_fixed_mul* entries serve it with the meanings above.  k
+ * is 1 .. 4096 (subset == NULL: all n bases, so n <= 4096).  window_bits = 0 picks the widest w in
+ * 2..12 whose table fits the 256 MiB limit: in the sweep of DESIGN.md §9 a call's time followed its
+ * window count ceil((b + 1) / w) at every shape, whatever the table's size.  For b = 256 that is w = 12
+ * up to k = 46, 9 at k = 256, 6 at k = 1024 and 3 at k = 4096 (tables of up to 256 MiB: pass window_bits
+ * for a smaller one).  For k <= 8 the records are those msm_fixed_create makes with the same w and b.
+ * A table of k <= 8 is evaluated as above whichever creator made it; one of k > 8 cuts every row into
+ * parts of up to 8 bases, sums each part in a lane of its own and adds a row's parts with the complete
+ * addition (k_vector_eval, k_vector_fold), in slabs of rows so that the partial sums stay within
+ * 256 MiB of the device context's workspace.  m * (parts per row) >= 2^30: MSM_ERR_INVALID_ARG. */
+#define MSM_FIXED_VECTOR_MAX_BASES 4096
+int msm_fixed_create_vector(const msm_bases* bases, const msm_subset_t* subset, uint32_t window_bits,
+                            uint32_t scalar_bits, const msm_opts* opts, msm_fixed** out);
 int msm_fixed_destroy(msm_fixed* table);
 int msm_fixed_info(const msm_fixed* table, msm_fixed_info_t* out);
 int msm_fixed_mul(const msm_fixed* table, const uint32_t* scalars_be /* [m][k][sw] */, size_t m, const msm_opts* opts,

@@ -122,6 +122,20 @@ with "form" one of "scale_once" (Bases.scale_device on the B side: the one-scala
 row's median over its reference's (one*: scale_once, joint*: scale_twice) and "spread" the runs' max - min.
 Sampled rows are checked against the oracle.
 
+With --vector the pass is the vector-table sweep of DESIGN.md §9 (msm_fixed_create_vector), in one process:
+for every shape k:log2(m) in --vector-shapes (default 16:16,64:14,256:12,1024:10,4096:8) and b in
+--vector-bits (default 256,64), on the same random scalars, first today's route -- m subset MSMs of the k
+bases through compute_subset_many_device ("form": "subset_many", and at b < 256 its scalar_bits form
+"subset_many_narrow"; the faster one is the baseline) -- then for w in --vector-widths (default
+2,4,6,8,10,12; 0 is the library's choice) whose table fits 256 MiB the build ("form": "table_build", with the rule's "auto_w") and
+
+  {"entry": "vector", "k", "m", "bits", "w", "auto_w", "form": "table", "forced_G", "G", "P", "passes", "slab_rows", "ms",
+   "us_per_row", "runs_ms", "baseline", "baseline_ms", "ratio_to_baseline", "table_bytes", "correct"}
+
+the awaited device-to-device call at the plan's own G ("forced_G": 0) and, at w = --vector-group-w (default
+6), at every G in --vector-groups (default 1,2,4,8).  Every row's records are checked against the
+baseline's points.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -949,6 +963,98 @@ def fixed_pass(a):
     return 1 if bad else 0
 
 
+def vector_pass(a):
+    """--vector: the vector-table sweep (msm_fixed_create_vector) in this one process.  For every shape
+    (k, m) and width b: today's route on the same scalars -- m subset MSMs of k terms through
+    compute_subset_many_device, at b < 256 also in its narrow form, the faster one kept --, then for
+    every window width whose table fits a table build and the evaluation (device to device, median of
+    `runs` awaited calls) with the plan's G and P; and at --vector-group-w the evaluation at every G."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    bad = 0
+    rng = np.random.default_rng(2026)
+    kmax = max(k for k, _ in a.vector_shapes)
+    pts = M.gen_points(kmax, k0=3, step=5)
+    with M.Bases.from_wire(pts, levels=1) as b:
+        b.vector_table(first=0, count=9, window_bits=2, scalar_bits=8).close()  # warm-up: the build's kernels
+        for k, lg in a.vector_shapes:
+            m = 1 << lg
+            d_out = torch.zeros((m, 32), dtype=torch.int32, device="cuda")
+            for bits in a.vector_bits:
+                sw = (bits + 31) // 32
+                kw = {} if bits == 256 else {"scalar_bits": bits}
+                sc = rng.integers(0, 1 << 32, size=(m, k, sw), dtype=np.uint64).astype(np.uint32)
+                if bits % 32:
+                    sc[:, :, 0] &= (1 << (bits % 32)) - 1
+                wide = np.zeros((m, k, 8), np.uint32)
+                wide[:, :, 8 - sw:] = sc
+                d_sc, d_wide = dev(sc), dev(wide)
+                torch.cuda.synchronize()
+                # today's route: one MSM per row, pipelined; raw row pointers, the caller orders the streams
+                routes = {"subset_many": ([d_wide.data_ptr() + i * k * 32 for i in range(m)], {})}
+                if bits < 256:
+                    routes["subset_many_narrow"] = ([d_sc.data_ptr() + i * k * sw * 4 for i in range(m)], kw)
+                base = {}
+                for form, (ptrs, okw) in routes.items():
+                    try:
+                        ms, runs, res = timed(lambda: b.compute_subset_many_device(ptrs, first=0, m=k, **okw), a.runs)
+                    except M.MsmError as e:
+                        emit({"entry": "vector", "k": k, "m": m, "bits": bits, "form": form, "error": e.code})
+                        return 1
+                    base[form] = (ms, runs, res)
+                    emit({"entry": "vector", "k": k, "m": m, "bits": bits, "form": form, "ms": round(ms, 4),
+                          "us_per_row": round(ms * 1e3 / m, 3), "runs_ms": runs})
+                best_form = min(base, key=lambda f: base[f][0])
+                base_ms, base_runs, base_xy = base[best_form]
+                if len(base) == 2:
+                    bad += not np.array_equal(base["subset_many"][2], base["subset_many_narrow"][2])
+
+                def evaluate(t, w, forced):
+                    nonlocal bad
+                    M._test_vector_group(forced)
+                    plan = M._test_vector_plan(k, w, t.info["scalar_bits"], m, sw)
+                    ms, runs, _ = timed(lambda: t.mul_device(d_sc, d_out, **kw), a.runs)
+                    M._test_vector_group(0)
+                    got = d_out.cpu().numpy().view(np.uint32)
+                    correct = bool(np.array_equal(got[:, :16], base_xy)) and bool(np.all(got[:, 31] == 1))
+                    bad += not correct
+                    emit({"entry": "vector", "k": k, "m": m, "bits": bits, "w": t.info["window_bits"], "auto_w": w == 0,
+                          "form": "table", "forced_G": forced,
+                          "G": plan["G"], "P": plan["P"], "passes": plan["passes"], "slab_rows": plan["slab_rows"],
+                          "ms": round(ms, 4), "us_per_row": round(ms * 1e3 / m, 3), "runs_ms": runs,
+                          "baseline": best_form, "baseline_ms": round(base_ms, 4), "ratio_to_baseline": round(base_ms / ms, 2),
+                          "table_bytes": t.info["bytes"], "correct": correct})
+
+                auto_w = M._test_vector_plan(k, 0, bits)["window_bits"]
+                for w in a.vector_widths:
+                    try:
+                        M._test_vector_plan(k, w, bits)
+                    except M.MsmError:
+                        continue  # over 256 MiB
+                    t0 = time.perf_counter()
+                    t = b.vector_table(first=0, count=k, window_bits=w, scalar_bits=bits)
+                    emit({"entry": "vector", "k": k, "bits": bits, "w": w or auto_w, "form": "table_build", "auto_w": auto_w,
+                          "ms": round((time.perf_counter() - t0) * 1e3, 3), "bytes": t.info["bytes"]})
+                    with t:
+                        evaluate(t, w, 0)
+                        if w == a.vector_group_w:
+                            for g in a.vector_groups:
+                                evaluate(t, w, g)
+    return 1 if bad else 0
+
+
 def dense_sweep(a):
     """The children of --dense, one after the other; stops at the first that fails."""
     def child(lg, bits, extra, equal, dense_min, extended):
@@ -1016,6 +1122,12 @@ def main():
     ap.add_argument("--fixed-widths", default="6,8,10,12", help="window widths w of the fixed sweep")
     ap.add_argument("--fixed-bases", default="1,2", help="base counts k of the fixed sweep")
     ap.add_argument("--fixed-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--vector", action="store_true", help="the vector-table sweep (msm_fixed_create_vector) instead")
+    ap.add_argument("--vector-shapes", default="16:16,64:14,256:12,1024:10,4096:8", help="shapes k:log2(m) of the vector sweep")
+    ap.add_argument("--vector-bits", default="256,64", help="scalar widths b of the vector sweep")
+    ap.add_argument("--vector-widths", default="2,4,6,8,10,12", help="window widths w of the vector sweep")
+    ap.add_argument("--vector-groups", default="1,2,4,8", help="bases per part G timed at --vector-group-w")
+    ap.add_argument("--vector-group-w", type=int, default=6, help="the window width at which every G is timed")
     ap.add_argument("--combine", action="store_true", help="the pairwise-combination sweep (msm_bases_combine*) instead")
     ap.add_argument("--combine-sizes", default="12,16,18,20", help="log2 point counts m of the combine sweep")
     ap.add_argument("--combine-bits", default="64,128,256", help="scalar widths b of the combine sweep")
@@ -1025,6 +1137,11 @@ def main():
     a.narrow_extra = [tuple(int(v) for v in x.split(":")) for x in str(a.narrow_extra).split(",") if x]
     if a.dense:
         return dense_sweep(a)
+    if a.vector:  # one process, as today's route is timed beside the table's rows
+        a.vector_shapes = [tuple(int(v) for v in x.split(":")) for x in str(a.vector_shapes).split(",") if x]
+        for name in ("vector_bits", "vector_widths", "vector_groups"):
+            setattr(a, name, [int(x) for x in str(getattr(a, name)).split(",") if x])
+        return vector_pass(a)
     if a.combine:  # one process, as the sweep's references are timed beside its rows
         a.combine_sizes = sorted(int(x) for x in str(a.combine_sizes).split(",") if x)
         a.combine_bits = [int(x) for x in str(a.combine_bits).split(",") if x]

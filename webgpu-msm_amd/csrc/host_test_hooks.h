@@ -422,6 +422,40 @@ int msm_test_fixed_plan(uint32_t k, uint32_t w, uint32_t b, uint32_t out[7]) {
   return MSM_OK;
 }
 
+// The shape msm_fixed_create_vector gives a table of k bases (host_fixed.h vector_table_plan), laid out
+// as msm_test_fixed_plan's, and with m > 0 how a call of m rows of sw-word scalars on it is cut
+// (vector_plan): out[7..] = G, P, the fold's passes, then a slab's rows and the partial buffer's bytes as
+// two words each.  Needs no device.
+int msm_test_vector_plan(uint32_t k, uint32_t w, uint32_t b, uint64_t m, uint32_t sw, uint32_t out[14]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  FixedPlan fp;
+  if (int rc = vector_table_plan(k, w, b, &fp)) return rc;
+  out[0] = fp.w;
+  out[1] = fp.b;
+  out[2] = fp.Wn;
+  out[3] = (uint32_t)fp.records;
+  out[4] = (uint32_t)(fp.records >> 32);
+  out[5] = (uint32_t)fp.bytes;
+  out[6] = (uint32_t)(fp.bytes >> 32);
+  for (int i = 7; i < 14; i++) out[i] = 0;
+  if (!m) return MSM_OK;
+  if (sw < 1 || sw > 8) return MSM_ERR_INVALID_ARG;
+  const VectorPlan vp = vector_plan(k, m, sw);
+  out[7] = vp.G;
+  out[8] = vp.P;
+  out[9] = vp.passes;
+  out[10] = (uint32_t)vp.slab_rows;
+  out[11] = (uint32_t)(vp.slab_rows >> 32);
+  out[12] = (uint32_t)vp.part_bytes;
+  out[13] = (uint32_t)(vp.part_bytes >> 32);
+  return MSM_OK;
+}
+// The cap on the partial buffer of the calls that follow (0: VEC_PART_MAX_BYTES again), so that a test
+// runs a small call as several slabs; and the G every plan takes (0: the rule's again), so that a
+// test, or a sweep, meets parts of a chosen size.
+void msm_test_vector_slab(uint64_t bytes) { g_vec_part_cap.store(bytes ? bytes : VEC_PART_MAX_BYTES); }
+void msm_test_vector_group(uint32_t g) { g_vec_group.store(g); }
+
 // out[i] = op(a[i], b[i]) on raw limbs, nothing converted or reduced (LimbOp and its word counts:
 // msm_kernels.hip).  b is read only by the two-operand ops, neg (n flags) only by LOP_PT_MADD.
 // The lane ops' loops are bounded whatever the operands hold: fe_sqrt_ts' m strictly decreases from

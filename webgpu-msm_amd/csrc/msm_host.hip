@@ -410,6 +410,11 @@ int msm_fixed_create(const msm_bases* h, const msm_subset_t* sub, uint32_t windo
   return fixed_create(h, sub, window_bits, scalar_bits, opts, out);
 }
 
+int msm_fixed_create_vector(const msm_bases* h, const msm_subset_t* sub, uint32_t window_bits, uint32_t scalar_bits,
+                            const msm_opts* opts, msm_fixed** out) {
+  return fixed_create(h, sub, window_bits, scalar_bits, opts, out, true);
+}
+
 int msm_fixed_destroy(msm_fixed* h) {
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_fixed.find(reinterpret_cast<uintptr_t>(h));

@@ -995,6 +995,192 @@ extern "C" __global__ void __launch_bounds__(FX_THREADS) k_fixed_normalise(const
 }
 
 // ---------------------------------------------------------------------------------------------
+// vector tables (msm_fixed_create_vector): the same tables over 9 .. 4096 bases, rows cut into parts
+// ---------------------------------------------------------------------------------------------
+// One lane per output over all k Wn digits (k_fixed_eval) is a chain of tens of thousands of dependent
+// additions at k = 1024, and m rows fill m / 64 waves.  Here the k bases are cut into P = ceil(k / G)
+// parts of G consecutive bases (the last one may be shorter): k_vector_eval sums one part of 64 rows per
+// wave, k_vector_fold adds up to VX_FOLD parts of a row per lane and pass, and the last pass leaves
+// (X : Y : Z) in k_fixed_eval's blocks for k_fixed_normalise.
+constexpr uint32_t VX_MAX_BASES = 4096;
+constexpr uint32_t VX_MAX_GROUP = 8;          // G: bases per part, with G sw <= VX_LANE_WORDS
+constexpr uint32_t VX_LANE_WORDS = 64;        // scalar words a lane keeps in LDS
+constexpr uint32_t VX_FOLD = 16;              // parts one lane of k_vector_fold adds
+constexpr uint32_t VX_PART_WORDS = 4 * NL;    // X | Y | Z | T of one partial sum
+
+// k_fixed_build's lane with the k base indices in device memory (the slot's sub_idx; every index was
+// checked on the host): the same statements, so the same records.
+extern "C" __global__ void __launch_bounds__(FX_THREADS, 2) k_vector_build(const uint32_t* __restrict__ recs,
+                                                                         const uint32_t* __restrict__ bases,
+                                                                         uint32_t w, uint32_t Wn,
+                                                                         uint32_t* __restrict__ out_xy,
+                                                                         uint32_t total) {
+  __shared__ uint4 st[FX_THREADS * 8];
+  const uint32_t p0 = blockIdx.x * FX_THREADS;
+  const uint32_t np = min(FX_THREADS, total - p0);
+  const uint32_t i = threadIdx.x;
+  // lanes past the last entry repeat it and write nothing
+  const uint32_t e = min(p0 + i, total - 1u);
+  const uint32_t d = (e & ((1u << (w - 1)) - 1u)) + 1u;
+  const uint32_t t = e >> (w - 1);
+  const uint32_t win = t % Wn, j = t / Wn;
+  uint32_t rec[32];
+  lane_gather_record(recs, bases[j], true, rec);
+  xyzt p = pt_from_record(rec);
+#pragma unroll 1
+  for (uint32_t s = w * win; s > 0; s--) p = pt_dbl(p);
+  xyzt acc = pt_identity();
+#pragma unroll 1
+  for (uint32_t bit = w; bit-- > 0;) {
+    acc = pt_dbl(acc);
+    acc = pt_sel(((d >> bit) & 1u) != 0, acc, pt_add(acc, p));  // (c ? b : a)
+  }
+  const fe zi = fe_inv(acc.Z);
+  lane_stage_affine(st, i, fe_mul(acc.X, zi), fe_mul(acc.Y, zi));
+  __syncthreads();
+  lane_flush_points<FX_THREADS>(st, out_xy, p0, np, 0u);
+}
+
+// `cnt` scalar words of each of a wave's np rows into LDS, row l's at ssc[l * stride ..): row l's words
+// start at word row0 + l * pitch of `scalars` (lane_stage_scalars takes one contiguous block; a part's
+// scalars are a column of the [m][k][sw] array).  16-byte loads where the vector is 16-byte aligned and
+// sw is a multiple of 4 -- every row's start and count are then multiples of 4 words --, word by word
+// elsewhere, as the narrow recode loads.
+__device__ __forceinline__ void vx_stage_rows(uint32_t* ssc, const uint32_t* __restrict__ scalars, size_t row0,
+                                              size_t pitch, uint32_t np, uint32_t cnt, uint32_t stride, uint32_t sw) {
+  if (!(reinterpret_cast<uintptr_t>(scalars) & 15u) && !(sw & 3u)) {
+    const uint32_t c4 = cnt >> 2;
+    for (uint32_t g = threadIdx.x; g < np * c4; g += FX_THREADS) {
+      const uint32_t l = g / c4, q = g - l * c4;
+      reinterpret_cast<uint4*>(ssc + l * stride)[q] = reinterpret_cast<const uint4*>(scalars + row0 + l * pitch)[q];
+    }
+  } else {
+    for (uint32_t g = threadIdx.x; g < np * cnt; g += FX_THREADS) {
+      const uint32_t l = g / cnt, q = g - l * cnt;
+      ssc[l * stride + q] = scalars[row0 + l * pitch + q];
+    }
+  }
+}
+
+// Part blockIdx.y of rows [64 blockIdx.x, +64): sum over the part's bases j in [G y, min(k, G y + G)) of
+// s_ij B_j as (X : Y : Z : T).  One lane per row, one wave per workgroup, k_fixed_eval's budget and
+// loop; j and win are wave-uniform, so the 64 lanes of a step gather from one sub-table of 2^(w-1)
+// records.
+//   scalars  [m][k][sw] big-endian words; the wave's 64 rows of the part's G sw words staged in LDS
+//            (vx_stage_rows), G sw <= VX_LANE_WORDS.  A bit at or above b is masked (fixed_window_bits)
+//            and raises MSM_DEV_ERR_SCALAR_RANGE.
+//   digits   as k_fixed_eval's: digit d != 0 of base j, window win, is record (j Wn + win) 2^(w-1) +
+//            |d| - 1; digit 0 adds nothing and reads nothing.
+//   output   part[((y nblk + x) VX_PART_WORDS + q) 64 + l] = limb q of X | Y | Z | T of row 64 x + l, nblk
+//            = gridDim.x: coalesced 256-byte rows, as proj's.  Lanes past m store the identity.
+extern "C" __global__ void __launch_bounds__(FX_THREADS, 4) k_vector_eval(const uint32_t* __restrict__ table, uint32_t k,
+                                                                        uint32_t w, uint32_t Wn, uint32_t G,
+                                                                        const uint32_t* __restrict__ scalars,
+                                                                        uint32_t sw, uint32_t b,
+                                                                        uint32_t* __restrict__ part, uint32_t m,
+                                                                        uint32_t* __restrict__ err) {
+  extern __shared__ uint4 vx_sc4[];  // FX_THREADS G sw words
+  uint32_t* ssc = reinterpret_cast<uint32_t*>(vx_sc4);
+  const uint32_t p0 = blockIdx.x * FX_THREADS;
+  const uint32_t np = min(FX_THREADS, m - p0);
+  const uint32_t i = threadIdx.x;
+  const bool live = i < np;
+  const uint32_t j0 = blockIdx.y * G;
+  const uint32_t g = min(G, k - j0);  // the part's bases
+  const uint32_t gsw = G * sw;
+  vx_stage_rows(ssc, scalars, ((size_t)p0 * k + j0) * sw, (size_t)k * sw, np, g * sw, gsw, sw);
+  __syncthreads();
+  const uint32_t* my = ssc + (live ? i : 0u) * gsw;
+  const uint32_t top_mask = (b & 31u) ? (1u << (b & 31u)) - 1u : 0xffffffffu;
+  const uint32_t hw = sw - 1u - ((b - 1u) >> 5);  // the word that holds bit b - 1
+  const uint32_t wn = fixed_windows(b, w);
+  uint32_t j = 0, win = 0, carry = 0;
+  // k_fixed_eval's next_entry over the part's bases: scalar j of the lane's staged row is base j0 + j
+  auto next_entry = [&]() -> uint32_t {
+    if (win == 0) {
+      uint32_t stray = my[j * sw + hw] & ~top_mask;
+      for (uint32_t q = 0; q < hw; q++) stray |= my[j * sw + q];
+      if (live && stray) atomicOr(err, MSM_DEV_ERR_SCALAR_RANGE);
+    }
+    const int32_t d = fixed_digit(my + j * sw, sw, b, w, win, carry);
+    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+    const uint32_t ent =
+        d && live ? (((((j0 + j) * Wn + win) << (w - 1)) + mag - 1u) << 1) | (d < 0 ? 1u : 0u) : FX_NO_ENTRY;
+    if (++win == wn) {
+      win = 0;
+      carry = 0;
+      j++;
+    }
+    return ent;
+  };
+  xyzt acc = pt_identity();
+  const uint32_t steps = g * wn;
+  uint32_t ent = next_entry();
+#pragma unroll 1
+  for (uint32_t s = 1; s <= steps; s++) {
+    const uint32_t cur = ent;
+    if (s < steps) ent = next_entry();  // the next digit beside this one's add
+    if (cur != FX_NO_ENTRY) acc = pt_madd(acc, load_pre_signed(table, cur));
+  }
+  uint32_t* dst = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * VX_PART_WORDS * FX_THREADS + i;
+#pragma unroll
+  for (int q = 0; q < NL; q++) {
+    dst[q * FX_THREADS] = acc.X.v[q];
+    dst[(NL + q) * FX_THREADS] = acc.Y.v[q];
+    dst[(2 * NL + q) * FX_THREADS] = acc.Z.v[q];
+    dst[(3 * NL + q) * FX_THREADS] = acc.T.v[q];
+  }
+}
+
+// A lane's partial sum out of a block of k_vector_eval's layout (`blk` = the block's first word + lane).
+__device__ __forceinline__ xyzt vx_load_point(const uint32_t* __restrict__ blk) {
+  xyzt r;
+#pragma unroll
+  for (int q = 0; q < NL; q++) {
+    r.X.v[q] = blk[q * FX_THREADS];
+    r.Y.v[q] = blk[(NL + q) * FX_THREADS];
+    r.Z.v[q] = blk[(2 * NL + q) * FX_THREADS];
+    r.T.v[q] = blk[(3 * NL + q) * FX_THREADS];
+  }
+  return r;
+}
+// One pass of the sum over a row's parts: output part blockIdx.y of rows [64 blockIdx.x, +64) is the
+// sum of input parts [VX_FOLD y, min(parts, VX_FOLD y + VX_FOLD)), one lane per row.  The additions
+// are the complete pt_add: parts of a row may cancel or coincide, and every input is a pt_madd or
+// pt_add output or the identity.  `last` (one output part): X | Y | Z into proj's blocks, k_fixed_eval's
+// layout; else X | Y | Z | T into `out` in the layout read.
+extern "C" __global__ void __launch_bounds__(FX_THREADS) k_vector_fold(const uint32_t* __restrict__ in,
+                                                                      uint32_t* __restrict__ out, uint32_t parts,
+                                                                      uint32_t last) {
+  const uint32_t nblk = gridDim.x;
+  const uint32_t q0 = blockIdx.y * VX_FOLD;
+  const uint32_t cnt = min(VX_FOLD, parts - q0);
+  const size_t step = (size_t)nblk * VX_PART_WORDS * FX_THREADS;  // from a part to the next
+  const uint32_t* src = in + ((size_t)q0 * nblk + blockIdx.x) * VX_PART_WORDS * FX_THREADS + threadIdx.x;
+  xyzt acc = vx_load_point(src);
+#pragma unroll 1
+  for (uint32_t q = 1; q < cnt; q++) acc = pt_add(acc, vx_load_point(src + q * step));
+  if (last) {
+    uint32_t* dst = out + (size_t)blockIdx.x * FX_PROJ_WORDS * FX_THREADS + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < NL; q++) {
+      dst[q * FX_THREADS] = acc.X.v[q];
+      dst[(NL + q) * FX_THREADS] = acc.Y.v[q];
+      dst[(2 * NL + q) * FX_THREADS] = acc.Z.v[q];
+    }
+  } else {
+    uint32_t* dst = out + ((size_t)blockIdx.y * nblk + blockIdx.x) * VX_PART_WORDS * FX_THREADS + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < NL; q++) {
+      dst[q * FX_THREADS] = acc.X.v[q];
+      dst[(NL + q) * FX_THREADS] = acc.Y.v[q];
+      dst[(2 * NL + q) * FX_THREADS] = acc.Z.v[q];
+      dst[(3 * NL + q) * FX_THREADS] = acc.T.v[q];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // pairwise combinations of bases handles (msm_bases_combine*): R_i = a_i A_i +- b_i B_i
 // ---------------------------------------------------------------------------------------------
 // One lane per output point and one wave per workgroup, as k_scale_points.  Three kernels, chosen on

@@ -968,12 +968,13 @@ napi_value ReleaseBases(napi_env env, napi_callback_info info) {
 }
 
 // ---- fixed-base tables (msm_fixed_*) --------------------------------------------------------------
-// prepareFixedBase(id, first?, count?, indices?, windowBits?, scalarBits?): the table of k <= 8 bases of
-// handle `id` -- all of them, the range [first, first + count), or bases indices[j] -- as an object of
-// its token and what msm_fixed_info says.  Synchronous, as prepareBases is.
+// prepareFixedBase(id, first?, count?, indices?, windowBits?, scalarBits?, vector?): the table of k <= 8
+// bases of handle `id` -- or with `vector` of up to 4096 (msm_fixed_create_vector) -- all of them, the
+// range [first, first + count), or bases indices[j] -- as an object of its token and what msm_fixed_info
+// says.  Synchronous, as prepareBases is.
 napi_value PrepareFixedBase(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   auto given = [&](size_t at) {
     napi_valuetype vt = napi_undefined;
@@ -985,12 +986,14 @@ napi_value PrepareFixedBase(napi_env env, napi_callback_info info) {
   size_t ilen = 0;
   double first = 0, count = 0;
   auto whole = [](double v) { return v >= 0 && v <= 9007199254740992.0 && v == (double)(uint64_t)v; };
+  bool vector = false;
   if (!h || (given(1) && (napi_get_value_double(env, argv[1], &first) != napi_ok || !whole(first))) ||
       (given(2) && (napi_get_value_double(env, argv[2], &count) != napi_ok || !whole(count))) ||
-      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen))) {
+      (has_idx && !get_u32_array(env, argv[3], &ix, &ilen)) ||
+      (given(6) && napi_get_value_bool(env, argv[6], &vector) != napi_ok)) {
     napi_throw_type_error(env, nullptr,
                           "prepareFixedBase(id: number, first?: number, count?: number, indices?: Uint32Array, "
-                          "windowBits?: number, scalarBits?: number)");
+                          "windowBits?: number, scalarBits?: number, vector?: boolean)");
     return nullptr;
   }
   msm_subset_t sub;
@@ -1004,8 +1007,9 @@ napi_value PrepareFixedBase(napi_env env, napi_callback_info info) {
     sub.m = inf.n > sub.first ? inf.n - sub.first : 0;
   }
   msm_fixed* t = nullptr;
-  int rc = msm_fixed_create(h, has_range || has_idx ? &sub : nullptr, given(4) ? get_window(env, argv[4]) : 0,
-                            given(5) ? get_window(env, argv[5]) : 0, nullptr, &t);
+  int rc = (vector ? msm_fixed_create_vector : msm_fixed_create)(
+      h, has_range || has_idx ? &sub : nullptr, given(4) ? get_window(env, argv[4]) : 0,
+      given(5) ? get_window(env, argv[5]) : 0, nullptr, &t);
   if (rc != MSM_OK) return throw_rc(env, rc);
   msm_fixed_info_t inf;
   if ((rc = msm_fixed_info(t, &inf)) != MSM_OK) return throw_rc(env, rc);

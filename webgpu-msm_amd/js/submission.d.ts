@@ -92,6 +92,11 @@ export declare function prepare_fixed_base(
   handle: BasesHandle,
   options?: { first?: number; count?: number; indices?: Uint32Array; windowBits?: number; scalarBits?: number }
 ): FixedBaseTable;
+// The same over up to 4096 bases; fixed_base_mul and release_fixed_base take the table.
+export declare function prepare_vector_base(
+  handle: BasesHandle,
+  options?: { first?: number; count?: number; indices?: Uint32Array; windowBits?: number; scalarBits?: number }
+): FixedBaseTable;
 export type FixedMulOptions = { scalarBits?: number; levels?: number; windowSize?: number };
 export declare function fixed_base_mul(
   table: FixedBaseTable,

@@ -385,12 +385,24 @@ export function combine_bases_prepared(handle, options) {
 // its own records, so the handle may be released at once; release_fixed_base frees the table.
 // Synchronous, as prepare_bases is.
 export function prepare_fixed_base(handle, options) {
-  if (!handle || typeof handle.id !== "number") throw new TypeError("prepare_fixed_base(handle): not a handle");
+  return prepareTable("prepare_fixed_base", handle, options, false);
+}
+
+// The same table over up to 4096 bases (msm_fixed_create_vector), for many rows over the same
+// generators: row commitments of a matrix, batches of Pedersen vector commitments.  { windowBits }
+// defaults to the widest window that keeps the table within 64 MiB.  fixed_base_mul and
+// release_fixed_base take the table it returns.
+export function prepare_vector_base(handle, options) {
+  return prepareTable("prepare_vector_base", handle, options, true);
+}
+
+function prepareTable(name, handle, options, vector) {
+  if (!handle || typeof handle.id !== "number") throw new TypeError(`${name}(handle): not a handle`);
   const { first, count, indices, windowBits, scalarBits } = options || {};
   if (indices !== undefined && !(indices instanceof Uint32Array)) throw new TypeError("options.indices: a Uint32Array");
   for (const [name, v] of [["first", first], ["count", count], ["windowBits", windowBits], ["scalarBits", scalarBits]])
     if (v !== undefined && !(Number.isSafeInteger(v) && v >= 0)) throw new RangeError(`options.${name}: a non-negative integer`);
-  return addon.prepareFixedBase(handle.id, first, count, indices, windowBits, scalarBits);
+  return addon.prepareFixedBase(handle.id, first, count, indices, windowBits, scalarBits, vector);
 }
 
 export function fixed_base_mul(table, scalars, options) {

@@ -224,6 +224,12 @@ def load() -> ctypes.CDLL:
         "msm_test_combine_digits": ([vp, vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p], ctypes.c_int),
         "msm_fixed_create": ([vp, ctypes.POINTER(Subset), ctypes.c_uint32, ctypes.c_uint32, optp, ctypes.POINTER(vp)],
                              ctypes.c_int),
+        "msm_fixed_create_vector": ([vp, ctypes.POINTER(Subset), ctypes.c_uint32, ctypes.c_uint32, optp,
+                                     ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_test_vector_plan": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                  u32p], ctypes.c_int),
+        "msm_test_vector_slab": ([ctypes.c_uint64], None),
+        "msm_test_vector_group": ([ctypes.c_uint32], None),
         "msm_fixed_destroy": ([vp], ctypes.c_int),
         "msm_fixed_info": ([vp, ctypes.POINTER(FixedInfo)], ctypes.c_int),
         "msm_fixed_mul": ([vp, vp, sz, optp, vp], ctypes.c_int),
@@ -1301,6 +1307,16 @@ class Bases:
         them, the range [first, first + count), or `indices` (repeats allowed).  window_bits 0 is the
         library's choice, scalar_bits 0 means 256.  The table keeps its own records: the handle may be
         closed at once."""
+        return self._table("msm_fixed_create", indices, first, count, window_bits, scalar_bits)
+
+    def vector_table(self, indices=None, first: Optional[int] = None, count: Optional[int] = None,
+                     window_bits: int = 0, scalar_bits: int = 0) -> "FixedBase":
+        """The same table over up to 4096 of the handle's bases (include/msm.h msm_fixed_create_vector),
+        for many rows over the same generators: the row commitments of a matrix, batches of Pedersen
+        vector commitments.  window_bits 0 keeps the table small (at most 64 MiB where a width allows)."""
+        return self._table("msm_fixed_create_vector", indices, first, count, window_bits, scalar_bits)
+
+    def _table(self, entry: str, indices, first, count, window_bits: int, scalar_bits: int) -> "FixedBase":
         if indices is not None:
             keep = np.ascontiguousarray(np.asarray(indices).astype(np.uint32, copy=False).reshape(-1))
             sub = ctypes.byref(self._subset(0, keep.shape[0], [keep.ctypes.data]))
@@ -1310,8 +1326,8 @@ class Bases:
         else:
             sub = None
         h = ctypes.c_void_p()
-        _check(load().msm_fixed_create(self._h or None, sub, int(window_bits), int(scalar_bits), None, ctypes.byref(h)),
-               "msm_fixed_create")
+        _check(getattr(load(), entry)(self._h or None, sub, int(window_bits), int(scalar_bits), None, ctypes.byref(h)),
+               entry)
         return FixedBase(h.value or 0)
 
     def close(self) -> None:
@@ -1335,7 +1351,7 @@ class Bases:
 
 class FixedBase:
     """A fixed-base table of k bases B_0 .. B_(k-1) (include/msm.h msm_fixed_*), made by
-    Bases.fixed_table: every call computes Q_i = sum_j s_ij * B_j for m rows of k scalars, one mixed
+    Bases.fixed_table (k <= 8) or Bases.vector_table (k <= 4096): every call computes Q_i = sum_j s_ij * B_j for m rows of k scalars, one mixed
     addition per window and base.
 
         with bases.fixed_table(indices=[0]) as g:
@@ -1685,6 +1701,33 @@ def _test_fixed_plan(bases: int, window_bits: int = 0, scalar_bits: int = 0) -> 
     _check(load().msm_test_fixed_plan(int(bases), int(window_bits), int(scalar_bits), op_), "msm_test_fixed_plan")
     return {"window_bits": int(o[0]), "scalar_bits": int(o[1]), "windows": int(o[2]),
             "records": int(o[3]) | int(o[4]) << 32, "bytes": int(o[5]) | int(o[6]) << 32}
+
+
+def _test_vector_plan(bases: int, window_bits: int = 0, scalar_bits: int = 0, m: int = 0, sw: int = 8) -> dict:
+    """The shape msm_fixed_create_vector gives a table (msm_test_vector_plan), as _test_fixed_plan's, and
+    with m > 0 how a call of m rows of sw-word scalars on it is cut: bases per part G, parts P, the
+    fold's passes, a slab's rows and the partial buffer's bytes.  Needs no device."""
+    o, op_ = _out(14)
+    _check(load().msm_test_vector_plan(int(bases), int(window_bits), int(scalar_bits), int(m), int(sw), op_),
+           "msm_test_vector_plan")
+    plan = {"window_bits": int(o[0]), "scalar_bits": int(o[1]), "windows": int(o[2]),
+            "records": int(o[3]) | int(o[4]) << 32, "bytes": int(o[5]) | int(o[6]) << 32}
+    if m:
+        plan.update(G=int(o[7]), P=int(o[8]), passes=int(o[9]), slab_rows=int(o[10]) | int(o[11]) << 32,
+                    part_bytes=int(o[12]) | int(o[13]) << 32)
+    return plan
+
+
+def _test_vector_slab(max_bytes: int = 0) -> None:
+    """Caps the partial buffer of the vector tables' calls that follow (msm_test_vector_slab), so that a
+    small call runs as several slabs of rows; 0 restores the library's 256 MiB."""
+    load().msm_test_vector_slab(int(max_bytes))
+
+
+def _test_vector_group(g: int = 0) -> None:
+    """Makes every vector-table call that follows take `g` bases per part (msm_test_vector_group; clipped
+    to what the scalars' width allows); 0 restores the library's rule."""
+    load().msm_test_vector_group(int(g))
 
 
 # msm_test_host_field's ops (csrc/host_test_hooks.h): name -> (op, takes b, works on points)
