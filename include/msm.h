@@ -708,6 +708,78 @@ int msm_fixed_mul_create(const msm_fixed* table, const uint32_t* scalars_be, siz
 int msm_fixed_mul_create_device(const msm_fixed* table, const uint32_t* d_scalars_be, size_t m, const msm_opts* opts,
                                 uint32_t levels, void* hip_stream, msm_bases** out);
 
+/* Scalar-field vectors: arithmetic mod r -- the order of the curve's prime subgroup, the Fr of
+ * ark-ed-on-bls12-377 -- on vectors of 32-byte elements: the scalar side of what the point entries above
+ * do.  A witness folded between the rounds of an inner-product argument (a'_i = x a_i + x^-1 a_(i+m)),
+ * Hadamard products, sums, differences and scalings, the powers tau^i of an SRS, inner products <a, b>,
+ * and the conversion of arkworks Fr memory into the wire scalars every *_device entry reads, without the
+ * vectors leaving the device.  Arithmetic mod r on scalars means something only for bases in the
+ * prime-order subgroup (the curve has cofactor 4): s and s + r move a point outside it differently.
+ *
+ * Element forms, 32 bytes each:
+ *   MSM_FR_WIRE   8 u32 words, most significant first: the scalar format of every entry above.  On input
+ *                 any integer < 2^256, meaning its residue mod r; on output canonical (< r).
+ *   MSM_FR_MONT   the 32 bytes of MSM_FIELD_FR_MONT (a 2^256 mod r, four little-endian u64 limbs).  On
+ *                 input a >= r is an error by that type's rule: MSM_ERR_INVALID_ARG from the host entries
+ *                 before anything is uploaded, from the device entries after the launch, which runs to its
+ *                 end and reads nothing out of range (the results are then unspecified).  On output
+ *                 canonical.
+ * Every entry computes exactly; the cost is word Montgomery products (DESIGN.md §9 has the counts and the
+ * measured times): converting between the forms is folded into the products an operation makes anyway.
+ *
+ * msm_fr_combine*: out_i = x_i * a_i +- y_i * b_i mod r for i < m.  `a` is required; b NULL: no second
+ * term (y or MSM_FR_SUB without b: MSM_ERR_INVALID_ARG).  x and y are each NULL (the multiplier 1), one
+ * element used for every i (MSM_FR_X_BROADCAST / MSM_FR_Y_BROADCAST) or m elements.  in_form is the form
+ * of a, b, x and y, out_form that of out.  So: a fold is a = the low half, b = the high half, both
+ * multipliers broadcast; a Hadamard product x per element and no b; a sum or difference a and b alone; a
+ * scaling a and a broadcast x; and `a` alone converts between the forms (and reduces wire integers mod r).
+ * `out` may be exactly `a` or exactly `b` (an in-place fold); any other overlap of the output with an
+ * operand is MSM_ERR_INVALID_ARG from the device entries, decided from the pointer values.  An unknown
+ * flag bit or form, reserved != 0 and a broadcast flag on a NULL operand give MSM_ERR_INVALID_ARG before
+ * any device work.
+ *
+ * msm_fr_powers*: out_i = c * g^i mod r for i < n (0^0 = 1).  g and c are host arrays of 8 wire words in
+ * both entries, any integers < 2^256; c NULL means 1.  A lane reaches its first power by square-and-multiply
+ * and steps from there, so no chain of products is longer than about 2 log2(n / 16) + 17.
+ *
+ * msm_fr_dot*: sum_i a_i * b_i mod r, or sum_i a_i with b NULL, over n elements in in_form: one element
+ * in out_form, written to the host array out[8] by both entries.  Two kernels: per-lane sums reduced per
+ * workgroup, then one workgroup over those partial sums; no atomics, and the result does not depend on the
+ * order since it is exact.
+ *
+ * Common rules.  m = 0 or n = 0 returns MSM_OK and touches nothing (msm_fr_dot leaves out as it is); m
+ * and n are below 2^32.  opts carries the device only (NULL is fine): MSM_FLAG_SCALAR_BITS, _SCALAR_TYPE,
+ * _SCALAR_FIELD, _DEVICES, _WINDOWS and _HALF_WINDOWS give MSM_ERR_INVALID_ARG.  Device vectors must be
+ * 16-byte aligned, as every row of an [n, 8] int32 tensor is (MSM_ERR_INVALID_ARG, decided from the
+ * pointer value before anything is enqueued).  The device entries are ordered after the work queued on
+ * hip_stream and return when the result is complete; the host entries stage their vectors through the
+ * device context's workspace.  A null required argument: MSM_ERR_INVALID_ARG. */
+#define MSM_FR_WIRE 0u
+#define MSM_FR_MONT 1u
+#define MSM_FR_SUB          1u  /* out_i = x_i a_i - y_i b_i                          */
+#define MSM_FR_X_BROADCAST  2u  /* x holds ONE element, used for every i             */
+#define MSM_FR_Y_BROADCAST  4u  /* likewise y                                        */
+typedef struct msm_fr_combine_t {
+  const uint32_t* a;          /* [m][8], required                                            */
+  const uint32_t* b;          /* NULL: no second term.  Else [m][8]                          */
+  const uint32_t* x;          /* NULL: x_i = 1.  Else [m][8] (or [8] with _X_BROADCAST)       */
+  const uint32_t* y;          /* NULL: y_i = 1.  Likewise                                    */
+  uint32_t flags;             /* MSM_FR_SUB | MSM_FR_X_BROADCAST | MSM_FR_Y_BROADCAST         */
+  uint32_t in_form, out_form; /* MSM_FR_WIRE or MSM_FR_MONT                                  */
+  uint32_t reserved;          /* 0                                                           */
+} msm_fr_combine_t;
+int msm_fr_combine(const msm_fr_combine_t* combine, size_t m, const msm_opts* opts, uint32_t* out /* [m][8] */);
+int msm_fr_combine_device(const msm_fr_combine_t* combine, size_t m, const msm_opts* opts, void* hip_stream,
+                          uint32_t* d_out);
+int msm_fr_powers(const uint32_t g_be[8], const uint32_t* c_be /* [8], or NULL: 1 */, size_t n, uint32_t out_form,
+                  const msm_opts* opts, uint32_t* out /* [n][8] */);
+int msm_fr_powers_device(const uint32_t g_be[8], const uint32_t* c_be, size_t n, uint32_t out_form, const msm_opts* opts,
+                         void* hip_stream, uint32_t* d_out);
+int msm_fr_dot(const uint32_t* a, const uint32_t* b /* NULL: sum of a */, size_t n, uint32_t in_form, uint32_t out_form,
+               const msm_opts* opts, uint32_t out[8]);
+int msm_fr_dot_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t in_form, uint32_t out_form,
+                      const msm_opts* opts, void* hip_stream, uint32_t out[8]);
+
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,
  * 7M mixed adds into per-thread bucket tables.  window_bits 0 = auto, n_threads <= 0 = all

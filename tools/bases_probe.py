@@ -136,6 +136,19 @@ the awaited device-to-device call at the plan's own G ("forced_G": 0) and, at w 
 6), at every G in --vector-groups (default 1,2,4,8).  Every row's records are checked against the
 baseline's points.
 
+With --fr the scalar-field vector entries (msm_fr_*) are swept instead, every row in this one process: for every
+n = 2^lg of --fr-sizes (default 16..22) one line per operation
+
+  {"entry": "fr", "op", "n", "ms", "ns_per_elem", "runs_ms", "bytes", "gb_per_s", "torch_op", "torch_ms",
+   "ratio_to_torch", "correct"}
+
+"fold" (n elements in, n / 2 out, both multipliers broadcast), "fold_in_place", "hadamard", "scale", "add",
+"convert" (fr_mont to wire), "powers" and "dot", device tensors in and out, beside a torch elementwise operation
+on int32 tensors that moves the same bytes (the memory-rate yardstick; "torch_op" names it), and sampled elements
+checked against Python integers.  At --fr-compare (default 20, 0: skip) two more lines: {"entry": "fr", "op":
+"fold_vs_bases_fold", ...} with fr_fold's time beside Bases.fold's on a handle of as many bases, and {"op":
+"srs", ...} with fr_powers + mul_bases_device beside host powers, scalars_to_wire, the upload and mul_bases.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -886,6 +899,129 @@ def combine_pass(a):
     return 1 if bad else 0
 
 
+def fr_pass(a):
+    """--fr: every size of the Fr vector sweep in this one process (one context, one torch import)."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+
+    R = M.FR_MODULUS
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def synced(fn):
+        def run():
+            fn()
+            torch.cuda.synchronize()
+        return run
+
+    def ints(t, idx, form="wire"):
+        return M.fr_to_ints(t[idx].cpu().numpy().view(np.uint32), form)
+
+    bad = 0
+    rng = np.random.default_rng(2026)
+    for lg in a.fr_sizes:
+        n = 1 << lg
+        h = n // 2
+        wa = rng.integers(0, 1 << 32, size=(n, 8), dtype=np.uint64).astype(np.uint32)
+        wb = rng.integers(0, 1 << 32, size=(n, 8), dtype=np.uint64).astype(np.uint32)
+        d_a, d_b = dev(wa), dev(wb)
+        va = lambda i: M.wire_to_int(wa[i])  # noqa: E731
+        vb = lambda i: M.wire_to_int(wb[i])  # noqa: E731
+        mont = wa.copy()  # canonical little-endian words: the top word below r's
+        mont[:, 7] &= 0x03ffffff
+        d_m = dev(mont)
+        x, y = int(rng.integers(1, 1 << 62)) << 180, int(rng.integers(1, 1 << 62)) << 150
+        d_x, d_y = dev(M.scalars_to_wire([x])), dev(M.scalars_to_wire([y]))
+        o_n = torch.zeros((n, 8), dtype=torch.int32, device="cuda")
+        o_h = torch.zeros((h, 8), dtype=torch.int32, device="cuda")
+        t_n, t_h = torch.zeros_like(o_n), torch.zeros_like(o_h)
+        sample = [0, 63, n - 1] + [int(i) for i in rng.integers(0, n, size=3)]
+        sample_h = [i % h for i in sample]
+        scratch = d_a.clone()
+        r_inv = pow(1 << 256, -1, R)
+        dot = {}
+
+        def run_dot():
+            dot["v"] = M.fr_dot(d_a[:a.fr_dot_check], d_b[:a.fr_dot_check])
+            return M.fr_dot(d_a, d_b)
+
+        # op: (call, bytes moved, torch yardstick and its name, check)
+        ops = {
+            "fold": (lambda: M.fr_fold(d_a, x, y, out=o_h), 48 * n, synced(lambda: torch.add(d_a[:h], d_a[h:], out=t_h)),
+                     "add(lo, hi, out)", lambda: ints(o_h, sample_h) == [(x * va(i) + y * va(i + h)) % R for i in sample_h]),
+            "fold_in_place": (lambda: M.fr_fold(scratch, x, y, out=scratch[:h]), 48 * n,
+                              synced(lambda: torch.add(d_a[:h], d_a[h:], out=t_h)), "add(lo, hi, out)", lambda: True),
+            "hadamard": (lambda: M.fr_mul(d_a, d_b, out=o_n), 96 * n, synced(lambda: torch.add(d_a, d_b, out=t_n)),
+                         "add(a, b, out)", lambda: ints(o_n, sample) == [va(i) * vb(i) % R for i in sample]),
+            "scale": (lambda: M.fr_mul(d_a, d_x, out=o_n), 64 * n, synced(lambda: torch.add(d_a, 1, out=t_n)), "add(a, 1, out)",
+                      lambda: ints(o_n, sample) == [va(i) * x % R for i in sample]),
+            "add": (lambda: M.fr_combine(d_a, d_b, out=o_n), 96 * n, synced(lambda: torch.add(d_a, d_b, out=t_n)),
+                    "add(a, b, out)", lambda: ints(o_n, sample) == [(va(i) + vb(i)) % R for i in sample]),
+            "convert": (lambda: M.fr_convert(d_m, "fr_mont", "wire", out=o_n), 64 * n,
+                        synced(lambda: torch.add(d_m, 1, out=t_n)), "add(a, 1, out)",
+                        lambda: ints(o_n, sample) == [int.from_bytes(mont[i].astype("<u4").tobytes(), "little") * r_inv % R
+                                                      for i in sample]),
+            "powers": (lambda: M.fr_powers(x, n, first=y, out=o_n), 32 * n, synced(lambda: t_n.zero_()), "zero_(out)",
+                       lambda: ints(o_n, sample) == [y * pow(x, i, R) % R for i in sample]),
+            "dot": (run_dot, 64 * n, synced(lambda: torch.add(d_a, d_b, out=t_n)), "add(a, b, out)",
+                    lambda: M.fr_to_ints([dot["v"]])[0] == sum(va(i) * vb(i) for i in range(a.fr_dot_check)) % R),
+        }
+        for op, (call, nbytes, yard, yard_name, check) in ops.items():
+            torch.cuda.synchronize()
+            ms, runs, _ = timed(call, a.runs)
+            ok = bool(check())
+            t_ms, _, _ = timed(yard, a.runs)
+            emit({"entry": "fr", "op": op, "n": n, "ms": round(ms, 4), "ns_per_elem": round(ms * 1e6 / n, 3), "runs_ms": runs,
+                  "bytes": nbytes, "gb_per_s": round(nbytes / ms / 1e6, 1), "torch_op": yard_name, "torch_ms": round(t_ms, 4),
+                  "ratio_to_torch": round(ms / t_ms, 3), "correct": ok})
+            bad += not ok
+        if lg != a.fr_compare:
+            continue
+        # the two routes of the issue's timing, in this process
+        pts = M.gen_points(n, k0=3, step=5)
+        with M.Bases.from_wire(pts, levels=1) as g:
+            def bases_fold():
+                g.fold(x, y).close()
+            f_ms, f_runs, _ = timed(bases_fold, a.runs)
+            s_ms, s_runs, _ = timed(lambda: M.fr_fold(d_a, x, y, out=o_h), a.runs)
+            emit({"entry": "fr", "op": "fold_vs_bases_fold", "n": n, "fr_fold_ms": round(s_ms, 4), "fr_fold_runs_ms": s_runs,
+                  "bases_fold_ms": round(f_ms, 4), "bases_fold_runs_ms": f_runs, "ratio": round(s_ms / f_ms, 5)})
+            with g.fixed_table(first=0, count=1) as t:
+                tau = (x + 12345) % R
+
+                def device_route():
+                    t.mul_bases_device(M.fr_powers(tau, n, device=0), n, levels=1).close()
+
+                def host_route():
+                    pw = [1] * n
+                    for i in range(1, n):
+                        pw[i] = pw[i - 1] * tau % R
+                    t.mul_bases(M.scalars_to_wire(pw), levels=1).close()
+
+                d_ms, d_runs, _ = timed(device_route, a.runs)
+                t0 = time.perf_counter()
+                host_route()
+                h_ms = (time.perf_counter() - t0) * 1e3
+                with t.mul_bases_device(M.fr_powers(tau, n, device=0), n, levels=1) as srs:
+                    got = srs.points(first=n - 2, m=2)
+                from oracle import oracle as O
+                exp = O.affine_to_wire([O.c_scalar_mul(O.c_scalar_mul(O.G, 3), pow(tau, i, R)) for i in (n - 2, n - 1)])
+                ok = bool(np.array_equal(got, exp))
+                emit({"entry": "fr", "op": "srs", "n": n, "device_route_ms": round(d_ms, 4), "device_route_runs_ms": d_runs,
+                      "host_route_ms": round(h_ms, 2), "ratio": round(d_ms / h_ms, 6), "correct": ok})
+                bad += not ok
+    return 1 if bad else 0
+
+
 def fixed_pass(a):
     """--fixed: every size of the fixed-base sweep in this one process (one context, one torch import)."""
     import numpy as np
@@ -1131,6 +1267,10 @@ def main():
     ap.add_argument("--combine", action="store_true", help="the pairwise-combination sweep (msm_bases_combine*) instead")
     ap.add_argument("--combine-sizes", default="12,16,18,20", help="log2 point counts m of the combine sweep")
     ap.add_argument("--combine-bits", default="64,128,256", help="scalar widths b of the combine sweep")
+    ap.add_argument("--fr", action="store_true", help="the scalar-field vector sweep (msm_fr_*) instead")
+    ap.add_argument("--fr-sizes", default="16,17,18,19,20,21,22", help="log2 element counts n of the Fr sweep")
+    ap.add_argument("--fr-compare", type=int, default=20, help="log2 n at which fold and SRS are timed against today's routes (0: skip)")
+    ap.add_argument("--fr-dot-check", type=int, default=4096, help="elements of the dot product checked against Python")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
@@ -1142,6 +1282,9 @@ def main():
         for name in ("vector_bits", "vector_widths", "vector_groups"):
             setattr(a, name, [int(x) for x in str(getattr(a, name)).split(",") if x])
         return vector_pass(a)
+    if a.fr:  # one process, as the yardsticks are timed beside the rows
+        a.fr_sizes = sorted(int(x) for x in str(a.fr_sizes).split(",") if x)
+        return fr_pass(a)
     if a.combine:  # one process, as the sweep's references are timed beside its rows
         a.combine_sizes = sorted(int(x) for x in str(a.combine_sizes).split(",") if x)
         a.combine_bits = [int(x) for x in str(a.combine_bits).split(",") if x]

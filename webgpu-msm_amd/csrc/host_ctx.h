@@ -177,6 +177,7 @@ struct Workspace {
   Buf dx_pts;              // k_decompress_x's output: x|y of a compressed creation, wire records of msm_decompress_points
   Buf fx_proj;             // k_fixed_eval's points (X : Y : Z) in blocks of 64, read by k_fixed_normalise (msm_fixed_mul*)
   Buf vx_part;             // k_vector_eval's partial sums (X : Y : Z : T) per part and block, and k_vector_fold's two halves
+  Buf fr_part;             // k_fr_dot_partial's sums, one element per workgroup, and k_fr_dot_final's result after them (msm_fr_dot*)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif
@@ -191,6 +192,7 @@ struct Workspace {
     WS_BUF(g_head), WS_BUF(g_hkey), WS_BUF(g_tkey), WS_BUF(red_U), WS_BUF(red_T);
     WS_BUF(wire_pts), WS_BUF(wire_sc), WS_BUF(red_G), WS_BUF(split_sc), WS_BUF(sub_idx);
     WS_BUF(seg_base), WS_BUF(unit_key), WS_BUF(partials), WS_BUF(dx_pts), WS_BUF(fx_proj), WS_BUF(vx_part);
+    WS_BUF(fr_part);
 #ifdef MSM_DUMMY_ALLOC
     WS_BUF(dummy_tiles), WS_BUF(dummy_cursor);
 #endif

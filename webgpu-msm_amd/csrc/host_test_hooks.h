@@ -616,6 +616,36 @@ int msm_test_fr_from_mont(const uint32_t* in_le, size_t n, uint32_t* out_le, uin
   return MSM_OK;
 }
 
+// fr.cuh's arithmetic on the host, the code the Fr vector kernels run: n pairs of 8 little-endian words
+// each, out_i = op(a_i, b_i) -- 0 fr_mont_mul, 1 fr_add, 2 fr_sub, 3 fr_to_mont(a_i), 4 fr_from_mont of
+// fr_to_mont(a_i).  The functions' preconditions are the hook's: b >= r for op 0, or either operand >= r for
+// ops 1 and 2, is MSM_ERR_INVALID_ARG.  Op 5 reads nothing and writes the constants: out[0..32) = R^k mod r
+// for k = 0..3 (fr_r_power), then FR_THREADS, FR_DOT_CAP, FR_COMBINE_CAP and FR_POW_STEPS (out holds 36 words).
+int msm_test_fr_op(uint32_t op, const uint32_t* a_le, const uint32_t* b_le, uint32_t* out_le, size_t n) {
+  if (op > 5 || !out_le) return MSM_ERR_INVALID_ARG;
+  if (op == 5) {
+    for (int k = 0; k < 4; k++) {
+      const FrWords w = fr_r_power(k);
+      memcpy(out_le + 8 * k, w.v, 32);
+    }
+    const uint32_t shape[4] = {FR_THREADS, FR_DOT_CAP, FR_COMBINE_CAP, FR_POW_STEPS};
+    memcpy(out_le + 32, shape, sizeof(shape));
+    return MSM_OK;
+  }
+  if ((!a_le || (op <= 2 && !b_le)) && n) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t *a = a_le + 8 * i, *b = b_le + 8 * i;
+    uint32_t* o = out_le + 8 * i;
+    if (op <= 2 && (!fr_is_canonical(b) || (op != 0 && !fr_is_canonical(a)))) return MSM_ERR_INVALID_ARG;
+    if (op == 0) fr_mont_mul(a, b, o);
+    else if (op == 1) fr_add(a, b, o);
+    else if (op == 2) fr_sub(a, b, o);
+    else fr_to_mont(a, o);
+    if (op == 4) fr_from_mont(o, o);
+  }
+  return MSM_OK;
+}
+
 // The dense-bucket part of the plan of a narrow launch (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
 // of nm MSMs of n terms at width window_bits (0: auto), pipelined or lone: out = {dense (0 / 1),
 // entries per unit lane E, keys W * B, the unit kernel's grid bound, run length K}, for the default

@@ -58,6 +58,7 @@ namespace {
 #include "host_bases.h"
 #include "host_fixed.h"
 #include "host_combine.h"
+#include "host_fr.h"
 }  // namespace
 #include "host_test_hooks.h"
 
@@ -468,6 +469,35 @@ int msm_fixed_mul_create_device(const msm_fixed* h, const uint32_t* d_scalars_be
                                 uint32_t levels, void* hip_stream, msm_bases** out) {
   if (!out) return MSM_ERR_INVALID_ARG;
   return fixed_mul(h, d_scalars_be, m, false, opts, (hipStream_t)hip_stream, nullptr, levels, out);
+}
+
+int msm_fr_combine(const msm_fr_combine_t* combine, size_t m, const msm_opts* opts, uint32_t* out) {
+  return fr_combine(combine, m, true, opts, nullptr, out);
+}
+
+int msm_fr_combine_device(const msm_fr_combine_t* combine, size_t m, const msm_opts* opts, void* hip_stream,
+                          uint32_t* d_out) {
+  return fr_combine(combine, m, false, opts, (hipStream_t)hip_stream, d_out);
+}
+
+int msm_fr_powers(const uint32_t g_be[8], const uint32_t* c_be, size_t n, uint32_t out_form, const msm_opts* opts,
+                  uint32_t* out) {
+  return fr_powers(g_be, c_be, n, out_form, true, opts, nullptr, out);
+}
+
+int msm_fr_powers_device(const uint32_t g_be[8], const uint32_t* c_be, size_t n, uint32_t out_form, const msm_opts* opts,
+                         void* hip_stream, uint32_t* d_out) {
+  return fr_powers(g_be, c_be, n, out_form, false, opts, (hipStream_t)hip_stream, d_out);
+}
+
+int msm_fr_dot(const uint32_t* a, const uint32_t* b, size_t n, uint32_t in_form, uint32_t out_form, const msm_opts* opts,
+               uint32_t out[8]) {
+  return fr_dot(a, b, n, in_form, out_form, true, opts, nullptr, out);
+}
+
+int msm_fr_dot_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t in_form, uint32_t out_form,
+                      const msm_opts* opts, void* hip_stream, uint32_t out[8]) {
+  return fr_dot(d_a, d_b, n, in_form, out_form, false, opts, (hipStream_t)hip_stream, out);
 }
 
 int msm_combine_partials(const uint32_t* partials_xyzt_be, size_t count, uint32_t out_xy_be[16]) {

@@ -3975,3 +3975,5 @@ __global__ void __launch_bounds__(64) k_test_limbs_lane(const uint32_t* __restri
 }
 
 }  // namespace msm
+
+#include "fr_kernels.cuh"

@@ -30,6 +30,7 @@ __all__ = [
     "lib_path", "points_to_wire", "scalars_to_wire", "wire_to_int", "P", "Bases", "BasesInfo",
     "MsmOptsTyped", "MSM_FLAG_SCALAR_TYPE", "SCALAR_TYPES", "scalars_to_native",
     "MSM_FLAG_SCALAR_FIELD", "WIDE_TYPES", "FR_MODULUS", "scalars_to_wide",
+    "FR_FORMS", "fr_combine", "fr_fold", "fr_mul", "fr_convert", "fr_powers", "fr_dot", "fr_to_ints",
 ]
 
 P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
@@ -104,6 +105,17 @@ class Combine(ctypes.Structure):
                 ("b_scalars", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class FrCombine(ctypes.Structure):
+    """include/msm.h msm_fr_combine_t."""
+    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("x", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("flags", ctypes.c_uint32), ("in_form", ctypes.c_uint32), ("out_form", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+MSM_FR_SUB = 1  # out_i = x_i a_i - y_i b_i (include/msm.h)
+MSM_FR_X_BROADCAST = 2  # x holds one element, used for every i
+MSM_FR_Y_BROADCAST = 4  # likewise y
+FR_FORMS = {"wire": 0, "fr_mont": 1}  # MSM_FR_WIRE, MSM_FR_MONT: the names scalar_type uses
 MSM_COMBINE_SUB = 1  # R_i = a_i A_i - b_i B_i (include/msm.h)
 MSM_COMBINE_A_BROADCAST = 2  # a_scalars holds one scalar, used for every i
 MSM_COMBINE_B_BROADCAST = 4  # likewise b_scalars
@@ -236,6 +248,13 @@ def load() -> ctypes.CDLL:
         "msm_fixed_mul_device": ([vp, vp, sz, optp, vp, vp], ctypes.c_int),
         "msm_fixed_mul_create": ([vp, vp, sz, optp, ctypes.c_uint32, ctypes.POINTER(vp)], ctypes.c_int),
         "msm_fixed_mul_create_device": ([vp, vp, sz, optp, ctypes.c_uint32, vp, ctypes.POINTER(vp)], ctypes.c_int),
+        "msm_fr_combine": ([ctypes.POINTER(FrCombine), sz, optp, vp], ctypes.c_int),
+        "msm_fr_combine_device": ([ctypes.POINTER(FrCombine), sz, optp, vp, vp], ctypes.c_int),
+        "msm_fr_powers": ([vp, vp, sz, ctypes.c_uint32, optp, vp], ctypes.c_int),
+        "msm_fr_powers_device": ([vp, vp, sz, ctypes.c_uint32, optp, vp, vp], ctypes.c_int),
+        "msm_fr_dot": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, u32p], ctypes.c_int),
+        "msm_fr_dot_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, vp, u32p], ctypes.c_int),
+        "msm_test_fr_op": ([ctypes.c_uint32, vp, vp, vp, sz], ctypes.c_int),
         "msm_test_fixed_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.POINTER(ctypes.c_int32), u32p, u32p], ctypes.c_int),
         "msm_test_fixed_plan": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -283,7 +302,7 @@ def load() -> ctypes.CDLL:
         "msm_test_guard_plant": ([ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
-        if name.startswith(("msm_test_", "msm_bases_", "msm_decompress_", "msm_compress_")) and not hasattr(L, name):
+        if name.startswith(("msm_test_", "msm_bases_", "msm_decompress_", "msm_compress_", "msm_fr_")) and not hasattr(L, name):
             continue  # a test hook or the handle API an older library variant (MSM_AMD_LIB A/B builds) predates
         f = getattr(L, name)
         f.argtypes = args
@@ -1451,6 +1470,201 @@ class FixedBase:
             pass
 
 
+# ---- scalar-field vectors (include/msm.h msm_fr_*) ----
+# Arithmetic mod r = FR_MODULUS on vectors of 32-byte elements, in one of two forms: "wire" ([n, 8] u32,
+# big-endian words: what scalars_to_wire makes and every *_device entry reads; any integer < 2^256 on
+# input, canonical on output) and "fr_mont" ([n, 4] u64 or [n, 8] u32, little-endian: what
+# scalars_to_wide(.., "fr_mont") makes, the memory of an arkworks Fr).  numpy arrays (and lists of ints) go
+# to the host entries and come back as numpy [n, 8] uint32; torch device tensors go to the device entries
+# and come back as tensors, into `out` if given (which may be the first or the second operand itself).
+# Arithmetic mod r is meaningful only for bases in the prime-order subgroup (the curve has cofactor 4).
+
+def _fr_form(form) -> int:
+    if form not in FR_FORMS:
+        raise ValueError(f"unknown Fr form {form!r}: one of {sorted(FR_FORMS)}")
+    return FR_FORMS[form]
+
+
+def _fr_on_device(v) -> bool:
+    return bool(getattr(v, "is_cuda", False))
+
+
+def _fr_rows(v) -> int:
+    """The 32-byte elements a device tensor holds."""
+    if not v.is_contiguous():
+        raise ValueError("Fr vectors must be contiguous")
+    nbytes = v.numel() * v.element_size()
+    if nbytes % 32:
+        raise ValueError("an Fr vector holds 32 bytes per element")
+    return nbytes // 32
+
+
+def _fr_host(v, form: str) -> np.ndarray:
+    """A host vector as C-contiguous [n, 8] uint32 in `form`: an array as it is ([n, 4] uint64 for "fr_mont"),
+    ints encoded (reduced mod r for "fr_mont")."""
+    if isinstance(v, np.ndarray):
+        if v.dtype == np.uint64 and form == "fr_mont":
+            v = np.ascontiguousarray(v).view(np.uint32)
+        return np.ascontiguousarray(v, dtype=np.uint32).reshape(-1, 8)
+    v = list(v)
+    if v and not isinstance(v[0], (int, np.integer)):  # a list of elements, 8 words each
+        return np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.uint32).reshape(8) for s in v]))
+    vals = [int(s) for s in v]
+    if form == "fr_mont":
+        return scalars_to_wide([s % FR_MODULUS for s in vals], "fr_mont").view(np.uint32).reshape(-1, 8)
+    return np.ascontiguousarray(scalars_to_wire(vals)).reshape(-1, 8)
+
+
+def fr_to_ints(v, form: str = "wire") -> list:
+    """The residues mod r of a host vector in `form` (a tensor is copied down first)."""
+    _fr_form(form)
+    if hasattr(v, "cpu"):
+        v = v.cpu().contiguous().numpy().view(np.uint32)
+    rows = _fr_host(v, form)
+    if form == "wire":
+        return [wire_to_int(row) % FR_MODULUS for row in rows]
+    r_inv = pow(1 << 256, -1, FR_MODULUS)
+    return [int.from_bytes(row.astype("<u4").tobytes(), "little") * r_inv % FR_MODULUS for row in rows]
+
+
+def _fr_operand(v, form: str, like, m: int, broadcast: bool):
+    """One operand of a combine call beside `like`, the first: (what to keep alive, pointer, rows, broadcast)."""
+    if v is None:
+        return None, None, 0, False
+    if _fr_on_device(like):
+        if isinstance(v, (int, np.integer)):
+            import torch
+
+            v = torch.from_numpy(_fr_host([int(v)], form).view(np.int32)).to(like.device)
+        elif not _fr_on_device(v):
+            raise TypeError("device and host Fr vectors in one call")
+        rows = _fr_rows(v)
+        ptr = _dev_ptr(v)
+    else:
+        if _fr_on_device(v):
+            raise TypeError("device and host Fr vectors in one call")
+        v = _fr_host([int(v)] if isinstance(v, (int, np.integer)) else v, form)
+        rows = v.shape[0]
+        ptr = _ptr(v)
+    broadcast = broadcast or (rows == 1 and m != 1)
+    if rows != (1 if broadcast else m):
+        raise ValueError("an Fr operand's length differs from the first operand's")
+    return v, ptr, rows, broadcast
+
+
+def fr_combine(a, b=None, x=None, y=None, sub: bool = False, form: str = "wire", out_form: Optional[str] = None,
+               out=None, x_broadcast: bool = False, y_broadcast: bool = False, device: int = -1, stream: int = 0):
+    """out_i = x_i * a_i +- y_i * b_i mod r.  b None: no second term.  x and y: None (1), one int or a
+    one-row vector (the same multiplier for every i), or a vector as long as a.  `form` is the form of
+    every operand, `out_form` (None: the same) that of the result."""
+    out_form = form if out_form is None else out_form
+    fi, fo = _fr_form(form), _fr_form(out_form)
+    dev = _fr_on_device(a)
+    if not dev:
+        a = _fr_host(a, form)
+    m = _fr_rows(a) if dev else a.shape[0]
+    kb, pb, rb, _ = _fr_operand(b, form, a, m, False)
+    if b is not None and rb != m:
+        raise ValueError("an Fr operand's length differs from the first operand's")
+    kx, px, _, bx = _fr_operand(x, form, a, m, x_broadcast)
+    ky, py, _, by = _fr_operand(y, form, a, m, y_broadcast)
+    flags = (MSM_FR_SUB if sub else 0) | (MSM_FR_X_BROADCAST if bx else 0) | (MSM_FR_Y_BROADCAST if by else 0)
+    if dev:
+        if out is None:
+            import torch
+
+            out = torch.empty_like(a) if fi == fo else torch.empty((m, 8), dtype=torch.int32, device=a.device)
+        elif not _fr_on_device(out) or _fr_rows(out) != m:
+            raise ValueError("out must be a device tensor of the first operand's length")
+        cb = FrCombine(_dev_ptr(a) if m else None, pb, px, py, flags, fi, fo, 0)
+        _check(load().msm_fr_combine_device(ctypes.byref(cb), m, _opts(None, device=a.device.index),
+                                            _stream(stream, a, kb, kx, ky, out), _dev_ptr(out)),
+               "msm_fr_combine_device")
+        return out
+    if out is not None:
+        raise ValueError("out= is for device tensors")
+    res = np.zeros((m, 8), dtype=np.uint32)
+    cb = FrCombine(_ptr(a), pb, px, py, flags, fi, fo, 0)
+    _check(load().msm_fr_combine(ctypes.byref(cb), m, _opts(None, device=device), _ptr(res)), "msm_fr_combine")
+    return res
+
+
+def fr_fold(a, x, x_inv=None, form: str = "wire", out_form: Optional[str] = None, out=None, device: int = -1,
+            stream: int = 0):
+    """One folding step of an inner-product argument's witness, for an even n: a'_i = x * a_i + x_inv *
+    a_(i + n/2), i < n/2 (x_inv None: x * a_i + a_(i + n/2)) -- the scalars that go with Bases.fold(x, x_inv).
+    `out` may be the low half itself (a[:n // 2] of a device tensor)."""
+    if not _fr_on_device(a):
+        a = _fr_host(a, form)
+    n = _fr_rows(a) if _fr_on_device(a) else a.shape[0]
+    if n % 2:
+        raise ValueError("fold needs an even number of elements")
+    rows = a.reshape(n, -1)
+    return fr_combine(rows[:n // 2], rows[n // 2:], x=x, y=x_inv, form=form, out_form=out_form, out=out, x_broadcast=True,
+                      y_broadcast=x_inv is not None, device=device, stream=stream)
+
+
+def fr_mul(a, x, form: str = "wire", out_form: Optional[str] = None, out=None, device: int = -1, stream: int = 0):
+    """x_i * a_i mod r: a Hadamard product for a vector x, a scaling for one int or a one-row x."""
+    return fr_combine(a, x=x, form=form, out_form=out_form, out=out, device=device, stream=stream)
+
+
+def fr_convert(a, form: str, out_form: str, out=None, device: int = -1, stream: int = 0):
+    """`a` in the other form: "fr_mont" to "wire" is the route from arkworks Fr memory to the scalars the
+    scale, fixed-base and combine entries read; "wire" to "wire" reduces 256-bit integers mod r."""
+    return fr_combine(a, form=form, out_form=out_form, out=out, device=device, stream=stream)
+
+
+def fr_powers(g: int, n: int, first: Optional[int] = None, out_form: str = "wire", out=None,
+              device: Optional[int] = None, stream: int = 0):
+    """first * g^i mod r for i < n (first None: 1).  A numpy [n, 8] uint32 from the host entry; with `device`
+    (a HIP ordinal) or a device tensor `out`, a device tensor from the device entry, which never leaves it:
+    table.mul_bases_device(fr_powers(tau, n, device=0), n) is an SRS."""
+    fo = _fr_form(out_form)
+    n = int(n)
+    gw = scalars_to_wire([int(g) % (1 << 256)])
+    cw = None if first is None else scalars_to_wire([int(first) % (1 << 256)])
+    cp = None if cw is None else _ptr(cw)
+    if out is None and device is None:
+        res = np.zeros((n, 8), dtype=np.uint32)
+        _check(load().msm_fr_powers(_ptr(gw), cp, n, fo, _opts(None), _ptr(res)), "msm_fr_powers")
+        return res
+    if out is None:
+        import torch
+
+        out = torch.empty((n, 8), dtype=torch.int32, device=f"cuda:{int(device)}")
+    elif not _fr_on_device(out) or _fr_rows(out) != n:
+        raise ValueError("out must be a device tensor of n elements")
+    _check(load().msm_fr_powers_device(_ptr(gw), cp, n, fo, _opts(None, device=out.device.index),
+                                       _stream(stream, out), _dev_ptr(out)), "msm_fr_powers_device")
+    return out
+
+
+def fr_dot(a, b=None, form: str = "wire", out_form: Optional[str] = None, device: int = -1, stream: int = 0) -> np.ndarray:
+    """sum_i a_i * b_i mod r (b None: sum_i a_i) as one element in `out_form` (None: `form`): a numpy [8]
+    uint32 on the host, whichever entry computed it (fr_to_ints([result], out_form)[0] is its residue)."""
+    out_form = form if out_form is None else out_form
+    fi, fo = _fr_form(form), _fr_form(out_form)
+    res = np.zeros(8, dtype=np.uint32)
+    rp = res.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    if _fr_on_device(a):
+        n = _fr_rows(a)
+        if b is not None and (not _fr_on_device(b) or _fr_rows(b) != n):
+            raise ValueError("b must be a device tensor as long as a")
+        _check(load().msm_fr_dot_device(_dev_ptr(a) if n else None, None if b is None else _dev_ptr(b), n, fi, fo,
+                                        _opts(None, device=a.device.index), _stream(stream, a, b), rp),
+               "msm_fr_dot_device")
+        return res
+    a = _fr_host(a, form)
+    if b is not None:
+        b = _fr_host(b, form)
+        if b.shape[0] != a.shape[0]:
+            raise ValueError("b must be as long as a")
+    _check(load().msm_fr_dot(_ptr(a), None if b is None else _ptr(b), a.shape[0], fi, fo, _opts(None, device=device), rp),
+           "msm_fr_dot")
+    return res
+
+
 def compute_msm_many(points_list, scalars_list, n: int, window_size: Optional[int] = None,
                      run_length: Optional[int] = None, device: int = -1, flags: int = 0,
                      devices: Optional[Sequence[int]] = None) -> np.ndarray:
@@ -1846,6 +2060,32 @@ def _test_fr_from_mont(values) -> Tuple[list, list]:
                                         ok.ctypes.data_as(ctypes.c_void_p)), "msm_test_fr_from_mont")
     raw = out.astype("<u4").tobytes()
     return [int.from_bytes(raw[32 * i: 32 * i + 32], "little") for i in range(len(vals))], [bool(x) for x in ok]
+
+
+_FR_OPS = {"mont_mul": 0, "add": 1, "sub": 2, "to_mont": 3, "round_trip": 4}
+
+
+def _test_fr_op(name: str, a, b=None) -> list:
+    """csrc/fr.cuh's arithmetic on the host (msm_test_fr_op; no GPU needed), on 256-bit ints: "mont_mul" a b
+    2^-256 mod r (b < r), "add" and "sub" (a, b < r), "to_mont" a 2^256 mod r, "round_trip" fr_from_mont of it."""
+    av = [int(v) for v in a]
+    bv = [0] * len(av) if b is None else [int(v) for v in b]
+    pack = lambda vals: np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype="<u4").astype(np.uint32)
+    pa, pb = pack(av), pack(bv)
+    out = np.zeros_like(pa)
+    _check(load().msm_test_fr_op(_FR_OPS[name], _ptr(pa), _ptr(pb), _ptr(out), len(av)), "msm_test_fr_op")
+    raw = out.astype("<u4").tobytes()
+    return [int.from_bytes(raw[32 * i: 32 * i + 32], "little") for i in range(len(av))]
+
+
+def _test_fr_constants() -> dict:
+    """fr.cuh's R^k mod r for k = 0..3 as ints, and the Fr kernels' shape: workgroup size, k_fr_dot_partial's
+    and k_fr_combine's grid caps, k_fr_powers' elements per lane."""
+    out = np.zeros(36, dtype=np.uint32)
+    _check(load().msm_test_fr_op(5, None, None, _ptr(out), 0), "msm_test_fr_op")
+    raw = out[:32].astype("<u4").tobytes()
+    return {"r_powers": [int.from_bytes(raw[32 * k: 32 * k + 32], "little") for k in range(4)],
+            "threads": int(out[32]), "dot_cap": int(out[33]), "combine_cap": int(out[34]), "pow_steps": int(out[35])}
 
 
 def _test_native_plan(n: int, scalar_type, scalar_bits: int, window_size: int = 0) -> dict:
