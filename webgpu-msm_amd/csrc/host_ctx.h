@@ -32,13 +32,55 @@ std::atomic<uint64_t> g_alloc_gen{0};
 // Guarded workspaces, a test mode (msm_test_guard, host_guard.h; off in production, no environment
 // knob): every allocation made while the switch is on is front guard | payload | back guard, with
 // `cap` the requested bytes exactly -- no 256-B floor, so nothing hides in slack --, the guards filled
-// with GUARD_FILL and the payload with zero bytes (a defined value: read as an index it stays in
-// range).  The back guard is one whole partition chunk of 32-bit entries, the largest unit any one
-// lane group writes; the front guard keeps `p` 256-B aligned.  msm_test_guard_check reads the guards
+// with GUARD_FILL and the payload with g_guard_word (below; zero by default, a defined value: read as an
+// index it stays in range).  The back guard is one whole partition chunk of 32-bit entries, the largest
+// unit any one lane group writes; the front guard keeps `p` 256-B aligned.  msm_test_guard_check reads the guards
 // back.  The switch changes only while nothing is allocated, so one process never mixes the layouts.
 std::atomic<bool> g_guard{false};
 constexpr size_t GUARD_FRONT = 4096, GUARD_BACK = 65536;
 constexpr int GUARD_FILL = 0xA5;
+
+// The payload's fill is a 32-bit word of the tests' choosing (msm_test_guard_fill; 0 unless a test says
+// otherwise): a poison, so that a kernel reading a word its launch never wrote computes with something
+// other than zero -- the neutral value of nearly all the integer state the kernels keep (no entry, an
+// empty count, a clear flag, key 0, the additive identity of an Fr sum), which is why a zero fill cannot
+// show such a read.  Only words <= GUARD_WORD_MAX = 3 are accepted.  Read as an index, a count, a key, an
+// entry word (index << 1 | sign), a run's workgroup or a shift, such a word addresses at most record 3 of
+// a table -- 4 point records of 144 B, 4 prepared records of 128 B, 4 Fr elements of 32 B, words 0..5 of
+// an integer table -- and every one of those lies inside the payload or the 64 KiB back guard of its
+// buffer: a kernel that does read poison computes a wrong value or touches a guard band
+// (msm_test_guard_check names it), it does not leave the allocation.  Read as the halves of a 16-bit
+// table (digits, part_fine) the word is {word, 0}; as limbs of a point or of a field element it is a
+// small residue, and the arithmetic forms no address from it.  (The per-point kernels -- k_scale_points,
+// the k_combine_* -- compare every index they gather by with n before they use it.)  What the kernels
+// multiply into an address (n, K, B, nbc, ch, rstride, the plan's counts) comes by value in the launch's
+// arguments, never from a workspace word.  The differences the kernels take of two workspace words -- bin_base[bin + 1] -
+// bin_base[bin] (k_fine_sort), bucket_start[k + 1] - bucket_start[k] (k_dense_segments, the reductions'
+// emptiness tests compare only), seg_base[key + 1] - seg_base[key] (k_dense_units, k_dense_fold) --
+// would wrap if one side were poison and the other a smaller true value; both sides of each are stored
+// by the launch's own sort (k_part_scatter writes bin_base[0 .. nbins], k_fine_sort bucket_start[0 ..
+// W B + 1], k_dense_segments seg_base[0 .. nkeys]) in a kernel that ends before the reader starts, and
+// a zero fill wraps the same way with the sides exchanged, so the poison adds no way out there.  No
+// buffer is excluded for its indexing.
+constexpr uint32_t GUARD_WORD_MAX = 3;
+std::atomic<uint32_t> g_guard_word{0};
+
+// `bytes` at device address p filled with `word`, whole words then the word's low bytes (null stream;
+// the caller synchronises).
+inline hipError_t guard_fill_dev(void* p, size_t bytes, uint32_t word) {
+  char* b = static_cast<char*>(p);
+  const size_t words = bytes / 4;
+  if (words)
+    if (hipError_t e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b), (int)word, words); e != hipSuccess) return e;
+  for (size_t k = 4 * words; k < bytes; k++)
+    if (hipError_t e = hipMemset(b + k, (int)((word >> (8 * (k & 3))) & 0xffu), 1); e != hipSuccess) return e;
+  return hipSuccess;
+}
+// The same on the host, for a pinned buffer.
+inline void guard_fill_host(void* p, size_t bytes, uint32_t word) {
+  uint8_t* b = static_cast<uint8_t*>(p);
+  for (size_t k = 0; k < bytes; k++) b[k] = (uint8_t)(word >> (8 * (k & 3)));
+}
 
 struct Buf {
   void* p = nullptr;
@@ -65,7 +107,8 @@ struct Buf {
     char* b = static_cast<char*>(base);
     // (the fills are complete before any of the library's streams, which do not wait for the null
     // stream, can touch the buffer)
-    if (hipMemset(b, GUARD_FILL, GUARD_FRONT) != hipSuccess || hipMemset(b + GUARD_FRONT, 0, bytes) != hipSuccess ||
+    if (hipMemset(b, GUARD_FILL, GUARD_FRONT) != hipSuccess ||
+        guard_fill_dev(b + GUARD_FRONT, bytes, g_guard_word.load(std::memory_order_relaxed)) != hipSuccess ||
         hipMemset(b + GUARD_FRONT + bytes, GUARD_FILL, GUARD_BACK) != hipSuccess ||
         hipStreamSynchronize(nullptr) != hipSuccess) {
       hipFree(base);
@@ -115,7 +158,7 @@ struct HostBuf {
     }
     char* b = static_cast<char*>(base);
     memset(b, GUARD_FILL, GUARD_FRONT);
-    memset(b + GUARD_FRONT, 0, bytes);
+    guard_fill_host(b + GUARD_FRONT, bytes, g_guard_word.load(std::memory_order_relaxed));
     memset(b + GUARD_FRONT + bytes, GUARD_FILL, GUARD_BACK);
     p = b + GUARD_FRONT;
     cap = bytes;

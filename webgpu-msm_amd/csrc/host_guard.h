@@ -117,6 +117,18 @@ int guard_scan_zero(const Buf& b, size_t bytes, uint32_t id, int device, int slo
   return MSM_OK;
 }
 
+// The poison pass of msm_test_guard_poison: a guarded buffer's payload from byte `skip` on overwritten
+// with the fill word (the caller has drained the streams, and synchronises the null stream after the
+// last buffer).  Nothing for a buffer that is not guarded.
+int guard_poison(const Buf& b, size_t skip, uint32_t word) {
+  if (!b.base || skip >= b.cap) return MSM_OK;
+  HIPCHECK(guard_fill_dev(static_cast<char*>(b.p) + skip, b.cap - skip, word));
+  return MSM_OK;
+}
+void guard_poison_host(const HostBuf& b, uint32_t word) {
+  if (b.base) guard_fill_host(b.p, b.cap, word);
+}
+
 // Findings on buffers that do not outlive their call (the error word of a handle's preparation),
 // kept for the next msm_test_guard_check.
 std::mutex g_guard_mu;

@@ -1213,6 +1213,89 @@ int msm_test_guard_plant(int device, int slot, uint32_t buffer, int where) {
   return found ? rc : MSM_ERR_INVALID_ARG;
 }
 
+// ---- poisoned payloads (host_ctx.h g_guard_word; tests/test_gpu_poison.py) -------------------------
+// Sets the word guarded allocations write over their payload and returns the previous one; the reasoning
+// that bounds it is host_ctx.h's.  MSM_ERR_INVALID_ARG for a word above GUARD_WORD_MAX.  It changes
+// allocations made after the call, and nothing while the guard switch is off.  No device needed.
+int msm_test_guard_fill(uint32_t word) {
+  if (word > GUARD_WORD_MAX) return MSM_ERR_INVALID_ARG;
+  return (int)g_guard_word.exchange(word);
+}
+
+// Overwrites, at quiescence, the payload of every guarded buffer of the device's context (every context
+// for device < 0) with the current fill word: every slot's workspace, its h_out, and the context's
+// shared_pts, host_sc and host_pts.  Nothing is freed and no graph is dropped, so the next call replays
+// its cached graph onto a workspace that holds nothing of the launch before it.  Left out, by name:
+//   err, lead_flag, colsum, bin_cur (whole) and skew_list[0] -- the five regions the kernels keep all-zero
+//     between MSMs (ensure_workspace starts that invariant only after a reallocation, so these do carry
+//     state from call to call: msm_test_guard_check's zero scan is what watches them);
+//   a handle's and a table's records (bases_rec) -- live state, the inputs of the calls to come.
+// No other buffer carries anything across calls: shared_pts is prepared again by every
+// msm_compute_shared* call (ManyRun::setup), host_sc and host_pts are uploaded whole by every split call,
+// and the preparation's error word (bases_prep_err) does not outlive its call.  Nothing while the guard
+// switch is off.
+int msm_test_guard_poison(int device) {
+  if (!g_guard.load()) return MSM_OK;
+  const uint32_t word = g_guard_word.load();
+  return guard_each_ctx(device, [&](DevCtx* c) -> int {
+    int r = MSM_OK;
+    for (Slot& sl : c->slot) {
+      Workspace& w = sl.ws;
+      w.each_buf([&](const char*, Buf& b) {
+        if (&b == &w.err || &b == &w.lead_flag || &b == &w.colsum || &b == &w.bin_cur) return;
+        if (r == MSM_OK) r = guard_poison(b, &b == &w.skew_list ? 4 : 0, word);
+      });
+      guard_poison_host(sl.h_out, word);
+    }
+    c->each_buf([&](const char*, Buf& b) {
+      if (r == MSM_OK) r = guard_poison(b, 0, word);
+    });
+    if (r == MSM_OK && hipStreamSynchronize(nullptr) != hipSuccess) r = MSM_ERR_HIP;
+    return r;
+  });
+}
+
+// Copies `words` payload words of buffer `buffer` (an index of msm_test_guard_name's table) from word
+// `first_word` on into out: a workspace buffer or the h_out of slot `slot`, or one of the context's own
+// buffers (the slot is not looked at).  Nothing is launched.  MSM_ERR_INVALID_ARG for a range that is
+// empty or not inside the payload, a buffer that is not allocated, a handle's buffers (there may be
+// many), an id past the table, and where the device has no context.
+int msm_test_guard_peek(int device, int slot, uint32_t buffer, size_t first_word, size_t words, uint32_t* out) {
+  const size_t nws = guard_id("h_out");
+  if (!out || !words || buffer >= guard_names().size() || (buffer <= nws && (slot < 0 || slot >= NSLOT)))
+    return MSM_ERR_INVALID_ARG;
+  if (first_word > (SIZE_MAX / 4) - words) return MSM_ERR_INVALID_ARG;
+  bool found = false;
+  int rc = guard_each_ctx(device, [&](DevCtx* c) -> int {
+    if (found) return MSM_OK;
+    found = true;
+    const void* p = nullptr;
+    size_t cap = 0;
+    bool host = false;
+    uint32_t id = 0;
+    auto pick = [&](const char*, Buf& b) {
+      if (id++ == buffer) p = b.p, cap = b.cap;
+    };
+    if (buffer < nws) {
+      c->slot[slot].ws.each_buf(pick);
+    } else if (buffer == nws) {
+      p = c->slot[slot].h_out.p, cap = c->slot[slot].h_out.cap, host = true;
+    } else {
+      id = (uint32_t)nws + 1;
+      c->each_buf(pick);
+    }
+    if (!p || (first_word + words) * 4 > cap) return MSM_ERR_INVALID_ARG;
+    const uint32_t* src = static_cast<const uint32_t*>(p) + first_word;
+    if (host) {
+      memcpy(out, src, words * 4);
+      return MSM_OK;
+    }
+    HIPCHECK(hipMemcpy(out, src, words * 4, hipMemcpyDeviceToHost));
+    return MSM_OK;
+  });
+  return found ? rc : MSM_ERR_INVALID_ARG;
+}
+
 #ifdef MSM_PHASE_PROBE
 // Tuning builds only: writes the sort kernels' phase stamps of the last launch (g_probe) to `path`.
 int msm_test_probe_dump(const char* path) {

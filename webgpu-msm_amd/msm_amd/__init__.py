@@ -300,6 +300,9 @@ def load() -> ctypes.CDLL:
         "msm_test_guard_release": ([ctypes.c_int], ctypes.c_int),
         "msm_test_guard_check": ([ctypes.c_int, ctypes.POINTER(GuardHit), sz, ctypes.POINTER(sz)], ctypes.c_int),
         "msm_test_guard_plant": ([ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int], ctypes.c_int),
+        "msm_test_guard_fill": ([ctypes.c_uint32], ctypes.c_int),
+        "msm_test_guard_poison": ([ctypes.c_int], ctypes.c_int),
+        "msm_test_guard_peek": ([ctypes.c_int, ctypes.c_int, ctypes.c_uint32, sz, sz, u32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name.startswith(("msm_test_", "msm_bases_", "msm_decompress_", "msm_compress_", "msm_fr_")) and not hasattr(L, name):
@@ -2335,3 +2338,36 @@ def _test_guard_plant(buffer: str, where: int, slot: int = 0, device: int = -1) 
     3: the second payload word."""
     _check(load().msm_test_guard_plant(int(device), int(slot), _test_guard_names().index(buffer), int(where)),
            "msm_test_guard_plant")
+
+
+def _test_guard_fill(word: int) -> int:
+    """Set the 32-bit word guarded allocations write over their payload (msm_test_guard_fill) and return
+    the previous one.  0 is the default; MsmError -1 for a word above 3.  It changes allocations made
+    after the call, and nothing while the guard mode is off.  No GPU needed."""
+    if not 0 <= int(word) < (1 << 32):
+        raise MsmError(-1, "msm_test_guard_fill")
+    rc = load().msm_test_guard_fill(int(word))
+    _check(min(rc, 0), "msm_test_guard_fill")
+    return int(rc)
+
+
+def _test_guard_poison(device: int = -1) -> None:
+    """Overwrite, at quiescence, the payload of every guarded workspace buffer, h_out and context buffer
+    with the current fill word (msm_test_guard_poison): nothing is freed, no graph dropped.  The five
+    regions the kernels keep all-zero and the handles' records are left as they are."""
+    _check(load().msm_test_guard_poison(int(device)), "msm_test_guard_poison")
+
+
+def _test_guard_peek(buffer, first_word: int, words: int, slot: int = 0, device: int = -1) -> np.ndarray:
+    """`words` payload words of `buffer` (a name of _test_guard_names, or an index) from `first_word` on,
+    as uint32 (msm_test_guard_peek); nothing is launched.  MsmError -1 for a range outside the payload,
+    a buffer that is not allocated or not a slot's or the context's, and a process without a context."""
+    if isinstance(buffer, str):
+        names = _test_guard_names()
+        buffer = names.index(buffer) if buffer in names else len(names)
+    if not (0 <= int(buffer) < (1 << 32) and 0 <= int(first_word) < (1 << 62) and 0 <= int(words) < (1 << 40)):
+        raise MsmError(-1, "msm_test_guard_peek")
+    out = np.zeros(max(int(words), 1), dtype=np.uint32)
+    _check(load().msm_test_guard_peek(int(device), int(slot), int(buffer), int(first_word), int(words),
+                                      out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "msm_test_guard_peek")
+    return out[:int(words)]
