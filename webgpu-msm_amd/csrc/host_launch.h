@@ -1,5 +1,6 @@
-// Layer 5, one launch: workspaces, the kernel launch sequence, its captured graphs, waiting for a slot and
-// finishing its MSMs.  Depends on the layers above it (knobs, ctx, plan, tail).
+// Layer 5, one launch: workspaces, the kernel tables (recode_kernel, scatter_kernel, RED1_TABLE), the arguments
+// of the repointable kernels (PrepareArgs, RecodeArgs), the launch sequence (enqueue_msm over LaunchCtx's stages), its
+// captured graphs, waiting for a slot and finishing its MSMs.  Depends on the layers above it (knobs, ctx, plan, tail).
 #pragma once
 // (`own_pts` false: the launch reads a handle's resident records, the slot needs no record buffer.)
 int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
@@ -66,6 +67,8 @@ int ensure_workspace(DevCtx* c, const Plan& pl, int si, bool own_pts = true) {
 }
 
 inline unsigned grid_for(size_t threads, unsigned block) { return (unsigned)((threads + block - 1) / block); }
+template <typename F>  // a kernel as hipLaunchKernel and a graph's kernel node name it
+const void* kfn(F* kernel) { return reinterpret_cast<const void*>(kernel); }
 
 bool slot_forks(const Slot& sl) { return sl.pipelined ? fork_prepare() && fork_prepare_pipelined() : fork_prepare(); }
 
@@ -76,28 +79,35 @@ uint32_t prep_nt(size_t records) {
   return records * 128 >= (size_t(1) << 27) ? 1u : 0u;
 }
 
+// k_prepare_points' arguments and launch, assembled here alone.  argv is the array hipLaunchKernel and
+// hipKernelNodeParams take; it points into the struct, which therefore does not copy.
+struct PrepareArgs {
+  BatchPtrs wires;
+  uint32_t* pts;
+  uint32_t n;
+  uint32_t* err;
+  uint32_t nt, fmt;
+  unsigned ny;  // wire buffers read: the grid's y
+  void* argv[6] = {&wires, &pts, &n, &err, &nt, &fmt};
+  PrepareArgs(const BatchPtrs& wires, uint32_t* pts, uint32_t n, uint32_t* err, uint32_t nt, uint32_t fmt, unsigned ny)
+      : wires(wires), pts(pts), n(n), err(err), nt(nt), fmt(fmt), ny(ny) {}
+  // a launch's own preparation: every MSM's points (one vector where they share it) into `pts`
+  PrepareArgs(const Plan& pl, Slot& sl, const BatchPtrs& points, uint32_t* pts)
+      : PrepareArgs(points, pts, pl.d.n, sl.ws.err.as<uint32_t>(),
+                    prep_nt((size_t)(pl.d.shared ? 1 : pl.d.nm) * pl.d.n), pl.pfmt, pl.d.shared ? 1 : pl.d.nm) {}
+  PrepareArgs(const PrepareArgs&) = delete;
+  void launch(hipStream_t s) {
+    (void)hipLaunchKernel(kfn(k_prepare_points), dim3(grid_for(n, PP_THREADS), ny), dim3(PP_THREADS), argv, 0, s);
+  }
+};
+
 // k_prepare_points over `cnt` points of one wire buffer into `pts_out` (one MSM, or one uploaded
 // chunk of it); `nt` from prep_nt of the whole record buffer.
 void launch_prepare(const uint32_t* wire, uint32_t* pts_out, uint32_t cnt, uint32_t* err, uint32_t nt,
                     hipStream_t s, uint32_t fmt = PT_FMT_WIRE) {
-  BatchPtrs bp{};
-  bp.p[0] = wire;
-  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(cnt, PP_THREADS), 1), dim3(PP_THREADS), 0, s, bp, pts_out, cnt,
-                     err, nt, fmt);
+  PrepareArgs(BatchPtrs{{wire}}, pts_out, cnt, err, nt, fmt, 1).launch(s);
 }
 
-template <uint32_t Q, uint32_t NHI>
-void launch_recode_fixed(const MsmDims& d, const BatchPtrs& sc, void* digits, uint32_t* colsum, hipStream_t s) {
-  const bool full = d.w0 == 0 && d.Wr == d.Wm && !d.half_lo && !d.half_hi;
-  const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
-  const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;
-  if (full)
-    hipLaunchKernelGGL((k_recode_fixed<Q, NHI, true>), grid, dim3(RC_THREADS), lds, s, sc, d,
-                       static_cast<uint16_t*>(digits), colsum);
-  else
-    hipLaunchKernelGGL((k_recode_fixed<Q, NHI, false>), grid, dim3(RC_THREADS), lds, s, sc, d,
-                       static_cast<uint16_t*>(digits), colsum);
-}
 // The bias C = sum_w (2^(b_w - 1) - 1) 2^off_w of the narrow, native and wide recodes over the
 // launch's windows (the sum stays below 2^(T - 1), so it fits the scalar's own words).
 NarrowBias narrow_bias(const MsmDims& d) {
@@ -122,9 +132,7 @@ struct RecodeRow {
   uint32_t stype, sw;
   const void* fn[2];  // 16-bit codes, 32-bit codes (c > 16)
 };
-#define RECODE_ROW(stype, sw, K, ...)                                        \
-  {stype, sw, {reinterpret_cast<const void*>(&K<uint16_t, __VA_ARGS__>), \
-               reinterpret_cast<const void*>(&K<uint32_t, __VA_ARGS__>)}}
+#define RECODE_ROW(stype, sw, K, ...) {stype, sw, {kfn(K<uint16_t, __VA_ARGS__>), kfn(K<uint32_t, __VA_ARGS__>)}}
 const RecodeRow RECODE_TABLE[] = {
     RECODE_ROW(0, 1, k_recode_narrow, 1),
     RECODE_ROW(0, 2, k_recode_narrow, 2),
@@ -149,106 +157,233 @@ const RecodeRow RECODE_TABLE[] = {
     RECODE_ROW(STYPE_FR_MONT, 0, k_recode_wide, 8, WIDE_MONT),
 };
 #undef RECODE_ROW
-// The recode kernel of a narrow, native or wide plan.
-const void* recode_kernel(const Plan& pl) {
-  for (const RecodeRow& r : RECODE_TABLE)
-    if (r.stype == pl.stype && (pl.stype || r.sw == pl.d.sw)) return r.fn[pl.d.c > 16];
-  return nullptr;  // (make_plan admits no other type)
-}
+// The four-argument recodes of 8-word scalars: k_recode_hist (wire words; [1]: k_recode_hist_le, little-endian
+// words) by code width, and the geometries k_recode_fixed is unrolled for, [1] with FULL (every window whole).
+const void* const RECODE_HIST[2][2] = {{kfn(k_recode_hist<uint16_t>), kfn(k_recode_hist<uint32_t>)},
+                                       {kfn(k_recode_hist_le<uint16_t>), kfn(k_recode_hist_le<uint32_t>)}};
+struct RecodeFixedRow {
+  uint32_t q, nhi;
+  const void* fn[2];
+};
+#define RECODE_FIXED_ROW(Q, NHI) {Q, NHI, {kfn(k_recode_fixed<Q, NHI, false>), kfn(k_recode_fixed<Q, NHI, true>)}}
+const RecodeFixedRow RECODE_FIXED[] = {RECODE_FIXED_ROW(15, 14), RECODE_FIXED_ROW(14, 16), RECODE_FIXED_ROW(13, 7),
+                                       RECODE_FIXED_ROW(12, 14)};
+#undef RECODE_FIXED_ROW
 
-void launch_recode(const Plan& pl, const BatchPtrs& sc, void* digits, uint32_t* colsum, uint32_t* err,
-                   hipStream_t s) {
+// The recode kernel of a plan, and how many arguments it takes: four, or RECODE_TABLE's six.
+struct RecodeKernel {
+  const void* fn;
+  unsigned nargs;
+};
+RecodeKernel recode_kernel(const Plan& pl) {
   const MsmDims& d = pl.d;
-  const dim3 grid(grid_for(d.n, RC_SPAN), d.nm);
-  const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;  // histogram + window totals
+  const bool wide = d.c > 16;  // 32-bit codes
   if (d.sw) {
-    BatchPtrs scal = sc;
-    MsmDims dd = d;
-    NarrowBias nb = narrow_bias(d);
-    void* args[] = {&scal, &dd, &digits, &colsum, &nb, &err};
-    (void)hipLaunchKernel(recode_kernel(pl), grid, dim3(RC_THREADS), args, lds, s);
-    return;
+    for (const RecodeRow& r : RECODE_TABLE)
+      if (r.stype == pl.stype && (pl.stype || r.sw == d.sw)) return {r.fn[wide], 6};
+    return {nullptr, 6};  // (make_plan admits no other type)
   }
-  if (pl.stype) {  // a 256-bit integer of 254 bits and more: the full-width geometry on little-endian words
-    if (d.c > 16)
-      hipLaunchKernelGGL(k_recode_hist_le<uint32_t>, grid, dim3(RC_THREADS), lds, s, sc, d,
-                         static_cast<uint32_t*>(digits), colsum);
-    else
-      hipLaunchKernelGGL(k_recode_hist_le<uint16_t>, grid, dim3(RC_THREADS), lds, s, sc, d,
-                         static_cast<uint16_t*>(digits), colsum);
-    return;
+  // (a typed plan here is a 256-bit integer of 254 bits and more: the full-width geometry)
+  if (pl.stype) return {RECODE_HIST[1][wide], 4};
+  if (!wide && recode_fixed_on()) {
+    const bool full = d.w0 == 0 && d.Wr == d.Wm && !d.half_lo && !d.half_hi;
+    for (const RecodeFixedRow& r : RECODE_FIXED)
+      if (r.q == d.q && r.nhi == d.nhi) return {r.fn[full], 4};
   }
-  if (d.c > 16) {
-    hipLaunchKernelGGL(k_recode_hist<uint32_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint32_t*>(digits),
-                       colsum);
-    return;
-  }
-  if (recode_fixed_on()) {
-    if (d.q == 15 && d.nhi == 14) return launch_recode_fixed<15, 14>(d, sc, digits, colsum, s);
-    if (d.q == 14 && d.nhi == 16) return launch_recode_fixed<14, 16>(d, sc, digits, colsum, s);
-    if (d.q == 13 && d.nhi == 7) return launch_recode_fixed<13, 7>(d, sc, digits, colsum, s);
-    if (d.q == 12 && d.nhi == 14) return launch_recode_fixed<12, 14>(d, sc, digits, colsum, s);
-  }
-  hipLaunchKernelGGL(k_recode_hist<uint16_t>, grid, dim3(RC_THREADS), lds, s, sc, d, static_cast<uint16_t*>(digits),
-                     colsum);
+  return {RECODE_HIST[0][wide], 4};
 }
-// Every recode kernel: a replayed graph must not read the previous call's scalars, whatever their
-// format.
+// Every recode kernel, from the tables recode_kernel picks from: a replayed graph must not read the
+// previous call's scalars, whatever their format.
 bool is_recode_kernel(const void* f) {
-  const void* ks[] = {reinterpret_cast<const void*>(&k_recode_hist<uint32_t>),
-                      reinterpret_cast<const void*>(&k_recode_hist<uint16_t>),
-                      reinterpret_cast<const void*>(&k_recode_hist_le<uint32_t>),
-                      reinterpret_cast<const void*>(&k_recode_hist_le<uint16_t>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<15, 14, true>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<15, 14, false>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<14, 16, true>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<14, 16, false>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<13, 7, true>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<13, 7, false>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<12, 14, true>),
-                      reinterpret_cast<const void*>(&k_recode_fixed<12, 14, false>)};
-  for (const void* k : ks)
-    if (f == k) return true;
+  for (const auto& pair : RECODE_HIST)
+    if (f == pair[0] || f == pair[1]) return true;
+  for (const RecodeFixedRow& r : RECODE_FIXED)
+    if (f == r.fn[0] || f == r.fn[1]) return true;
   for (const RecodeRow& r : RECODE_TABLE)
     if (f == r.fn[0] || f == r.fn[1]) return true;
   return false;
 }
 
+// A recode kernel's arguments and launch: argv holds as many entries as the plan's kernel has
+// parameters (it points into the struct, which therefore does not copy).
+struct RecodeArgs {
+  RecodeKernel k;
+  BatchPtrs scalars;
+  MsmDims d;
+  void* digits;
+  uint32_t* colsum;
+  NarrowBias nb;
+  uint32_t* err;
+  void* argv[6] = {&scalars, &d, &digits, &colsum, &nb, &err};
+  RecodeArgs(const Plan& pl, Slot& sl, const BatchPtrs& scalars)
+      : k(recode_kernel(pl)), scalars(scalars), d(pl.d), digits(sl.ws.digits.p), colsum(sl.ws.colsum.as<uint32_t>()),
+        nb(k.nargs == 6 ? narrow_bias(pl.d) : NarrowBias{}), err(sl.ws.err.as<uint32_t>()) {
+    if (k.nargs == 4) argv[4] = argv[5] = nullptr;
+  }
+  RecodeArgs(const RecodeArgs&) = delete;
+  void launch(hipStream_t s) {
+    const size_t lds = ((size_t)d.Wr * d.nbc + d.Wr) * 4;  // histogram + window totals
+    (void)hipLaunchKernel(k.fn, dim3(grid_for(d.n, RC_SPAN), d.nm), dim3(RC_THREADS), argv, lds, s);
+  }
+};
+
+// k_part_scatter's instantiation for a plan's code width and subset kind (MsmDims::sub); the subset
+// variants take one more argument, the index buffer.
+const void* scatter_kernel(const MsmDims& d) {
+  using I = const uint32_t*;
+#define SCATTER_ROW(T) \
+  {kfn(k_part_scatter<T>), kfn(k_part_scatter<T, MSM_SUB_RANGE, I>), kfn(k_part_scatter<T, MSM_SUB_INDEXED, I>)}
+  static const void* const K[2][3] = {SCATTER_ROW(uint16_t), SCATTER_ROW(uint32_t)};
+#undef SCATTER_ROW
+  static_assert(MSM_SUB_NONE == 0 && MSM_SUB_RANGE == 1 && MSM_SUB_INDEXED == 2, "K's columns");
+  return K[d.c > 16][d.sub];
+}
+
+// The first reduction stage's kernels, a row per chunk length of RED1_LENGTHS (host_plan.h).
+struct Red1Row {
+  uint32_t L;
+  decltype(&k_bucket_reduce_1<8>) lanes, pairs;  // one lane per chunk; lane pairs (MSM_RED1_PAIRS)
+  decltype(&k_bucket_reduce_1g<8>) fold;         // with the second stage's group trees (MSM_RED_FOLD)
+};
+#define RED1_ROW(L) {L, k_bucket_reduce_1<L>, k_bucket_reduce_1p<L>, k_bucket_reduce_1g<L>}
+const Red1Row RED1_TABLE[] = {RED1_LENGTHS(RED1_ROW)};
+#undef RED1_ROW
+const Red1Row* red1_row(uint32_t L) {
+  for (const Red1Row& r : RED1_TABLE)
+    if (r.L == L) return &r;
+  return nullptr;
+}
+
+// The stages of one launch sequence (enqueue_msm puts them in order), over what they share: the plan,
+// the slot whose workspace they work in, their stream and the point-record buffer.
+struct LaunchCtx {
+  const Plan& pl;
+  const MsmDims& d;
+  Slot& sl;
+  Workspace& w;
+  hipStream_t s;
+  uint32_t* pts;
+  static uint32_t* u32(const Buf& b) { return b.as<uint32_t>(); }
+  const uint32_t* total() const { return u32(w.bin_base) + d.nbins; }  // the launch's entry count
+  // The preparation, on `ps`: the launch's stream, or the slot's aux stream where it forks.
+  void launch_prepare(const BatchPtrs& in, hipStream_t ps) const { PrepareArgs(pl, sl, in, pts).launch(ps); }
+  // The sort: recode (digits and bin counts), coarse scatter, fine sort.
+  void launch_recode(const BatchPtrs& d_scalars) const { RecodeArgs(pl, sl, d_scalars).launch(s); }
+  void launch_scatter() const {
+    MsmDims dd = d;
+    void* digits = w.digits.p;
+    uint32_t *colsum = u32(w.colsum), *bin_cur = u32(w.bin_cur), *bin_base = u32(w.bin_base);
+    uint32_t* part_entry = u32(w.part_entry);
+    uint16_t* part_fine = w.part_fine.as<uint16_t>();
+    // a subset launch on a handle's records: the record-mapping variants read the slot's own index
+    // buffer (a fixed address: the captured node never holds a caller's pointer)
+    const uint32_t* sub_idx = w.sub_idx.as<uint32_t>();
+    void* args[8] = {&digits, &dd, &colsum, &bin_cur, &bin_base, &part_entry, &part_fine};
+    if (d.sub != MSM_SUB_NONE) args[7] = &sub_idx;
+    (void)hipLaunchKernel(scatter_kernel(d), dim3(d.nch, d.W), dim3(PT_THREADS), args, (size_t)d.nbc * 12, s);
+  }
+  void launch_fine_sort() const {
+    hipLaunchKernelGGL(k_fine_sort, dim3(d.nbins), dim3(FS_THREADS), 0, s, u32(w.part_entry),
+                       w.part_fine.as<uint16_t>(), u32(w.bin_base), d, pl.K, u32(w.sorted_entry),
+                       u32(w.bucket_start), u32(w.run_key), u32(w.colsum), u32(w.bin_cur));
+#ifdef MSM_GAP_KERNEL
+    hipLaunchKernelGGL(k_gap, dim3(MSM_GAP_KERNEL), dim3(64), 0, s, u32(w.err));
+#endif
+  }
+  // The accumulation: k_accumulate, or a dense plan's k_dense_segments, k_dense_units and k_dense_fold.
+  void launch_accumulation() const {
+    if (!pl.dense) {
+      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(pl.runs_max, ACC_THREADS)), dim3(ACC_THREADS), 0, s, pts,
+                         u32(w.sorted_entry), u32(w.bucket_start), u32(w.run_key), total(), pl.K, d.W * d.B,
+                         u32(w.buckets), u32(w.lead_val), u32(w.lead_open), u32(w.cross_key), u32(w.skew_list),
+                         u32(w.g_head), u32(w.g_hkey), u32(w.g_tkey));
+      return;
+    }
+    // The segment map is data: k_dense_segments rebuilds it from this launch's bucket_start, so a
+    // replayed graph holds nothing of any launch's bucket sizes, only the plan's grid bound.
+    const uint32_t nkeys = d.W * d.B;
+    const uint32_t ncross = (uint32_t)(pl.runs_max / ACC_THREADS + 2);  // ensure_workspace's cross_key words
+    hipLaunchKernelGGL(k_dense_segments, dim3(1), dim3(DS_THREADS), 0, s, u32(w.bucket_start), nkeys, 64u * pl.dense_E,
+                       u32(w.seg_base), u32(w.unit_key), pl.dense_units, u32(w.cross_key), pl.K * ACC_THREADS, ncross);
+    hipLaunchKernelGGL(k_dense_units, dim3(grid_for(pl.dense_units, DU_THREADS / 64)), dim3(DU_THREADS), 0, s, pts,
+                       u32(w.sorted_entry), u32(w.bucket_start), u32(w.seg_base), u32(w.unit_key), pl.dense_E, nkeys,
+                       pl.dense_units, u32(w.buckets), u32(w.partials));
+    hipLaunchKernelGGL(k_dense_fold, dim3(nkeys), dim3(DF_THREADS), 0, s, u32(w.seg_base), u32(w.partials),
+                       pl.dense_units, u32(w.buckets));
+  }
+  // The bucket joins of skewed launches.
+  void launch_joins() const {
+    hipLaunchKernelGGL(k_chain_join, dim3(CJ_GRID), dim3(ACC_THREADS), 0, s, u32(w.skew_list), total(), pl.K,
+                       u32(w.g_head), u32(w.g_hkey), u32(w.g_tkey), u32(w.buckets), u32(w.lead_val), u32(w.lead_open),
+                       u32(w.lead_flag));
+    hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(LS_THREADS), 0, s, u32(w.lead_val), u32(w.lead_open),
+                       u32(w.lead_flag), total(), pl.K);
+  }
+  // The reduction.  Its first stage, from the plan's row of RED1_TABLE: folded with the second stage's
+  // group trees (red_fold), on lane pairs (red1_pairs), or one lane per chunk.
+  bool folds() const { return red_fold() && red2_tree(pl); }
+  void launch_reduce_1(const Red1Row& row) const {
+    const uint32_t G = red2_groups(pl);
+    const bool pairs = red1_pairs();
+    if (folds())
+      hipLaunchKernelGGL(row.fold, dim3(d.W * G), dim3(RG_CH), 0, s, u32(w.buckets), u32(w.bucket_start), d, pl.K,
+                         pl.nchunks, G, u32(w.cross_key), u32(w.lead_val), u32(w.red_G));
+    else
+      hipLaunchKernelGGL(pairs ? row.pairs : row.lanes,
+                         dim3(grid_for((size_t)d.W * pl.nchunks * (pairs ? 2 : 1), RED1_THREADS)), dim3(RED1_THREADS),
+                         0, s, u32(w.buckets), u32(w.bucket_start), d, pl.K, pl.nchunks, u32(w.cross_key),
+                         u32(w.lead_val), u32(w.red_U), u32(w.red_T));
+  }
+  // Its second stage; the terms land in the slot's h_out.  `joins`: the bucket joins ran before it.
+  void launch_reduce_2(bool joins) const {
+    uint32_t* out = reinterpret_cast<uint32_t*>(sl.h_out_dev);
+    if (!red2_tree(pl)) {
+      hipLaunchKernelGGL(k_bucket_reduce_2, dim3(d.W * pl.nterms), dim3(RED2_THREADS), 0, s, u32(w.red_U),
+                         u32(w.red_T), pl.nchunks, pl.nv, pl.nterms, u32(w.err), u32(w.lead_flag), u32(w.skew_list),
+                         total(), joins ? 1u : 0u, u32(w.bucket_start), d.B, out);
+      return;
+    }
+    const uint32_t G = red2_groups(pl);
+    if (!folds())
+      hipLaunchKernelGGL(k_red2_groups, dim3(d.W * G), dim3(4 * RG_CH), 0, s, u32(w.red_U), u32(w.red_T), pl.nchunks,
+                         G, u32(w.bucket_start), d.B, u32(w.red_G));
+    // one lane quad per group point of the widest term (a wave at least): 2^16 pipelined
+    // 0.117-0.120 against 0.125-0.131 ms per MSM with 64 quads throughout
+    uint32_t gp = 16;
+    while (gp < G) gp <<= 1;
+    hipLaunchKernelGGL(k_red2_terms, dim3(d.W * pl.nterms), dim3(4 * gp), 0, s, u32(w.red_G), G, pl.nv, pl.nterms,
+                       u32(w.err), u32(w.lead_flag), u32(w.skew_list), total(), joins ? 1u : 0u, u32(w.bucket_start),
+                       d.B, out);
+  }
+};
+
 // Enqueue parts of the device pipeline on `s`; the reduced per-window terms land in the slot's
 // h_out.  `pts` is the point-record buffer (the slot's own, or a shared base vector's).
-// With `acc_events` (eager launches only), the accumulation -- k_accumulate, or a dense plan's
-// k_dense_segments, k_dense_units and k_dense_fold -- runs between the slot's ev_acc0 / ev_acc1
-// (2), or is followed by ev_acc1 alone (1);
+// With `acc_events` (eager launches only), the accumulation runs between the slot's ev_acc0 /
+// ev_acc1 (2), or is followed by ev_acc1 alone (1);
 // captured graphs get the same events as record nodes (add_acc_event_nodes).
 int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const BatchPtrs& d_scalars, int si,
                 hipStream_t s, int parts, uint32_t* pts, int acc_events = 0) {
-  const MsmDims& d = pl.d;
   Slot& sl = c->slot[si];
-  Workspace& w = sl.ws;
+  const LaunchCtx x{pl, pl.d, sl, sl.ws, s, pts};
   const bool prof = c->profiling == 1;
   auto mark = [&](int ph) {
     if (prof) hipEventRecord(c->ev[ph], s);
   };
-  const uint32_t* total = w.bin_base.as<uint32_t>() + d.nbins;
-  const unsigned rgrid = grid_for(pl.runs_max, ACC_THREADS);
+  const Red1Row* red1 = red1_row(pl.L);
+  if ((parts & PART_POST) && !red1) return MSM_ERR_INVALID_ARG;  // (make_plan gives no such L)
   // The preparation reads only the points and the sort only the scalars: with both in this
   // sequence the preparation forks onto the slot's aux stream (a parallel branch of the captured
   // graph) and rejoins before the accumulation, so a lone MSM's sort no longer waits behind it.
   // (Profiling mode 1 keeps them in order, one event between every phase.)
   const bool fork = (parts & PART_PREP) && (parts & PART_SORT) && !prof && slot_forks(sl);
-  auto prepare = [&](hipStream_t ps) {
-    hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(d.n, PP_THREADS), d.shared ? 1 : d.nm), dim3(PP_THREADS), 0, ps,
-                       d_points, pts, d.n, w.err.as<uint32_t>(), prep_nt((size_t)(d.shared ? 1 : d.nm) * d.n), pl.pfmt);
-  };
   if (parts & PART_PREP) {
     mark(PH_START);
-    hipStream_t ps = s;
     if (fork) {
       HIPCHECK(hipEventRecord(sl.ev_fork, s));
       HIPCHECK(hipStreamWaitEvent(sl.aux, sl.ev_fork, 0));
-      ps = sl.aux;
     }
-    prepare(ps);
+    x.launch_prepare(d_points, fork ? sl.aux : s);
     if (fork) HIPCHECK(hipEventRecord(sl.ev_join, sl.aux));
     mark(PH_PREPARE);
   }
@@ -257,139 +392,30 @@ int enqueue_msm(DevCtx* c, const Plan& pl, const BatchPtrs& d_points, const Batc
       mark(PH_START);
       mark(PH_PREPARE);
     }
-    launch_recode(pl, d_scalars, w.digits.p, w.colsum.as<uint32_t>(), w.err.as<uint32_t>(), s);
+    x.launch_recode(d_scalars);
     mark(PH_RECODE);
     mark(PH_SCAN);
-    if (d.sub != MSM_SUB_NONE) {
-      // a subset launch on a handle's records: the scatter's record-mapping variants, reading the
-      // slot's own index buffer (a fixed address: the captured node never holds a caller's pointer)
-      auto scatter = [&](auto kern, auto* dig) {
-        hipLaunchKernelGGL(kern, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s, dig, d,
-                           w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(), w.bin_base.as<uint32_t>(),
-                           w.part_entry.as<uint32_t>(), w.part_fine.as<uint16_t>(),
-                           static_cast<const uint32_t*>(w.sub_idx.as<uint32_t>()));
-      };
-      const bool ix = d.sub == MSM_SUB_INDEXED;
-      if (d.c <= 16) {
-        const uint16_t* dig = w.digits.as<uint16_t>();
-        if (ix) scatter(k_part_scatter<uint16_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
-        else scatter(k_part_scatter<uint16_t, MSM_SUB_RANGE, const uint32_t*>, dig);
-      } else {
-        const uint32_t* dig = w.digits.as<uint32_t>();
-        if (ix) scatter(k_part_scatter<uint32_t, MSM_SUB_INDEXED, const uint32_t*>, dig);
-        else scatter(k_part_scatter<uint32_t, MSM_SUB_RANGE, const uint32_t*>, dig);
-      }
-    } else if (d.c <= 16) {
-      hipLaunchKernelGGL(k_part_scatter<uint16_t>, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s,
-                         w.digits.as<uint16_t>(), d, w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(),
-                         w.bin_base.as<uint32_t>(), w.part_entry.as<uint32_t>(),
-                         w.part_fine.as<uint16_t>());
-    } else {
-      hipLaunchKernelGGL(k_part_scatter<uint32_t>, dim3(d.nch, d.W), dim3(PT_THREADS), (size_t)d.nbc * 12, s,
-                         w.digits.as<uint32_t>(), d, w.colsum.as<uint32_t>(), w.bin_cur.as<uint32_t>(),
-                         w.bin_base.as<uint32_t>(), w.part_entry.as<uint32_t>(),
-                         w.part_fine.as<uint16_t>());
-    }
+    x.launch_scatter();
     mark(PH_SCATTER);
-    hipLaunchKernelGGL(k_fine_sort, dim3(d.nbins), dim3(FS_THREADS), 0, s, w.part_entry.as<uint32_t>(),
-                       w.part_fine.as<uint16_t>(), w.bin_base.as<uint32_t>(), d, pl.K, w.sorted_entry.as<uint32_t>(),
-                       w.bucket_start.as<uint32_t>(), w.run_key.as<uint32_t>(), w.colsum.as<uint32_t>(),
-                       w.bin_cur.as<uint32_t>());
-#ifdef MSM_GAP_KERNEL
-    hipLaunchKernelGGL(k_gap, dim3(MSM_GAP_KERNEL), dim3(64), 0, s, w.err.as<uint32_t>());
-#endif
+    x.launch_fine_sort();
     mark(PH_FINE);
   }
   if (fork) HIPCHECK(hipStreamWaitEvent(s, sl.ev_join, 0));
   if ((parts & PART_ACC) && acc_events == 2) HIPCHECK(hipEventRecord(sl.ev_acc0, s));
-  if ((parts & PART_ACC) && pl.dense) {
-    // The segment map is data: k_dense_segments rebuilds it from this launch's bucket_start, so a
-    // replayed graph holds nothing of any launch's bucket sizes, only the plan's grid bound.
-    const uint32_t nkeys = d.W * d.B;
-    const uint32_t ncross = (uint32_t)(pl.runs_max / ACC_THREADS + 2);  // ensure_workspace's cross_key words
-    hipLaunchKernelGGL(k_dense_segments, dim3(1), dim3(DS_THREADS), 0, s, w.bucket_start.as<uint32_t>(), nkeys,
-                       64u * pl.dense_E, w.seg_base.as<uint32_t>(), w.unit_key.as<uint32_t>(), pl.dense_units,
-                       w.cross_key.as<uint32_t>(), pl.K * ACC_THREADS, ncross);
-    hipLaunchKernelGGL(k_dense_units, dim3(grid_for(pl.dense_units, DU_THREADS / 64)), dim3(DU_THREADS), 0, s, pts,
-                       w.sorted_entry.as<uint32_t>(), w.bucket_start.as<uint32_t>(), w.seg_base.as<uint32_t>(),
-                       w.unit_key.as<uint32_t>(), pl.dense_E, nkeys, pl.dense_units, w.buckets.as<uint32_t>(),
-                       w.partials.as<uint32_t>());
-    hipLaunchKernelGGL(k_dense_fold, dim3(nkeys), dim3(DF_THREADS), 0, s, w.seg_base.as<uint32_t>(),
-                       w.partials.as<uint32_t>(), pl.dense_units, w.buckets.as<uint32_t>());
-    mark(PH_ACCUM);
-  } else if (parts & PART_ACC) {
-    hipLaunchKernelGGL(k_accumulate, dim3(rgrid), dim3(ACC_THREADS), 0, s, pts, w.sorted_entry.as<uint32_t>(),
-                       w.bucket_start.as<uint32_t>(), w.run_key.as<uint32_t>(), total, pl.K, d.W * d.B,
-                       w.buckets.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.lead_open.as<uint32_t>(),
-                       w.cross_key.as<uint32_t>(), w.skew_list.as<uint32_t>(), w.g_head.as<uint32_t>(),
-                       w.g_hkey.as<uint32_t>(), w.g_tkey.as<uint32_t>());
+  if (parts & PART_ACC) {
+    x.launch_accumulation();
     mark(PH_ACCUM);
   }
   if ((parts & PART_ACC) && acc_events) HIPCHECK(hipEventRecord(sl.ev_acc1, s));
   // profiling mode 1 keeps the joins in line (its per-phase timings include them)
   // (a dense launch has none: no bucket continues in another lane's run, skew_list and lead_flag stay clear)
   const bool joins = ((parts & PART_JOIN) || prof) && !pl.dense;
-  if ((parts & PART_POST) && joins) {
-    hipLaunchKernelGGL(k_chain_join, dim3(CJ_GRID), dim3(ACC_THREADS), 0, s, w.skew_list.as<uint32_t>(), total, pl.K,
-                       w.g_head.as<uint32_t>(), w.g_hkey.as<uint32_t>(), w.g_tkey.as<uint32_t>(),
-                       w.buckets.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.lead_open.as<uint32_t>(),
-                       w.lead_flag.as<uint32_t>());
-    hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(LS_THREADS), 0, s, w.lead_val.as<uint32_t>(),
-                       w.lead_open.as<uint32_t>(), w.lead_flag.as<uint32_t>(), total, pl.K);
-  }
+  if ((parts & PART_POST) && joins) x.launch_joins();
   if (parts & PART_POST) {
     mark(PH_FIXUP);
-    const bool fold = red_fold() && red2_tree(pl);
-    if (fold) {
-      const uint32_t G = red2_groups(pl);
-      auto red1g = pl.L == 4    ? k_bucket_reduce_1g<4>
-                   : pl.L == 9  ? k_bucket_reduce_1g<9>
-                   : pl.L == 10 ? k_bucket_reduce_1g<10>
-                   : pl.L == 12 ? k_bucket_reduce_1g<12>
-                   : pl.L == 16 ? k_bucket_reduce_1g<16>
-                   : pl.L == 17 ? k_bucket_reduce_1g<17>
-                   : pl.L == 20 ? k_bucket_reduce_1g<20>
-                                : k_bucket_reduce_1g<8>;
-      hipLaunchKernelGGL(red1g, dim3(d.W * G), dim3(RG_CH), 0, s, w.buckets.as<uint32_t>(),
-                         w.bucket_start.as<uint32_t>(), d, pl.K, pl.nchunks, G, w.cross_key.as<uint32_t>(),
-                         w.lead_val.as<uint32_t>(), w.red_G.as<uint32_t>());
-    }
-    const bool pairs = red1_pairs();
-    auto red1 = pl.L == 4    ? (pairs ? k_bucket_reduce_1p<4> : k_bucket_reduce_1<4>)
-                : pl.L == 9  ? (pairs ? k_bucket_reduce_1p<9> : k_bucket_reduce_1<9>)
-                : pl.L == 10 ? (pairs ? k_bucket_reduce_1p<10> : k_bucket_reduce_1<10>)
-                : pl.L == 12 ? (pairs ? k_bucket_reduce_1p<12> : k_bucket_reduce_1<12>)
-                : pl.L == 16 ? (pairs ? k_bucket_reduce_1p<16> : k_bucket_reduce_1<16>)
-                : pl.L == 17 ? (pairs ? k_bucket_reduce_1p<17> : k_bucket_reduce_1<17>)
-                : pl.L == 20 ? (pairs ? k_bucket_reduce_1p<20> : k_bucket_reduce_1<20>)
-                             : (pairs ? k_bucket_reduce_1p<8> : k_bucket_reduce_1<8>);
-    if (!fold)
-    hipLaunchKernelGGL(red1, dim3(grid_for((size_t)d.W * pl.nchunks * (pairs ? 2 : 1), RED1_THREADS)), dim3(RED1_THREADS), 0, s,
-                       w.buckets.as<uint32_t>(), w.bucket_start.as<uint32_t>(), d, pl.K, pl.nchunks,
-                       w.cross_key.as<uint32_t>(), w.lead_val.as<uint32_t>(), w.red_U.as<uint32_t>(),
-                       w.red_T.as<uint32_t>());
+    x.launch_reduce_1(*red1);
     mark(PH_RED1);
-    if (red2_tree(pl)) {
-      const uint32_t G = red2_groups(pl);
-      if (!fold)
-        hipLaunchKernelGGL(k_red2_groups, dim3(d.W * G), dim3(4 * RG_CH), 0, s, w.red_U.as<uint32_t>(),
-                           w.red_T.as<uint32_t>(), pl.nchunks, G, w.bucket_start.as<uint32_t>(), d.B,
-                           w.red_G.as<uint32_t>());
-      // one lane quad per group point of the widest term (a wave at least): 2^16 pipelined
-      // 0.117-0.120 against 0.125-0.131 ms per MSM with 64 quads throughout
-      uint32_t gp = 16;
-      while (gp < G) gp <<= 1;
-      hipLaunchKernelGGL(k_red2_terms, dim3(d.W * pl.nterms), dim3(4 * gp), 0, s,
-                         w.red_G.as<uint32_t>(), G,
-                         pl.nv, pl.nterms, w.err.as<uint32_t>(), w.lead_flag.as<uint32_t>(),
-                         w.skew_list.as<uint32_t>(), total, joins ? 1u : 0u, w.bucket_start.as<uint32_t>(), d.B,
-                         reinterpret_cast<uint32_t*>(sl.h_out_dev));
-    } else {
-      hipLaunchKernelGGL(k_bucket_reduce_2, dim3(d.W * pl.nterms), dim3(RED2_THREADS), 0, s, w.red_U.as<uint32_t>(),
-                         w.red_T.as<uint32_t>(), pl.nchunks, pl.nv, pl.nterms, w.err.as<uint32_t>(),
-                         w.lead_flag.as<uint32_t>(), w.skew_list.as<uint32_t>(), total, joins ? 1u : 0u,
-                         w.bucket_start.as<uint32_t>(), d.B, reinterpret_cast<uint32_t*>(sl.h_out_dev));
-    }
+    x.launch_reduce_2(joins);
     mark(PH_RED2);
     mark(PH_READBACK);
   }
@@ -406,9 +432,6 @@ int add_acc_event_nodes(hipGraph_t g, Slot& sl, bool both) {
   if (hipGraphGetNodes(g, nullptr, &num) != hipSuccess || num == 0) return MSM_ERR_HIP;
   std::vector<hipGraphNode_t> nodes(num);
   if (hipGraphGetNodes(g, nodes.data(), &num) != hipSuccess) return MSM_ERR_HIP;
-  const void* f_acc = reinterpret_cast<const void*>(&k_accumulate);
-  const void* f_seg = reinterpret_cast<const void*>(&k_dense_segments);
-  const void* f_fold = reinterpret_cast<const void*>(&k_dense_fold);
   hipGraphNode_t acc = nullptr, acc_end = nullptr;  // the accumulation's first and last node
   for (hipGraphNode_t nd : nodes) {
     hipGraphNodeType ty;
@@ -416,9 +439,9 @@ int add_acc_event_nodes(hipGraph_t g, Slot& sl, bool both) {
     if (hipGraphNodeGetType(nd, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel ||
         hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess)
       continue;
-    if (kp.func == f_acc) acc = acc_end = nd;
-    if (kp.func == f_seg) acc = nd;
-    if (kp.func == f_fold) acc_end = nd;
+    if (kp.func == kfn(k_accumulate)) acc = acc_end = nd;
+    if (kp.func == kfn(k_dense_segments)) acc = nd;
+    if (kp.func == kfn(k_dense_fold)) acc_end = nd;
   }
   if (!acc || !acc_end) return MSM_ERR_HIP;
   size_t nd = 0, nx = 0;
@@ -478,13 +501,12 @@ int find_input_nodes(Segment& sg) {
   if (hipGraphGetNodes(sg.graph, nullptr, &num) != hipSuccess || num == 0) return MSM_ERR_HIP;
   std::vector<hipGraphNode_t> nodes(num);
   if (hipGraphGetNodes(sg.graph, nodes.data(), &num) != hipSuccess) return MSM_ERR_HIP;
-  const void* f_prep = reinterpret_cast<const void*>(&k_prepare_points);
   for (hipGraphNode_t nd : nodes) {
     hipGraphNodeType ty;
     if (hipGraphNodeGetType(nd, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
     hipKernelNodeParams kp{};
     if (hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess) continue;
-    if (kp.func == f_prep) {
+    if (kp.func == kfn(k_prepare_points)) {
       sg.n_prep = nd;
       sg.p_prep = kp;
     } else if (is_recode_kernel(kp.func)) {
@@ -501,35 +523,19 @@ bool same_ptrs(const BatchPtrs& a, const BatchPtrs& b) { return memcmp(&a, &b, s
 // Point an instantiated segment at new input buffers (kernel-node argument update, no
 // re-capture).
 int repoint_inputs(const Plan& pl, Slot& sl, Segment& sg, const BatchPtrs& d_points, const BatchPtrs& d_scalars) {
-  const MsmDims& d = pl.d;
-  Workspace& w = sl.ws;
-  if (sg.n_prep && !same_ptrs(sg.in_pts, d_points)) {
-    BatchPtrs wire = d_points;
-    uint32_t* ptsb = const_cast<uint32_t*>(sg.pts_buf);
-    uint32_t n = d.n;
-    uint32_t* err = w.err.as<uint32_t>();
-    uint32_t nt = prep_nt((size_t)(d.shared ? 1 : d.nm) * d.n);
-    uint32_t fmt = pl.pfmt;
-    void* a_prep[] = {&wire, &ptsb, &n, &err, &nt, &fmt};
-    hipKernelNodeParams kp = sg.p_prep;
-    kp.kernelParams = a_prep;
+  auto set_args = [&](hipGraphNode_t nd, hipKernelNodeParams kp, void** argv) {
+    kp.kernelParams = argv;
     kp.extra = nullptr;
-    if (hipGraphExecKernelNodeSetParams(sg.exec, sg.n_prep, &kp) != hipSuccess) return MSM_ERR_HIP;
+    return hipGraphExecKernelNodeSetParams(sg.exec, nd, &kp) == hipSuccess;
+  };
+  if (sg.n_prep && !same_ptrs(sg.in_pts, d_points)) {
+    PrepareArgs a(pl, sl, d_points, const_cast<uint32_t*>(sg.pts_buf));
+    if (!set_args(sg.n_prep, sg.p_prep, a.argv)) return MSM_ERR_HIP;
     sg.in_pts = d_points;
   }
   if (sg.n_recode && !same_ptrs(sg.in_sc, d_scalars)) {
-    BatchPtrs scal = d_scalars;
-    MsmDims dd = d;
-    void* digits = w.digits.p;
-    uint32_t* hist = w.colsum.as<uint32_t>();
-    // (k_recode_narrow takes two more arguments; the other recodes read the first four)
-    NarrowBias nb = d.sw ? narrow_bias(d) : NarrowBias{};
-    uint32_t* err = w.err.as<uint32_t>();
-    void* a_rc[] = {&scal, &dd, &digits, &hist, &nb, &err};
-    hipKernelNodeParams kr = sg.p_recode;
-    kr.kernelParams = a_rc;
-    kr.extra = nullptr;
-    if (hipGraphExecKernelNodeSetParams(sg.exec, sg.n_recode, &kr) != hipSuccess) return MSM_ERR_HIP;
+    RecodeArgs a(pl, sl, d_scalars);
+    if (!set_args(sg.n_recode, sg.p_recode, a.argv)) return MSM_ERR_HIP;
     sg.in_sc = d_scalars;
   }
   return MSM_OK;

@@ -21,22 +21,25 @@ uint32_t pipelined_window(size_t n) {
   return msm_best_window(n);
 }
 
-// Chunk lengths k_bucket_reduce_1 is instantiated for.
-constexpr uint32_t RED1_LS[] = {8, 9, 10, 12, 16, 17, 20};
+// The chunk lengths the first reduction stage is instantiated for, written out here alone (RED1_TABLE of
+// host_launch.h has a row of kernels per entry); RED1_KNOB_ONLY is reachable only through MSM_RED_L.
+#define RED1_LENGTHS(X) X(4), X(8), X(9), X(10), X(12), X(16), X(17), X(20)
+constexpr uint32_t RED1_LS[] = {RED1_LENGTHS(uint32_t)};
+constexpr uint32_t RED1_KNOB_ONLY = 4;
+bool red_l_known(uint32_t L) { return std::count(std::begin(RED1_LS), std::end(RED1_LS), L) != 0; }
 
 // Buckets per k_bucket_reduce_1 lane: the shortest chain (L) for which the live lanes of every
 // MSM's main windows fit in one wave per SIMD (see msm_kernels.hip); 16 if none does.  Measured
 // (profiles/r2i_ks17*): c = 15 with two MSMs per launch ran L = 8 as 1,056 waves -- two chains on
 // some SIMDs, 140 us -- where L = 9 fits.  Chains past 16 serve the four-MSM launches of small
-// sizes (2^17: L = 17, 994 waves).  MSM_RED_L overrides (any of RED1_LS, or 4).
+// sizes (2^17: L = 17, 994 waves).  MSM_RED_L overrides (any of RED1_LS).
 uint32_t bucket_reduce_L(const MsmDims& d, const DevShape& sh) {
   const int n_cu = sh.n_cu;
   const uint32_t l_env = knob_red_l();
-  if (l_env == 4) return 4;
-  for (uint32_t L : RED1_LS)
-    if (l_env == L) return L;
+  if (red_l_known(l_env)) return l_env;
   const uint64_t simds = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 256);
   for (uint32_t L : RED1_LS) {
+    if (L == RED1_KNOB_ONLY) continue;
     const uint32_t nchunks = (d.B + L - 1) / L;
     uint64_t lanes = 0;
     for (uint32_t l = 0; l < d.Wr; l++) lanes += red1_live_chunks(d, L, nchunks, d.w0 + l);

@@ -507,10 +507,7 @@ int msm_test_records(uint32_t fmt, const uint32_t* in, size_t n, uint32_t* recor
   HIPCHECK(derr.alloc(4));
   HIPCHECK(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice));
   HIPCHECK(hipMemset(derr.p, 0, 4));
-  BatchPtrs bp{};
-  bp.p[0] = din.p;
-  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(n, PP_THREADS), 1), dim3(PP_THREADS), 0, 0, bp, dpts.p, (uint32_t)n,
-                     derr.p, 0u, fmt);
+  launch_prepare(din.p, dpts.p, (uint32_t)n, derr.p, 0u, nullptr, fmt);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpy(records, dpts.p, n * PRE_WORDS * 4, hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(err, derr.p, 4, hipMemcpyDeviceToHost));
@@ -937,14 +934,6 @@ int msm_test_acc_state(uint32_t info[8], uint32_t* bucket_start, uint32_t* run_k
 }
 
 // ---- the bucket reduction's state and maps (tests/test_gpu_red_state.py, tests/_red_model.py) ------
-// Whether L is a chunk length the reduction is instantiated for (RED1_LS, or 4).
-static bool red_l_known(uint32_t L) {
-  if (L == 4) return true;
-  for (uint32_t l : RED1_LS)
-    if (l == L) return true;
-  return false;
-}
-
 // What the reduction of the last lone MSM of the default device's slot 0 left behind, read back after
 // the call as msm_test_acc_state does: nothing is launched, and every array may be null (with its
 // count 0).  info = {L, nchunks, ngroups, nv, nterms, W, B, the second stage that ran (0: k_red2_groups
