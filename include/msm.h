@@ -780,6 +780,59 @@ int msm_fr_dot(const uint32_t* a, const uint32_t* b /* NULL: sum of a */, size_t
 int msm_fr_dot_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t in_form, uint32_t out_form,
                       const msm_opts* opts, void* hip_stream, uint32_t out[8]);
 
+/* Scalar-field vectors, second set: what a prover or verifier still did on the host with an Fr column --
+ * batch inverses (arkworks' batch_inversion_and_mul: the x^-1 of every folding round, the denominators of
+ * a permutation or lookup argument, Lagrange and barycentric weights), running products and sums (the grand
+ * product z_0 = 1, z_(i+1) = z_i f_i / g_i of a permutation argument, the running sums of a log-derivative
+ * lookup) and tensor products of k pairs (the verifier's s_i = prod_j x_j^(+-1) after k folds, the
+ * eq(r, .) table prod_j (r_j or 1 - r_j) that weights a vector table's row commitments; msm_fr_powers is
+ * the pairs (1, g^(2^j))).  The element forms, the common rules above and their error codes hold for
+ * every entry here: opts carries the device only, device vectors are 16-byte aligned, m < 2^32, m = 0
+ * returns MSM_OK and touches nothing, a Montgomery input >= r is refused by the host entries before
+ * anything is uploaded and by the device entries after the launch, results are complete on return and
+ * canonical.  `c` is a host array of 8 wire words in both entries of a pair, any integer < 2^256, NULL
+ * meaning 1, as msm_fr_powers' c.  DESIGN.md §9 has the products per element and the measured times.
+ *
+ * msm_fr_inverse*: out_i = c * a_i^-1 mod r for i < m, and out_i = 0 where a_i = 0 mod r (arkworks'
+ * convention: zeros stay zeros and change nothing else; a wire input that is a non-zero multiple of r is
+ * such a zero).  `out` may be exactly `a`; any other overlap is MSM_ERR_INVALID_ARG from the device entry,
+ * decided from the pointer values.  Montgomery's trick per tile of 2048 elements: the elements of a tile
+ * are multiplied together (a zero as 1), ONE inversion per tile -- t^(r-2) by a fixed 4-bit window over the
+ * constant exponent, 249 squarings and 72 products, no branch on the data -- and a walk back: three
+ * products per element, and c and the output's form folded into the tile's inverse.
+ *
+ * msm_fr_scan*: the inclusive running product out_i = c * prod_(j<=i) a_j, or with MSM_FR_SCAN_SUM the
+ * running sum out_i = sum_(j<=i) a_j (c must then be NULL: MSM_ERR_INVALID_ARG).  MSM_FR_SCAN_EXCLUSIVE
+ * takes j < i instead: out_0 = c (1 if NULL) for a product, 0 for a sum.  An unknown flag bit is
+ * MSM_ERR_INVALID_ARG.  `out` may be exactly `a`, as above.  Three launches -- every span of the vector
+ * folded to one total (at most 1024 spans, each a whole number of tiles), one workgroup turning the totals
+ * into carries, every span scanned again from its carry -- and NO waiting between workgroups inside a
+ * kernel: no look-back, no flag to spin on, no grid barrier, so nothing depends on which workgroups are
+ * resident.  Three operations per element.
+ *
+ * msm_fr_tensor*: out_i = c * prod_(j<k) (bit_j(i) ? hi_j : lo_j) mod r for i < 2^k, bit 0 the least
+ * significant, 0 <= k <= MSM_FR_TENSOR_MAX_K (more: MSM_ERR_INVALID_ARG; k = 0 gives the one element c).
+ * lo and hi are host arrays [k][8] of wire words in both entries, any integers < 2^256 (NULL with k > 0:
+ * MSM_ERR_INVALID_ARG); out holds 2^k elements in out_form.  A lane multiplies out the low k - 4 bits and
+ * steps through the 16 products of the top four, which the host prepares: k + 12 products in a chain at
+ * most, one product per element stored. */
+#define MSM_FR_SCAN_SUM       1u  /* running sum instead of running product         */
+#define MSM_FR_SCAN_EXCLUSIVE 2u  /* out_i over j < i instead of j <= i             */
+#define MSM_FR_TENSOR_MAX_K 31u
+int msm_fr_inverse(const uint32_t* a, const uint32_t* c_be /* [8], or NULL: 1 */, size_t m, uint32_t in_form,
+                   uint32_t out_form, const msm_opts* opts, uint32_t* out /* [m][8] */);
+int msm_fr_inverse_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t in_form, uint32_t out_form,
+                          const msm_opts* opts, void* hip_stream, uint32_t* d_out);
+int msm_fr_scan(const uint32_t* a, const uint32_t* c_be /* [8], or NULL: 1; NULL for a sum */, size_t m, uint32_t flags,
+                uint32_t in_form, uint32_t out_form, const msm_opts* opts, uint32_t* out /* [m][8] */);
+int msm_fr_scan_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t flags, uint32_t in_form,
+                       uint32_t out_form, const msm_opts* opts, void* hip_stream, uint32_t* d_out);
+int msm_fr_tensor(const uint32_t* lo_be /* [k][8] */, const uint32_t* hi_be /* [k][8] */, uint32_t k,
+                  const uint32_t* c_be /* [8], or NULL: 1 */, uint32_t out_form, const msm_opts* opts,
+                  uint32_t* out /* [2^k][8] */);
+int msm_fr_tensor_device(const uint32_t* lo_be, const uint32_t* hi_be, uint32_t k, const uint32_t* c_be, uint32_t out_form,
+                         const msm_opts* opts, void* hip_stream, uint32_t* d_out);
+
 /* The reference's CPU-only path (cpuWorkRatio = 1: submission.ts:96-115 -> msm_end_to_end,
  * lib.rs:24-44, 106-121) as the library's own multithreaded host Pippenger: signed c-bit digits,
  * 7M mixed adds into per-thread bucket tables.  window_bits 0 = auto, n_threads <= 0 = all

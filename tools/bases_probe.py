@@ -149,6 +149,18 @@ checked against Python integers.  At --fr-compare (default 20, 0: skip) two more
 "fold_vs_bases_fold", ...} with fr_fold's time beside Bases.fold's on a handle of as many bases, and {"op":
 "srs", ...} with fr_powers + mul_bases_device beside host powers, scalars_to_wire, the upload and mul_bases.
 
+With --frscan the second set of Fr entries (msm_fr_inverse*, msm_fr_scan*, msm_fr_tensor*) is swept, every row in
+this one process: for every n = 2^lg of --frscan-sizes (default 16..22) one line per operation
+
+  {"entry": "frscan", "op", "n", "ms", "ns_per_elem", "runs_ms", "fr_mul_ms", "ratio_to_fr_mul", "host_route_ms",
+   "host_parts_ms", "correct"}
+
+"inverse", "cumprod", "cumsum" and "tensor" (lg pairs), device tensors in and out, beside fr_mul (a Hadamard
+product) on the same vector -- the yardstick for the products per element -- and beside the route a caller had
+before: the vector down, Python integers (Montgomery's trick for the inverse), the result up; that route is run
+once, its download and decode and its encode and upload shared by the operations ("host_parts_ms" has the three
+parts).  Every device result is compared whole with the host route's.
+
 c runs from the unfolded pipelined width to that + 2, capped at 16 (wider windows take the 32-bit
 digit codes); --c17 adds c = 17 so that cap can be checked.  Every timed configuration is also
 checked against the closed form.  Times are host wall clock around calls that return with the
@@ -1022,6 +1034,104 @@ def fr_pass(a):
     return 1 if bad else 0
 
 
+def frscan_pass(a):
+    """--frscan: every size of the inverse / scan / tensor sweep in this one process."""
+    import numpy as np
+    import torch
+
+    import msm_amd as M
+
+    R = M.FR_MODULUS
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).cuda()
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+
+    def decode(words):
+        raw = np.ascontiguousarray(words, dtype=np.uint32).astype(">u4").tobytes()
+        return [int.from_bytes(raw[32 * i: 32 * i + 32], "big") for i in range(len(raw) // 32)]
+
+    def encode(vals):
+        return np.frombuffer(b"".join(v.to_bytes(32, "big") for v in vals), dtype=">u4").astype(np.uint32).reshape(-1, 8)
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        res = fn()
+        return res, (time.perf_counter() - t0) * 1e3
+
+    def host_inverse(vals):  # Montgomery's trick: one inversion, three products per element
+        pre, acc = [], 1
+        for v in vals:
+            pre.append(acc)
+            acc = acc * v % R
+        inv = pow(acc, -1, R)
+        out = [0] * len(vals)
+        for i in range(len(vals) - 1, -1, -1):
+            out[i] = inv * pre[i] % R
+            inv = inv * vals[i] % R
+        return out
+
+    def host_cumprod(vals):
+        out, acc = [], 1
+        for v in vals:
+            acc = acc * v % R
+            out.append(acc)
+        return out
+
+    def host_cumsum(vals):
+        out, acc = [], 0
+        for v in vals:
+            acc = (acc + v) % R
+            out.append(acc)
+        return out
+
+    def host_tensor(pairs):
+        out = [1]
+        for lo, hi in pairs:
+            out = [v * lo % R for v in out] + [v * hi % R for v in out]
+        return out
+
+    bad = 0
+    rng = np.random.default_rng(2027)
+    for lg in a.frscan_sizes:
+        n = 1 << lg
+        wa = rng.integers(0, 1 << 32, size=(n, 8), dtype=np.uint64).astype(np.uint32)
+        wb = rng.integers(0, 1 << 32, size=(n, 8), dtype=np.uint64).astype(np.uint32)
+        d_a, d_b = dev(wa), dev(wb)
+        o_n = torch.zeros((n, 8), dtype=torch.int32, device="cuda")
+        pairs = [(int.from_bytes(rng.bytes(32), "big"), int.from_bytes(rng.bytes(32), "big")) for _ in range(lg)]
+        torch.cuda.synchronize()
+        mul_ms, mul_runs, _ = timed(lambda: M.fr_mul(d_a, d_b, out=o_n), a.runs)
+        # the route a caller had: down and decode once, encode and up once, shared by the operations
+        vals, down_ms = clock(lambda: [v % R for v in decode(d_a.cpu().numpy().view(np.uint32))])
+        ops = {
+            "inverse": (lambda: M.fr_inverse(d_a, out=o_n), lambda: host_inverse(vals)),
+            "cumprod": (lambda: M.fr_cumprod(d_a, out=o_n), lambda: host_cumprod(vals)),
+            "cumsum": (lambda: M.fr_cumsum(d_a, out=o_n), lambda: host_cumsum(vals)),
+            "tensor": (lambda: M.fr_tensor(pairs, out=o_n), lambda: host_tensor(pairs)),
+        }
+        up_ms = None
+        for op, (call, host) in ops.items():
+            torch.cuda.synchronize()
+            ms, runs, _ = timed(call, a.runs)
+            exp, host_ms = clock(host)
+            if up_ms is None:
+                _, up_ms = clock(lambda: dev(encode(exp)))
+            ok = bool(np.array_equal(o_n.cpu().numpy().view(np.uint32), encode(exp)))
+            parts = {"down_decode": round(0.0 if op == "tensor" else down_ms, 2), "python": round(host_ms, 2),
+                     "encode_up": round(up_ms, 2)}
+            emit({"entry": "frscan", "op": op, "n": n, "ms": round(ms, 4), "ns_per_elem": round(ms * 1e6 / n, 3), "runs_ms": runs,
+                  "fr_mul_ms": round(mul_ms, 4), "fr_mul_runs_ms": mul_runs, "ratio_to_fr_mul": round(ms / mul_ms, 3),
+                  "host_route_ms": round(sum(parts.values()), 2), "host_parts_ms": parts, "correct": ok})
+            bad += not ok
+    return 1 if bad else 0
+
+
 def fixed_pass(a):
     """--fixed: every size of the fixed-base sweep in this one process (one context, one torch import)."""
     import numpy as np
@@ -1271,6 +1381,8 @@ def main():
     ap.add_argument("--fr-sizes", default="16,17,18,19,20,21,22", help="log2 element counts n of the Fr sweep")
     ap.add_argument("--fr-compare", type=int, default=20, help="log2 n at which fold and SRS are timed against today's routes (0: skip)")
     ap.add_argument("--fr-dot-check", type=int, default=4096, help="elements of the dot product checked against Python")
+    ap.add_argument("--frscan", action="store_true", help="the inverse / scan / tensor sweep (msm_fr_inverse* ..) instead")
+    ap.add_argument("--frscan-sizes", default="16,17,18,19,20,21,22", help="log2 element counts n of the --frscan sweep")
     ap.add_argument("--step-timeout", type=int, default=150, help="seconds each size may take")
     a = ap.parse_args()
     a.levels = [int(x) for x in str(a.levels).split(",")]
@@ -1282,6 +1394,9 @@ def main():
         for name in ("vector_bits", "vector_widths", "vector_groups"):
             setattr(a, name, [int(x) for x in str(getattr(a, name)).split(",") if x])
         return vector_pass(a)
+    if a.frscan:  # one process, as fr_mul and the host route are timed beside the rows
+        a.frscan_sizes = sorted(int(x) for x in str(a.frscan_sizes).split(",") if x)
+        return frscan_pass(a)
     if a.fr:  # one process, as the yardsticks are timed beside the rows
         a.fr_sizes = sorted(int(x) for x in str(a.fr_sizes).split(",") if x)
         return fr_pass(a)

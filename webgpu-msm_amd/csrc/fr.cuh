@@ -2,8 +2,8 @@
 // 2^32, the canonical test a < r and the conversion out of Montgomery form, v = a 2^-256 mod r, which
 // the wide scalar types need (include/msm.h MSM_FIELD_FR_MONT); and below them the arithmetic mod r of
 // the Fr vector entries (msm_fr_*): Montgomery product, sum, difference, conversion into Montgomery
-// form.  Host and device run this one code: the host entries' range checks (host_bases.h, host_fr.h), the
-// kernels (k_recode_wide, fr_kernels.cuh) and the test hooks.
+// form, inverse.  Host and device run this one code: the host entries' range checks (host_bases.h,
+// host_fr.h), the kernels (k_recode_wide, fr_kernels.cuh, fr_scan_kernels.cuh) and the test hooks.
 // Values are 8 x uint32, LITTLE-endian words (index 0 least significant): the memory of an arkworks
 // Fr -- four little-endian u64 limbs -- read as words on a little-endian machine.
 #pragma once
@@ -175,6 +175,64 @@ __host__ __device__ inline void fr_sub(const uint32_t a[8], const uint32_t b[8],
 __host__ __device__ inline void fr_to_mont(const uint32_t a[8], uint32_t out[8]) {
   constexpr FrWords R2 = fr_r_power(2);
   fr_mont_mul(a, R2.v, out);
+}
+
+// Word k of the constant exponent r - 2, as selects on k (no table in memory: k is uniform in a kernel).
+__host__ __device__ inline uint32_t fr_inv_exp_word(int k) {
+  constexpr FrWords R = fr_modulus();
+  static_assert(R.v[0] >= 2, "r - 2 borrows from no word");
+  return k == 0 ? R.v[0] - 2u : k == 1 ? R.v[1] : k == 2 ? R.v[2] : k == 3 ? R.v[3] : k == 4 ? R.v[4] : k == 5 ? R.v[5]
+         : k == 6 ? R.v[6] : R.v[7];
+}
+// The products of one fr_inv: 62 windows of four squarings and tab[2] = a^2; tab[3..15] and one product per
+// non-zero window below the top one (three of the 62 nibbles of r - 2 are zero).
+constexpr uint32_t FR_INV_SQUARINGS = 62 * 4 + 1, FR_INV_PRODUCTS = 13 + 59;
+
+// tab[e] = a^e for e = 2 .. E from tab[1] = a, by recursion: every index is a constant, so the table of a
+// kernel stays in registers whatever the unroller makes of a loop this large.
+template <int E>
+__host__ __device__ inline __attribute__((always_inline)) void fr_inv_table(uint32_t (&tab)[16][8]) {
+  if constexpr (E > 2) fr_inv_table<E - 1>(tab);
+  fr_mont_mul(tab[E - 1], tab[1], tab[E]);
+}
+
+// out = a^-1 for a < r in Montgomery form, in Montgomery form (a^-1 2^256 mod r), and 0 for a = 0: a^(r - 2)
+// by a fixed 4-bit window over the constant exponent, top nibble first -- the table a^1 .. a^15, then per
+// nibble four squarings and, where the nibble is not zero, one product by its table entry, which is read
+// with selects (no indexed private memory).  The chain is FR_INV_SQUARINGS + FR_INV_PRODUCTS = 321
+// dependent fr_mont_mul long; every branch is on the exponent, none on a, so lanes never diverge.
+// `out` may alias `a`.
+__host__ __device__ inline void fr_inv(const uint32_t a[8], uint32_t out[8]) {
+  constexpr FrWords R = fr_modulus();
+  constexpr uint32_t top = R.v[7] >> 24;  // nibble 62 of r - 2; nibble 63 is zero
+  static_assert(top >= 1 && top < 16, "r has 63 nibbles");
+  uint32_t tab[16][8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) tab[1][j] = a[j];
+  fr_inv_table<15>(tab);
+  uint32_t acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = tab[top][j];
+#pragma unroll 1
+  for (int i = 61; i >= 0; i--) {
+#pragma unroll 1
+    for (int s = 0; s < 4; s++) fr_mont_mul(acc, acc, acc);
+    const uint32_t w = (fr_inv_exp_word(i >> 3) >> (4 * (i & 7))) & 15u;
+    if (w) {
+      uint32_t x[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) x[j] = tab[1][j];
+#pragma unroll
+      for (int e = 2; e < 16; e++) {
+        const bool take = w == (uint32_t)e;
+#pragma unroll
+        for (int j = 0; j < 8; j++) x[j] = take ? tab[e][j] : x[j];
+      }
+      fr_mont_mul(acc, x, acc);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; j++) out[j] = acc[j];
 }
 
 }  // namespace msm

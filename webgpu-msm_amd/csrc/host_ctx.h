@@ -220,7 +220,8 @@ struct Workspace {
   Buf dx_pts;              // k_decompress_x's output: x|y of a compressed creation, wire records of msm_decompress_points
   Buf fx_proj;             // k_fixed_eval's points (X : Y : Z) in blocks of 64, read by k_fixed_normalise (msm_fixed_mul*)
   Buf vx_part;             // k_vector_eval's partial sums (X : Y : Z : T) per part and block, and k_vector_fold's two halves
-  Buf fr_part;             // k_fr_dot_partial's sums, one element per workgroup, and k_fr_dot_final's result after them (msm_fr_dot*)
+  Buf fr_part;             // k_fr_dot_partial's sums, one element per workgroup, and k_fr_dot_final's result after them (msm_fr_dot*);
+                           // k_fr_scan_spans' totals, one per span, which k_fr_scan_totals turns into carries (msm_fr_scan*)
 #ifdef MSM_DUMMY_ALLOC
   Buf dummy_tiles, dummy_cursor;  // tuning builds: the round-5 allocation layout
 #endif

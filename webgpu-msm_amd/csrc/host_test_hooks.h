@@ -643,6 +643,49 @@ int msm_test_fr_op(uint32_t op, const uint32_t* a_le, const uint32_t* b_le, uint
   return MSM_OK;
 }
 
+// fr.cuh's fr_inv on the host, the code k_fr_inverse runs once per tile: n values of 8 little-endian words
+// each, canonical and in Montgomery form (a >= r: MSM_ERR_INVALID_ARG); out_i = a_i^-1 in Montgomery form,
+// 0 for 0.
+int msm_test_fr_inv(const uint32_t* a_le, uint32_t* out_le, size_t n) {
+  if ((!a_le || !out_le) && n) return MSM_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n; i++) {
+    if (!fr_is_canonical(a_le + 8 * i)) return MSM_ERR_INVALID_ARG;
+    fr_inv(a_le + 8 * i, out_le + 8 * i);
+  }
+  return MSM_OK;
+}
+
+// The shape of the second set of Fr kernels: out = {FR_TILE_E, FR_TILE, FR_SCAN_CAP, k_fr_inverse's grid
+// cap, fr_inv's squarings, fr_inv's products, MSM_FR_TENSOR_MAX_K, 0}.
+int msm_test_fr_scan_constants(uint32_t out[8]) {
+  if (!out) return MSM_ERR_INVALID_ARG;
+  const uint32_t v[8] = {FR_TILE_E, FR_TILE, FR_SCAN_CAP, FR_COMBINE_CAP, FR_INV_SQUARINGS, FR_INV_PRODUCTS, FR_TENSOR_MAX_K, 0};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// The plan of a scan of m elements over at most grid_cap spans, as msm_fr_scan* makes it (fr_scan_plan):
+// out = {elements per lane, elements per tile, workgroups, tiles per span}.  Host code only.
+int msm_test_fr_scan_plan(size_t m, uint32_t grid_cap, uint32_t out[4]) {
+  if (!out || !grid_cap || m >= (1ull << 32)) return MSM_ERR_INVALID_ARG;
+  const FrScanPlan pl = fr_scan_plan(m, grid_cap);
+  const uint32_t v[4] = {pl.e, pl.tile, pl.grid, pl.tiles_per_span};
+  memcpy(out, v, sizeof(v));
+  return MSM_OK;
+}
+
+// msm_fr_scan_device and msm_fr_inverse_device on the current device and the null stream with a
+// caller-given grid cap (1 .. FR_SCAN_CAP for a scan), so that spans of several tiles and workgroups
+// striding over tiles are reached at a few thousand elements.  Everything else is the entries' own path.
+int msm_test_fr_scan_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t flags, uint32_t in_form,
+                            uint32_t out_form, uint32_t grid_cap, uint32_t* d_out) {
+  return fr_scan(d_a, c_be, m, flags, in_form, out_form, false, nullptr, (hipStream_t)MSM_STREAM_NULL, d_out, grid_cap);
+}
+int msm_test_fr_inverse_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t in_form, uint32_t out_form,
+                               uint32_t grid_cap, uint32_t* d_out) {
+  return fr_inverse(d_a, c_be, m, in_form, out_form, false, nullptr, (hipStream_t)MSM_STREAM_NULL, d_out, grid_cap);
+}
+
 // The dense-bucket part of the plan of a narrow launch (msm_bases_compute* with MSM_FLAG_SCALAR_BITS)
 // of nm MSMs of n terms at width window_bits (0: auto), pipelined or lone: out = {dense (0 / 1),
 // entries per unit lane E, keys W * B, the unit kernel's grid bound, run length K}, for the default

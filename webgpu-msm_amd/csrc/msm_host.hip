@@ -59,6 +59,7 @@ namespace {
 #include "host_fixed.h"
 #include "host_combine.h"
 #include "host_fr.h"
+#include "host_fr_scan.h"
 }  // namespace
 #include "host_test_hooks.h"
 
@@ -498,6 +499,36 @@ int msm_fr_dot(const uint32_t* a, const uint32_t* b, size_t n, uint32_t in_form,
 int msm_fr_dot_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t in_form, uint32_t out_form,
                       const msm_opts* opts, void* hip_stream, uint32_t out[8]) {
   return fr_dot(d_a, d_b, n, in_form, out_form, false, opts, (hipStream_t)hip_stream, out);
+}
+
+int msm_fr_inverse(const uint32_t* a, const uint32_t* c_be, size_t m, uint32_t in_form, uint32_t out_form,
+                   const msm_opts* opts, uint32_t* out) {
+  return fr_inverse(a, c_be, m, in_form, out_form, true, opts, nullptr, out);
+}
+
+int msm_fr_inverse_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t in_form, uint32_t out_form,
+                          const msm_opts* opts, void* hip_stream, uint32_t* d_out) {
+  return fr_inverse(d_a, c_be, m, in_form, out_form, false, opts, (hipStream_t)hip_stream, d_out);
+}
+
+int msm_fr_scan(const uint32_t* a, const uint32_t* c_be, size_t m, uint32_t flags, uint32_t in_form, uint32_t out_form,
+                const msm_opts* opts, uint32_t* out) {
+  return fr_scan(a, c_be, m, flags, in_form, out_form, true, opts, nullptr, out);
+}
+
+int msm_fr_scan_device(const uint32_t* d_a, const uint32_t* c_be, size_t m, uint32_t flags, uint32_t in_form,
+                       uint32_t out_form, const msm_opts* opts, void* hip_stream, uint32_t* d_out) {
+  return fr_scan(d_a, c_be, m, flags, in_form, out_form, false, opts, (hipStream_t)hip_stream, d_out);
+}
+
+int msm_fr_tensor(const uint32_t* lo_be, const uint32_t* hi_be, uint32_t k, const uint32_t* c_be, uint32_t out_form,
+                  const msm_opts* opts, uint32_t* out) {
+  return fr_tensor(lo_be, hi_be, k, c_be, out_form, true, opts, nullptr, out);
+}
+
+int msm_fr_tensor_device(const uint32_t* lo_be, const uint32_t* hi_be, uint32_t k, const uint32_t* c_be, uint32_t out_form,
+                         const msm_opts* opts, void* hip_stream, uint32_t* d_out) {
+  return fr_tensor(lo_be, hi_be, k, c_be, out_form, false, opts, (hipStream_t)hip_stream, d_out);
 }
 
 int msm_combine_partials(const uint32_t* partials_xyzt_be, size_t count, uint32_t out_xy_be[16]) {

@@ -3977,3 +3977,4 @@ __global__ void __launch_bounds__(64) k_test_limbs_lane(const uint32_t* __restri
 }  // namespace msm
 
 #include "fr_kernels.cuh"
+#include "fr_scan_kernels.cuh"

@@ -31,6 +31,7 @@ __all__ = [
     "MsmOptsTyped", "MSM_FLAG_SCALAR_TYPE", "SCALAR_TYPES", "scalars_to_native",
     "MSM_FLAG_SCALAR_FIELD", "WIDE_TYPES", "FR_MODULUS", "scalars_to_wide",
     "FR_FORMS", "fr_combine", "fr_fold", "fr_mul", "fr_convert", "fr_powers", "fr_dot", "fr_to_ints",
+    "fr_inverse", "fr_cumprod", "fr_cumsum", "fr_tensor", "MSM_FR_SCAN_SUM", "MSM_FR_SCAN_EXCLUSIVE",
 ]
 
 P = 8444461749428370424248824938781546531375899335154063827935233455917409239041
@@ -115,6 +116,8 @@ class FrCombine(ctypes.Structure):
 MSM_FR_SUB = 1  # out_i = x_i a_i - y_i b_i (include/msm.h)
 MSM_FR_X_BROADCAST = 2  # x holds one element, used for every i
 MSM_FR_Y_BROADCAST = 4  # likewise y
+MSM_FR_SCAN_SUM = 1  # msm_fr_scan*: the running sum instead of the running product
+MSM_FR_SCAN_EXCLUSIVE = 2  # out_i over j < i instead of j <= i
 FR_FORMS = {"wire": 0, "fr_mont": 1}  # MSM_FR_WIRE, MSM_FR_MONT: the names scalar_type uses
 MSM_COMBINE_SUB = 1  # R_i = a_i A_i - b_i B_i (include/msm.h)
 MSM_COMBINE_A_BROADCAST = 2  # a_scalars holds one scalar, used for every i
@@ -255,6 +258,19 @@ def load() -> ctypes.CDLL:
         "msm_fr_dot": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, u32p], ctypes.c_int),
         "msm_fr_dot_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, vp, u32p], ctypes.c_int),
         "msm_test_fr_op": ([ctypes.c_uint32, vp, vp, vp, sz], ctypes.c_int),
+        "msm_fr_inverse": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, vp], ctypes.c_int),
+        "msm_fr_inverse_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, optp, vp, vp], ctypes.c_int),
+        "msm_fr_scan": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, optp, vp], ctypes.c_int),
+        "msm_fr_scan_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, optp, vp, vp],
+                               ctypes.c_int),
+        "msm_fr_tensor": ([vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32, optp, vp], ctypes.c_int),
+        "msm_fr_tensor_device": ([vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32, optp, vp, vp], ctypes.c_int),
+        "msm_test_fr_inv": ([vp, vp, sz], ctypes.c_int),
+        "msm_test_fr_scan_constants": ([u32p], ctypes.c_int),
+        "msm_test_fr_scan_plan": ([sz, ctypes.c_uint32, u32p], ctypes.c_int),
+        "msm_test_fr_scan_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp],
+                                    ctypes.c_int),
+        "msm_test_fr_inverse_device": ([vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp], ctypes.c_int),
         "msm_test_fixed_digits": ([vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.POINTER(ctypes.c_int32), u32p, u32p], ctypes.c_int),
         "msm_test_fixed_plan": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p], ctypes.c_int),
@@ -1668,6 +1684,96 @@ def fr_dot(a, b=None, form: str = "wire", out_form: Optional[str] = None, device
     return res
 
 
+def _fr_word(c: Optional[int]):
+    """One int as the 8 wire words the entries take for `c` (None: NULL, the factor 1)."""
+    return None if c is None else scalars_to_wire([int(c) % (1 << 256)])
+
+
+def _fr_unary(host_name: str, dev_name: str, a, cw, extra: tuple, form: str, out_form: Optional[str], out, device: int,
+              stream: int, grid_cap: Optional[int] = None):
+    """The calling convention of msm_fr_inverse* and msm_fr_scan* (`extra`: the words between m and the
+    forms): numpy in, numpy out through the host entry; a device tensor in, a device tensor out -- `out`
+    if given, which may be `a` itself -- through the device entry, or its test hook with `grid_cap`."""
+    out_form = form if out_form is None else out_form
+    fi, fo = _fr_form(form), _fr_form(out_form)
+    cp = None if cw is None else _ptr(cw)
+    L = load()
+    if _fr_on_device(a):
+        m = _fr_rows(a)
+        if out is None:
+            import torch
+
+            out = torch.empty_like(a) if fi == fo else torch.empty((m, 8), dtype=torch.int32, device=a.device)
+        elif not _fr_on_device(out) or _fr_rows(out) != m:
+            raise ValueError("out must be a device tensor of the operand's length")
+        pa = _dev_ptr(a) if m else None
+        if grid_cap is not None:
+            _check(getattr(L, "msm_test_" + dev_name[4:])(pa, cp, m, *extra, fi, fo, int(grid_cap), _dev_ptr(out)),
+                   "msm_test_" + dev_name[4:])
+        else:
+            _check(getattr(L, dev_name)(pa, cp, m, *extra, fi, fo, _opts(None, device=a.device.index), _stream(stream, a, out),
+                                        _dev_ptr(out)), dev_name)
+        return out
+    if out is not None or grid_cap is not None:
+        raise ValueError("out= is for device tensors")
+    a = _fr_host(a, form)
+    res = np.zeros((a.shape[0], 8), dtype=np.uint32)
+    _check(getattr(L, host_name)(_ptr(a), cp, a.shape[0], *extra, fi, fo, _opts(None, device=device), _ptr(res)), host_name)
+    return res
+
+
+def fr_inverse(a, scale: Optional[int] = None, form: str = "wire", out_form: Optional[str] = None, out=None,
+               device: int = -1, stream: int = 0):
+    """scale * a_i^-1 mod r (scale None: 1), and 0 where a_i is 0 mod r -- arkworks' batch_inversion_and_mul.
+    `out` may be the device tensor `a` itself."""
+    return _fr_unary("msm_fr_inverse", "msm_fr_inverse_device", a, _fr_word(scale), (), form, out_form, out, device, stream)
+
+
+def fr_cumprod(a, first: Optional[int] = None, exclusive: bool = False, form: str = "wire", out_form: Optional[str] = None,
+               out=None, device: int = -1, stream: int = 0):
+    """The running product first * a_0 * .. * a_i (first None: 1); exclusive: first * a_0 * .. * a_(i-1), which
+    starts at `first`.  `out` may be the device tensor `a` itself."""
+    return _fr_unary("msm_fr_scan", "msm_fr_scan_device", a, _fr_word(first), (MSM_FR_SCAN_EXCLUSIVE if exclusive else 0,),
+                     form, out_form, out, device, stream)
+
+
+def fr_cumsum(a, exclusive: bool = False, form: str = "wire", out_form: Optional[str] = None, out=None, device: int = -1,
+              stream: int = 0):
+    """The running sum a_0 + .. + a_i; exclusive: a_0 + .. + a_(i-1), which starts at 0."""
+    return _fr_unary("msm_fr_scan", "msm_fr_scan_device", a, None,
+                     (MSM_FR_SCAN_SUM | (MSM_FR_SCAN_EXCLUSIVE if exclusive else 0),), form, out_form, out, device, stream)
+
+
+def fr_tensor(pairs, first: Optional[int] = None, out_form: str = "wire", out=None, device: Optional[int] = None,
+              stream: int = 0):
+    """first * prod_j (bit_j(i) ? hi_j : lo_j) mod r for i < 2^k, from k pairs (lo_j, hi_j) of ints, pair j on
+    bit j of the index (first None: 1).  A numpy [2^k, 8] uint32 from the host entry; with `device` (a HIP
+    ordinal) or a device tensor `out`, a device tensor from the device entry, as fr_powers."""
+    fo = _fr_form(out_form)
+    pairs = [(int(lo) % (1 << 256), int(hi) % (1 << 256)) for lo, hi in pairs]
+    k = len(pairs)
+    if k > 31:
+        raise MsmError(-1, "msm_fr_tensor")
+    n = 1 << k
+    lo = scalars_to_wire([p[0] for p in pairs] or [0])
+    hi = scalars_to_wire([p[1] for p in pairs] or [0])
+    cw = _fr_word(first)
+    cp = None if cw is None else _ptr(cw)
+    if out is None and device is None:
+        res = np.zeros((n, 8), dtype=np.uint32)
+        _check(load().msm_fr_tensor(_ptr(lo), _ptr(hi), k, cp, fo, _opts(None), _ptr(res)), "msm_fr_tensor")
+        return res
+    if out is None:
+        import torch
+
+        out = torch.empty((n, 8), dtype=torch.int32, device=f"cuda:{int(device)}")
+    elif not _fr_on_device(out) or _fr_rows(out) != n:
+        raise ValueError("out must be a device tensor of 2^k elements")
+    _check(load().msm_fr_tensor_device(_ptr(lo), _ptr(hi), k, cp, fo, _opts(None, device=out.device.index),
+                                       _stream(stream, out), _dev_ptr(out)), "msm_fr_tensor_device")
+    return out
+
+
 def compute_msm_many(points_list, scalars_list, n: int, window_size: Optional[int] = None,
                      run_length: Optional[int] = None, device: int = -1, flags: int = 0,
                      devices: Optional[Sequence[int]] = None) -> np.ndarray:
@@ -2089,6 +2195,54 @@ def _test_fr_constants() -> dict:
     raw = out[:32].astype("<u4").tobytes()
     return {"r_powers": [int.from_bytes(raw[32 * k: 32 * k + 32], "little") for k in range(4)],
             "threads": int(out[32]), "dot_cap": int(out[33]), "combine_cap": int(out[34]), "pow_steps": int(out[35])}
+
+
+def _test_fr_inv(values) -> list:
+    """csrc/fr.cuh's fr_inv on the host (msm_test_fr_inv; no GPU needed): for every a < r in Montgomery form,
+    a^-1 in Montgomery form, 0 for 0.  MsmError -1 for a value at or above r."""
+    vals = [int(v) for v in values]
+    buf = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype="<u4").astype(np.uint32)
+    out = np.zeros(max(len(vals), 1) * 8, dtype=np.uint32)
+    _check(load().msm_test_fr_inv(_ptr(buf) if len(vals) else None, _ptr(out), len(vals)), "msm_test_fr_inv")
+    raw = out.astype("<u4").tobytes()
+    return [int.from_bytes(raw[32 * i: 32 * i + 32], "little") for i in range(len(vals))]
+
+
+def _test_fr_scan_constants() -> dict:
+    """The shape of k_fr_inverse, k_fr_scan_* and k_fr_tensor (msm_test_fr_scan_constants; no GPU needed):
+    elements per lane and per tile, the most spans of a scan, k_fr_inverse's grid cap, the squarings and
+    products of one fr_inv, the largest k of a tensor product."""
+    out = np.zeros(8, dtype=np.uint32)
+    _check(load().msm_test_fr_scan_constants(out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+           "msm_test_fr_scan_constants")
+    keys = ("e", "tile", "scan_cap", "inverse_cap", "inv_squarings", "inv_products", "tensor_max_k")
+    return {k: int(v) for k, v in zip(keys, out)}
+
+
+def _test_fr_scan_plan(m: int, grid_cap: int) -> dict:
+    """The launch plan of a scan of m elements over at most grid_cap spans, as msm_fr_scan* makes it
+    (msm_test_fr_scan_plan; no GPU needed)."""
+    if not (0 <= int(m) < (1 << 64) and 0 <= int(grid_cap) < (1 << 32)):
+        raise MsmError(-1, "msm_test_fr_scan_plan")
+    out = np.zeros(4, dtype=np.uint32)
+    _check(load().msm_test_fr_scan_plan(int(m), int(grid_cap), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+           "msm_test_fr_scan_plan")
+    return {"e": int(out[0]), "tile": int(out[1]), "grid": int(out[2]), "tiles_per_span": int(out[3])}
+
+
+def _test_fr_inverse_device(a, grid_cap: int, scale: Optional[int] = None, form: str = "wire",
+                            out_form: Optional[str] = None, out=None):
+    """fr_inverse of a device tensor with at most grid_cap workgroups (msm_test_fr_inverse_device)."""
+    return _fr_unary("msm_fr_inverse", "msm_fr_inverse_device", a, _fr_word(scale), (), form, out_form, out, -1, 0,
+                     grid_cap=grid_cap)
+
+
+def _test_fr_scan_device(a, grid_cap: int, first: Optional[int] = None, sum: bool = False, exclusive: bool = False,
+                         form: str = "wire", out_form: Optional[str] = None, out=None):
+    """fr_cumprod / fr_cumsum of a device tensor over at most grid_cap spans (msm_test_fr_scan_device)."""
+    flags = (MSM_FR_SCAN_SUM if sum else 0) | (MSM_FR_SCAN_EXCLUSIVE if exclusive else 0)
+    return _fr_unary("msm_fr_scan", "msm_fr_scan_device", a, _fr_word(first), (flags,), form, out_form, out, -1, 0,
+                     grid_cap=grid_cap)
 
 
 def _test_native_plan(n: int, scalar_type, scalar_bits: int, window_size: int = 0) -> dict:
